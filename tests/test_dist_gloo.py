@@ -96,3 +96,49 @@ def test_bench_config3_two_ranks_rehearsal(pkg, tmp_path, T_sweep):
         assert np.array_equal(st["inner_iters"], expect) and np.array_equal(z["X"][:, 0, 0], expect.astype(float))
         # ... and the shards were built from the global index: the gathered initial controls are rows of the one-piece sweep
         assert np.array_equal(z["U"][:, :, 0], whole.U0[expect][:, :, 0])
+
+
+def test_bench_dump_outputs_rehearsal(pkg, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step computed, float64, and the same inputs give the same files
+    (one rank over gloo, the solver stubbed as above: its "results" carry the global index of their trajectory)"""
+    root = os.path.dirname(HERE)
+    T_sweep, N = 10, 12
+    dirs = []
+    for run in range(2):
+        d = tmp_path / f"dump{run}"
+        env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()),
+                   TSAT_BENCH_REHEARSAL=os.path.join(HERE, "bench_stub.py"), TSAT_BENCH_REHEARSAL_T=str(T_sweep),
+                   TSAT_BENCH_REHEARSAL_N=str(N), OMP_NUM_THREADS="2")
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "3", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        dirs.append(d)
+    names = sorted(f.name for f in dirs[0].iterdir())
+    assert names == sorted(["sample_index.npy", "X.npy", "U.npy"] + [f"stats_{f}.npy" for f in pkg._abi.STATS_DTYPE.names])
+    assert names == sorted(f.name for f in dirs[1].iterdir())
+    for f in names:
+        a, b = np.load(dirs[0] / f), np.load(dirs[1] / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    assert np.array_equal(np.load(dirs[0] / "sample_index.npy"), np.arange(T_sweep))     # small enough to be dumped whole
+    assert np.load(dirs[0] / "X.npy").shape == (T_sweep, N, 7) and np.load(dirs[0] / "U.npy").shape == (T_sweep, N - 1, 3)
+    assert np.array_equal(np.load(dirs[0] / "X.npy")[:, 0, 0], np.arange(T_sweep))
+    assert np.array_equal(np.load(dirs[0] / "stats_inner_iters.npy"), np.arange(T_sweep))
+
+
+def test_bench_dump_outputs_sample_of_a_large_batch(pkg, tmp_path):
+    """a batch too large to dump whole (the 65536 x 1000-knot sweep) is dumped on a fixed, seeded sample: under 64 MB in all"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import bench
+    T, N = 65536, 1000
+    ids = np.arange(T, dtype=np.float64)
+    traj = {"X": np.broadcast_to(ids[:, None, None], (T, N, 7)), "U": np.broadcast_to(ids[:, None, None], (T, N - 1, 3))}
+    stats = np.zeros(T, dtype=pkg._abi.STATS_DTYPE)
+    stats["inner_iters"] = np.arange(T)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), traj, stats)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert 1 < len(idx) < T and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "sample_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "X.npy")[:, 0, 0], idx) and np.array_equal(np.load(tmp_path / "a" / "U.npy")[:, -1, 2], idx)
+    assert np.array_equal(np.load(tmp_path / "a" / "stats_inner_iters.npy"), np.arange(T))

@@ -11,13 +11,13 @@ PART="${PART:-AB}"     # A: configs[1], pipeline, experiment, batch sizes; B: co
                        # S: the configs[3] shard entry of the default line on its own (bench entry, kernel statistics, PMC passes)
                        # L: the bench lines alone, once more (after the PMC summaries of A / P / B have been committed: the lines then carry `roofline.traffic`)
 if [[ "$PART" == *A* || "$PART" == *L* ]]; then
-python3 bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+python3 bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 fi
 if [[ "$PART" == *L* ]]; then
-python3 bench.py --config 2 --precision 64 --steps 3 --warmup 1 --cpu-seconds 8 > "$OUT/bench_c2_fp64.json" 2> "$OUT/bench_c2_fp64.err"
-python3 bench.py --config 2 --steps 3 --warmup 1 --cpu-seconds 8 > "$OUT/bench_c2_mixed.json" 2> "$OUT/bench_c2_mixed.err"
-python3 bench.py --config 4 --steps 2 --warmup 1 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
-python3 bench.py --config 3 --steps 2 --warmup 1 --cpu-seconds 8 --gather none > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
+python3 bench.py --full --config 2 --precision 64 --steps 3 --warmup 1 --cpu-seconds 8 > "$OUT/bench_c2_fp64.json" 2> "$OUT/bench_c2_fp64.err"
+python3 bench.py --full --config 2 --steps 3 --warmup 1 --cpu-seconds 8 > "$OUT/bench_c2_mixed.json" 2> "$OUT/bench_c2_mixed.err"
+python3 bench.py --full --config 4 --steps 2 --warmup 1 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
+python3 bench.py --full --config 3 --steps 2 --warmup 1 --cpu-seconds 8 --gather none > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
 fi
 if [[ "$PART" == *A* || "$PART" == *P* ]]; then      # P: the rocprofv3 passes of configs[1] alone
 cd /tmp && export TMPDIR=/tmp
@@ -45,9 +45,9 @@ fi
 if [[ "$PART" == *B* ]]; then
 # larger configurations on this one GPU: configs[2] shape in fp64 (packed build) and as quoted (fp32), a configs[3] shard of
 # 8192 trajectories per GPU (what each of 8 GPUs gets), configs[4]; kernel statistics and PMC passes of the fp64 16384 run
-python3 bench.py --config 2 --precision 64 --steps 3 --warmup 1 --cpu-seconds 8 > "$OUT/bench_c2_fp64.json" 2> "$OUT/bench_c2_fp64.err"
-python3 bench.py --config 2 --steps 3 --warmup 1 --cpu-seconds 8 > "$OUT/bench_c2_mixed.json" 2> "$OUT/bench_c2_mixed.err"
-python3 bench.py --config 4 --steps 2 --warmup 1 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
+python3 bench.py --full --config 2 --precision 64 --steps 3 --warmup 1 --cpu-seconds 8 > "$OUT/bench_c2_fp64.json" 2> "$OUT/bench_c2_fp64.err"
+python3 bench.py --full --config 2 --steps 3 --warmup 1 --cpu-seconds 8 > "$OUT/bench_c2_mixed.json" 2> "$OUT/bench_c2_mixed.err"
+python3 bench.py --full --config 4 --steps 2 --warmup 1 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
 cd /tmp
 C2="python3 $ROOT/bench.py --config 2 --precision 64 --steps 2 --warmup 1 --no-cpu-baseline --gather none"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_c2" -o run -- $C2 > /dev/null 2> "$OUT/stats_c2.err"
@@ -64,7 +64,7 @@ rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY
   --output-format csv -d "$OUT/pmc_sq_c2mixed" -o run -- $C2F > /dev/null 2> "$OUT/pmc_sq_c2mixed.err"
 echo "configs[2] mixed passes done" > "$OUT/progress.txt"
 cd "$ROOT"
-python3 bench.py --config 3 --steps 2 --warmup 1 --cpu-seconds 8 --gather none > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
+python3 bench.py --full --config 3 --steps 2 --warmup 1 --cpu-seconds 8 --gather none > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
 cd /tmp
 C3="python3 $ROOT/bench.py --config 3 --steps 1 --warmup 1 --no-cpu-baseline --gather none"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_c3" -o run -- $C3 > /dev/null 2> "$OUT/stats_c3.err"
