@@ -289,6 +289,37 @@ int  tsat_tvlqr_resident(tsat_handle* h, const tsat_tvlqr_options* o, const doub
                          const double* Rd, const double* x0_sim, const double* noise,
                          double* X_sim, double* U_sim, double* K_lqr, tsat_tvlqr_stats* stats, const int64_t* noise_id);
 
+/* Closed-loop tracking of T solved slews under M noise realisations each: TVLQR gains once per slew, then M plants
+ * (one Monte-Carlo trial of src/monte_carlo.jl:199-262 per realisation; lane of a wavefront = realisation).
+ *   everything up to Rd        as for tsat_tvlqr_batch (same shapes, same meaning)
+ *   M                          realisations per slew, 1 .. 65535
+ *   x0_sim     7 x M x T       perturbed initial state of realisation m of slew t (x0_lqr, src/monte_carlo.jl:204-210)
+ *   noise_id0  T or NULL       realisation m of slew t draws generator id noise_id0[t] + m  (NULL: t * M + m),
+ *                              with the draw layout documented at tsat_tvlqr_options (Philox4x32-10, counters id, knot, stage)
+ *   n_knots    T or NULL       per-slew horizons as for tsat_tvlqr_batch
+ *   stats      M x T   out     the slew-time statistic of every realisation (realisation fastest)
+ *   summary    8 x T   out     per slew, from `stats`, summed in realisation order on the host:
+ *                              [0] M  [1] failures  [2] mean slew_time of the realisations that did not fail (0 if none)
+ *                              [3] min and [4] max of the same (0 if none)
+ *                              [5] mean slew_time of all M (a failure counts dt * n_knots, as `slew_time[i]` does, src/monte_carlo.jl:237)
+ *                              [6] max final_angle  [7] max final_w_norm
+ *   stats_nominal T out, may be NULL   statistic of the noise-free plant started at the plan's own first state X[:,1,t]
+ *   K_lqr      3 x 6 x (N-1) x T out, may be NULL     the gains, as tsat_tvlqr_batch returns them
+ *   X_sim      7 x N x M x T out, may be NULL         every simulated state (for tests and plots; not a fast path)
+ * Realisation (t, m) is exactly what tsat_tvlqr_batch computes for slew t with x0_sim = x0_sim[:, m, t], noise_mode = 1,
+ * noise_id = noise_id0[t] + m; the statistic is evaluated while the roll-out runs.
+ * o->noise_mode must be 1 (the noise is drawn in the kernel; an array would be 36 (N-1) M T doubles) and
+ * o->rate_as_written must be 0 (that reading needs a sample that may lie after the one being judged); both are rejected with -1. */
+int  tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                         const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* K_lqr, double* X_sim);
+/* text of the last failure of tsat_tvlqr_ensemble on the calling thread ("" if none) */
+const char* tsat_ensemble_last_error(void);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Receding-horizon re-solve on the RESIDENT batch (BASELINE.json configs[4]). NOT in the reference —
  * it tracks its plan with TVLQR (src/attitude_controller.jl:1-48); defined here as: n_steps times

@@ -308,6 +308,31 @@ function attitude_simulation_resident(s::HIPSolver, p::BatchProblem, x0_lqr::Mat
 end
 
 """
+attitude_ensemble(s, p, x0_lqr, Q_lqr, Qf_lqr, R_lqr; noise_id0, opts, want_K, want_trajectories) — `tsat_tvlqr_ensemble`:
+every solved slew of `p` tracked under M = size(x0_lqr, 2) noise realisations (x0_lqr 7 x M x T), the gains once per slew.
+`opts.noise_mode` must be 1. Returns (stats M x T, summary 8 x T, nominal T, K or nothing, X_sim 7 x N x M x T or nothing).
+"""
+function attitude_ensemble(s::HIPSolver, p::BatchProblem, x0_lqr::Array{Float64,3}, Q_lqr::Matrix{Float64},
+                           Qf_lqr::Matrix{Float64}, R_lqr::Matrix{Float64}; noise_id0::Vector{Int64} = Int64[],
+                           opts::TvlqrOptions = TvlqrOptions(noise_mode = 1), want_K::Bool = false,
+                           want_trajectories::Bool = false)
+    T = size(p.x0, 2); N = p.N; M = size(x0_lqr, 2)
+    opts.n_knots = N; opts.n_tab = size(p.B_ECI, 2)
+    st = Matrix{TvlqrStats}(undef, M, T); nominal = Vector{TvlqrStats}(undef, T); summary = zeros(8, T)
+    K = want_K ? zeros(3, 6, N - 1, T) : nothing
+    Xs = want_trajectories ? zeros(7, N, M, T) : nothing
+    rc = ccall((:tsat_tvlqr_ensemble, LIB), Cint,
+        (Ptr{Cvoid}, Ref{TvlqrOptions}, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Int64}, Ptr{Int32}, Ptr{TvlqrStats}, Ptr{Float64}, Ptr{TvlqrStats}, Ptr{Float64}, Ptr{Float64}),
+        s.handle, opts, T, size(p.B_ECI, 3), M, p.X, p.U, p.xf, p.B_ECI, p.btab_idx, p.tau0, p.dtau, p.dt, p.J,
+        Q_lqr, Qf_lqr, R_lqr, x0_lqr, isempty(noise_id0) ? C_NULL : noise_id0, isempty(p.n_knots) ? C_NULL : p.n_knots,
+        st, summary, nominal, K === nothing ? C_NULL : K, Xs === nothing ? C_NULL : Xs)
+    rc == 0 || error("tsat_tvlqr_ensemble failed ($rc): " * unsafe_string(ccall((:tsat_ensemble_last_error, LIB), Cstring, ())))
+    return st, summary, nominal, K, Xs
+end
+
+"""
 receding_horizon!(s, p, n_steps; plant_integrator = 4) — `tsat_mpc_run` on the batch `p` (uploaded here): re-solve the
 horizon every control step with the budget of `s.opts`, apply U[:,1] to the noise-free plant, shift the plan.
 No reference equivalent (BASELINE.json configs[4]). Returns X_hist 7×(n_steps+1)×T, U_hist 3×n_steps×T.

@@ -119,6 +119,10 @@ PROTOTYPES = {
     "tsat_tvlqr_default_options": (None, [C.POINTER(TvlqrOptions)]),
     "tsat_tvlqr_batch": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _ip,
                                    _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_void_p, _ip, C.POINTER(C.c_int64)]),
+    "tsat_tvlqr_ensemble": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp, _ip,
+                                      _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip, C.c_void_p, _dp, C.c_void_p,
+                                      _dp, _dp]),
+    "tsat_ensemble_last_error": (C.c_char_p, []),
 }
 
 LIB_NAME = "libtortoise_hip.so"

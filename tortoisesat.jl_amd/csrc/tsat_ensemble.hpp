@@ -1,0 +1,223 @@
+// tsat_ensemble.hpp — closed-loop tracking of a solved slew under an ENSEMBLE of plant-noise realisations
+// (tsat_tvlqr_ensemble, include/tortoise_hip.h): one Monte-Carlo trial of src/monte_carlo.jl:199-262 per lane.
+//
+// The tracking kernel of tsat_device.hpp (tvlqr_trajectory) rolls ONE realisation out with all 64 lanes computing the same
+// state. Here lane = realisation: wavefront (t, w) simulates realisations 64 w .. 64 w + 63 of slew t — one instruction
+// stream, 64 different plants. Everything a knot needs besides the lane's own state and noise is addressed by (t, k) only:
+// reference record (10), gain rows (18), three field rows (9). Those are read through constant-address-space pointers built
+// from the block index and the loop counter, i.e. by scalar LOADS into SGPRs (no LDS, no vector memory traffic in the loop;
+// the kernel's only vector stores are the debugging X_sim path and the statistic at the end).
+// The per-lane noise is drawn where it is consumed, one RK4 stage at a time (3 Philox blocks + 3 Box-Muller pairs), so that
+// only nine noise values are live instead of 36.
+//
+// Written over the lane abstraction of tsat_device.hpp (TSAT_DEV, TSAT_LANE, TSAT_CONSTMEM, ...) so that the CPU lane
+// emulator runs the same source (tests/emu/tsat_emu_ensemble.cpp). The plant, the generator and the table clock are the
+// device functions the tracking kernel uses: dyn_sim_h, plant_noise, brow_index, control_scale.
+#pragma once
+#include "tsat_device.hpp"
+
+namespace tsat {
+
+template <typename real>
+struct EnsArgs {
+  int T, N, n_tab, M, min_steps;   // realisation index M of every slew is the noise-free plant started at the plan's first state
+  real us, w_tol, ang_tol;
+  const real* P;      // [T][PSTRIDE]   parameter records (pack_tv_params)
+  const real* BT;     // [n_btab][n_tab][4]
+  const int* bidx;    // [T]
+  const int* nk;      // [T] per-slew knot counts or null (all N)
+  const real* XUR;    // [T][N][10]     optimised (X,U) records
+  const real* KD;     // [T][N-1][24]   gains, solver sign (-K_lqr), rows of 7
+  const real* X0;     // [T][M][7]      perturbed initial states
+  unsigned k0, k1;    // generator key
+  const long long* nid0;   // [T] first generator id of each slew or null (t * M)
+  real sg, sa, fa;    // sigma_gyro, sigma_att, field_amp
+  real* XS;           // [T][M][N][7] every simulated state, or null
+  tsat_tvlqr_stats* stats;      // [T][M]
+  tsat_tvlqr_stats* stats_nom;  // [T]
+};
+
+// waves per slew: M realisations + the nominal one over 64 lanes
+inline int ensemble_waves(int M) { return (M + 1 + WAVE - 1) / WAVE; }
+
+// the constants of a slew straight from its parameter record (wave-uniform: scalar loads), with the derived values formed as
+// stage_traj / load_traj form them (h inv(J), h / 2, the control scales)
+template <typename real>
+TSAT_DEV Traj<real> ensemble_traj(const TSAT_CONSTMEM real* p, real u_scale, int N, int n_tab) {
+  Traj<real> tr;
+  const real h = p[P_DT];
+  for (int i = 0; i < 7; ++i) { tr.xf[i] = p[P_XF + i]; tr.Qd[i] = 0; tr.Qfd[i] = 0; }
+  for (int i = 0; i < 3; ++i) { tr.Rd[i] = 0; tr.ulo[i] = 0; tr.uhi[i] = 0; }
+  for (int i = 0; i < 9; ++i) { tr.J[i] = p[P_J + i]; tr.hJi[i] = h * p[P_JI + i]; }
+  tr.h = h; tr.hh = (real)0.5 * h; tr.us = u_scale; tr.usj = tr.us * tr.hJi[0];
+  tr.tau0 = (double)p[P_TAU0] + (double)p[P_TAU0L]; tr.dtau = (double)p[P_DTAU] + (double)p[P_DTAUL];
+  tr.N = N; tr.n_tab = n_tab; tr.bt = nullptr;
+  return tr;
+}
+
+// the error angle of a sample, as the statistic of tvlqr_trajectory evaluates it
+template <typename real>
+TSAT_DEV real ensemble_angle(const Traj<real>& tr, const real x[7]) {
+  const real qf0 = tr.xf[3], qf1 = -tr.xf[4], qf2 = -tr.xf[5], qf3 = -tr.xf[6];
+  const real e0 = qf0 * x[3] - (qf1 * x[4] + qf2 * x[5] + qf3 * x[6]);
+  return 2 * acos_(e0 < 1 ? e0 : (real)1);
+}
+
+template <typename real, int DIAGJ>
+TSAT_DEV void ensemble_wave(const EnsArgs<real>& a, int traj, int wave) {
+  const int lane = TSAT_LANE();
+  const int NS = a.N, n_tab = a.n_tab, M = a.M;
+  const int N = a.nk ? a.nk[traj] : a.N;                       // own horizon; slabs keep the stride NS
+  const int R = M + 1;
+  // lanes past the last realisation compute a duplicate of it and store nothing (no divergent exit)
+  const int r_own = wave * WAVE + lane;
+  const bool live = r_own < R;
+  const int r = live ? r_own : R - 1;
+  const bool noisy = r < M;
+  const TSAT_CONSTMEM real* Pc = (const TSAT_CONSTMEM real*)(a.P + (size_t)traj * PSTRIDE);
+  const TSAT_CONSTMEM real* xu = (const TSAT_CONSTMEM real*)(a.XUR + (size_t)traj * NS * XUW);
+  const TSAT_CONSTMEM real* kdg = (const TSAT_CONSTMEM real*)(a.KD + (size_t)traj * (NS - 1) * KDW);
+  const TSAT_CONSTMEM real* bt = (const TSAT_CONSTMEM real*)(a.BT + (size_t)a.bidx[traj] * n_tab * 4);
+  const Traj<real> tr = ensemble_traj<real>(Pc, a.us, N, n_tab);
+  const long long gid = (a.nid0 ? a.nid0[traj] : (long long)traj * (long long)M) + (long long)r;
+  TSAT_GLOBAL real* xs = (a.XS && live && noisy) ? (TSAT_GLOBAL real*)(a.XS + ((size_t)traj * M + r) * NS * 7) : nullptr;
+  real x[7];
+  if (noisy) {
+    const TSAT_GLOBAL real* x0 = (const TSAT_GLOBAL real*)(a.X0 + ((size_t)traj * M + r) * 7);
+    for (int i = 0; i < 7; ++i) x[i] = x0[i];
+  } else {
+    for (int i = 0; i < 7; ++i) x[i] = xu[i];
+  }
+  const real cs = control_scale<real, DIAGJ>(tr);
+  int first = 0;                                               // the statistic, evaluated while the roll-out runs
+  TSAT_NO_UNROLL
+  for (int k = 0; k < N - 1; ++k) {
+    {  // sample j = k + 1 (1-based): src/monte_carlo.jl:242-262
+      const real wj = sqrt_(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+      if (first == 0 && k + 1 > a.min_steps && wj < a.w_tol) {
+        if (ensemble_angle<real>(tr, x) < a.ang_tol) first = k + 1;
+      }
+    }
+    if (xs)
+      for (int i = 0; i < 7; ++i) xs[(size_t)k * 7 + i] = x[i];
+    const TSAT_CONSTMEM real* xr = xu + (size_t)k * XUW;
+    const TSAT_CONSTMEM real* kd = kdg + (size_t)k * KDW;
+    real dX[6];
+    for (int i = 0; i < 3; ++i) dX[i] = x[i] - xr[i];
+    {  // vector part of q_ref^-1 (x) q_sim  (src/attitude_controller.jl:42)
+      const real s1 = xr[3], a1 = -xr[4], a2 = -xr[5], a3 = -xr[6];
+      dX[3] = s1 * x[4] + x[3] * a1 + (a2 * x[6] - a3 * x[5]);
+      dX[4] = s1 * x[5] + x[3] * a2 + (a3 * x[4] - a1 * x[6]);
+      dX[5] = s1 * x[6] + x[3] * a3 + (a1 * x[5] - a2 * x[4]);
+    }
+    real us[3];
+    for (int c = 0; c < 3; ++c) {
+      real v = xr[7 + c];
+      for (int j = 0; j < 6; ++j) v += kd[c * 7 + j] * dX[j];   // kd = -K_lqr
+      us[c] = v * cs;
+    }
+    // rows at tau, tau + dtau/2, tau + dtau: wave-uniform indices, said so (the clock is fp64 arithmetic on the vector unit)
+    const TSAT_CONSTMEM real* p0 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tr, k, 0.0)) * 4;
+    const TSAT_CONSTMEM real* p1 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tr, k, 0.5)) * 4;
+    const TSAT_CONSTMEM real* p2 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tr, k, 1.0)) * 4;
+    const real b0[3] = {p0[0], p0[1], p0[2]}, b1[3] = {p1[0], p1[1], p1[2]}, b2[3] = {p2[0], p2[1], p2[2]};
+    real k1[7], k2[7], k3[7], k4[7], t[7], nz[9];
+    for (int i = 0; i < 9; ++i) nz[i] = 0;
+    if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 0, a.sg, a.sa, a.fa, nz);
+    dyn_sim_h<real, DIAGJ>(tr, x, us, b0, noisy, nz, k1);
+    for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k1[i];
+    if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 1, a.sg, a.sa, a.fa, nz);
+    dyn_sim_h<real, DIAGJ>(tr, t, us, b1, noisy, nz, k2);
+    for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k2[i];
+    if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 2, a.sg, a.sa, a.fa, nz);
+    dyn_sim_h<real, DIAGJ>(tr, t, us, b1, noisy, nz, k3);
+    for (int i = 0; i < 7; ++i) t[i] = x[i] + k3[i];
+    if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 3, a.sg, a.sa, a.fa, nz);
+    dyn_sim_h<real, DIAGJ>(tr, t, us, b2, noisy, nz, k4);
+    for (int i = 0; i < 7; ++i) x[i] = x[i] + (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) * (real)(1.0 / 6.0);
+  }
+  // last sample j = N
+  const real wN = sqrt_(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  const real angN = ensemble_angle<real>(tr, x);
+  if (first == 0 && N > a.min_steps && wN < a.w_tol && angN < a.ang_tol) first = N;
+  if (xs)
+    for (int i = 0; i < 7; ++i) xs[(size_t)(N - 1) * 7 + i] = x[i];
+  if (live) {
+    tsat_tvlqr_stats st;
+    st.slew_index = first;
+    st.failed = first ? 0 : 1;
+    st.slew_time = (double)tr.h * (first ? (double)first : (double)N);
+    st.final_w_norm = (double)wN;
+    st.final_angle = (double)angN;
+    if (noisy) a.stats[(size_t)traj * M + r] = st;
+    else a.stats_nom[traj] = st;
+  }
+}
+
+// gains of one slew, exactly as tvlqr_trajectory computes them before its roll-out: terminal S = Qf_lqr, then chunks of
+// Jacobian lanes (tv_jacobian_chunk) + the element-oriented Riccati recursion (riccati_chunk<real, 6, TvRec>), written to KD
+// in the solver's sign. One wavefront per slew; uses the wave's LDS block of tsat_device.hpp (wide layout).
+#if !defined(TSAT_DENSE) && !defined(TSAT_F32)
+template <typename real, int DIAGJ>
+TSAT_DEV void ensemble_gains(const real* Pg, const real* BTg, const int* bidx, const int* nkg, const real* XUR, real* KDg,
+                             int NS, int n_tab, real u_scale, int lin_sq, int traj) {
+  real* lds = lds_base<real>();
+  const int lane = TSAT_LANE();
+  const int N = nkg ? nkg[traj] : NS;
+  TPtrs<real> p;
+  p.XU = (TSAT_GLOBAL real*)(XUR + (size_t)traj * NS * XUW);
+  p.KD = (TSAT_GLOBAL real*)(KDg + (size_t)traj * (NS - 1) * KDW);
+  p.LAM = nullptr; p.CAND = nullptr; p.XU0 = p.XU; p.cur = 0;
+  p.bt = (const TSAT_GLOBAL real*)(BTg + (size_t)bidx[traj] * n_tab * 4);
+  stage_traj<real>((const TSAT_GLOBAL real*)(Pg + (size_t)traj * PSTRIDE), u_scale);
+  TSAT_SYNC();
+  const real h = lds[L_TR + P_DT];
+  const real hl = lin_sq ? h * h : h;
+  const real frac = hl / h;
+  {
+    const int r1 = lane & 7, c1 = lane >> 3;
+    if (c1 < 6 && r1 <= 6) lds[L_ST + r1 * 9 + c1] = (r1 == c1) ? lds[L_TR + P_QFD + c1] : (real)0;
+    if (lane == 0) { lds[L_ZERO] = 0; lds[L_SINK] = 0; }
+  }
+  TSAT_SYNC();
+  constexpr int CHB = TV_CHB;
+  BwdOut<real> acc;
+  acc.dV1 = 0; acc.dV2 = 0; acc.pd_ok = 1;
+  for (int ch = (N - 1 + CHB - 1) / CHB - 1; ch >= 0 && acc.pd_ok; --ch) {
+    const int k0 = ch * CHB;
+    const int nk = (N - 1 - k0 < CHB) ? (N - 1 - k0) : CHB;
+    tv_jacobian_chunk<real, DIAGJ>(p, N, n_tab, k0, nk, hl, frac);
+    TSAT_SYNC();
+    acc = riccati_chunk<real, 6, TvRec>(p.KD, k0, nk, (real)0, acc.dV1, acc.dV2);
+    TSAT_SYNC();
+  }
+}
+#endif
+
+// `summary` (8 per slew) from `stats` (M per slew), summed in realisation order — the definitions of include/tortoise_hip.h
+inline void ensemble_summary(int64_t T, int M, const tsat_tvlqr_stats* stats, double* summary) {
+  for (int64_t t = 0; t < T; ++t) {
+    const tsat_tvlqr_stats* s = stats + (size_t)t * M;
+    double* o = summary + 8 * t;
+    int fails = 0;
+    double sum_ok = 0, mn = 0, mx = 0, sum_all = 0, ang = 0, w = 0;
+    bool any = false;
+    for (int m = 0; m < M; ++m) {
+      sum_all += s[m].slew_time;
+      if (m == 0 || s[m].final_angle > ang) ang = s[m].final_angle;
+      if (m == 0 || s[m].final_w_norm > w) w = s[m].final_w_norm;
+      if (s[m].failed) { ++fails; continue; }
+      sum_ok += s[m].slew_time;
+      if (!any || s[m].slew_time < mn) mn = s[m].slew_time;
+      if (!any || s[m].slew_time > mx) mx = s[m].slew_time;
+      any = true;
+    }
+    o[0] = (double)M; o[1] = (double)fails;
+    o[2] = any ? sum_ok / (double)(M - fails) : 0.0;
+    o[3] = mn; o[4] = mx;
+    o[5] = sum_all / (double)M;
+    o[6] = ang; o[7] = w;
+  }
+}
+
+}  // namespace tsat

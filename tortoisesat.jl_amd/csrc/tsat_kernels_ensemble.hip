@@ -1,0 +1,227 @@
+// tsat_kernels_ensemble.hip — tsat_tvlqr_ensemble (include/tortoise_hip.h): TVLQR gains once per slew, then M noisy plants per
+// slew with lane = realisation (tsat_ensemble.hpp). A translation unit of its own, built on the public ABI: `struct tsat_handle`
+// is private to tsat_kernels.hip, so the call keeps its own buffers and stream.
+//
+// Host side of one call (all of it synchronous):
+//   1. argument checks; a one-slew, two-knot call of tsat_tvlqr_batch validates the handle and the options block with the
+//      library's own checks and leaves the handle's GPU current on the calling thread;
+//   2. X, U and the field tables go up AS THEY ARE (no host-side repacking of 10 N T doubles) and are packed into knot records
+//      and padded table rows by two copy kernels on the device;
+//   3. the gains kernel: one wavefront per slew runs the gain half of the tracking kernel — the same device functions
+//      (tv_jacobian_chunk, riccati_chunk), so K is what tsat_tvlqr_batch returns, and it never leaves the device unless asked for;
+//   4. the ensemble kernel: grid (T, ceil((M + 1) / 64)); the extra realisation is the noise-free plant from the plan's own
+//      first state (stats_nominal);
+//   5. statistics (and K / X_sim when asked for) come down; `summary` is formed on the host in realisation order.
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+#include "tsat_host_pack.hpp"
+#include "tsat_ensemble.hpp"
+
+using namespace tsat;
+
+template <typename real, int DIAGJ>
+__global__ __launch_bounds__(64) void tsat_ensemble_kernel(EnsArgs<real> a) {
+  ensemble_wave<real, DIAGJ>(a, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+template <typename real, int DIAGJ>
+__global__ __launch_bounds__(64) void tsat_ensemble_gains_kernel(const real* P, const real* BT, const int* bidx, const int* nk,
+                                                                 const real* XUR, real* KD, int N, int n_tab, real u_scale,
+                                                                 int lin_sq) {
+  ensemble_gains<real, DIAGJ>(P, BT, bidx, nk, XUR, KD, N, n_tab, u_scale, lin_sq, (int)blockIdx.x);
+}
+
+// X (T,N,7) + U (T,N-1,3) -> knot records [T][N][10] (pack_xu_records, on the device)
+__global__ __launch_bounds__(256) void tsat_ensemble_pack_xu_kernel(int64_t n_rec, int N, const double* X, const double* U, double* XU) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_rec) return;
+  const int64_t t = e / N;
+  const int k = (int)(e - t * N);
+  double* r = XU + (size_t)e * XUW;
+  for (int i = 0; i < 7; ++i) r[i] = X[(size_t)e * 7 + i];
+  for (int c = 0; c < 3; ++c) r[7 + c] = (k < N - 1) ? U[((size_t)t * (N - 1) + k) * 3 + c] : 0.0;
+}
+// field rows [rows][3] -> [rows][4] (pack_btab, on the device)
+__global__ __launch_bounds__(256) void tsat_ensemble_pack_bt_kernel(int64_t rows, const double* B, double* BT) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= rows) return;
+  BT[4 * e + 0] = B[3 * e + 0]; BT[4 * e + 1] = B[3 * e + 1]; BT[4 * e + 2] = B[3 * e + 2]; BT[4 * e + 3] = 0.0;
+}
+// gains in the solver's sign [T][N-1][24] -> K_lqr 3 x 6 x (N-1) x T (unpack_tv, on the device)
+__global__ __launch_bounds__(256) void tsat_ensemble_export_k_kernel(int64_t n, const double* KD, double* K) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  for (int j = 0; j < 6; ++j)
+    for (int c = 0; c < 3; ++c) K[(size_t)e * 18 + j * 3 + c] = -KD[(size_t)e * KDW + c * 7 + j];
+}
+
+namespace {
+
+thread_local std::string g_err;
+
+int efail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+
+// the call's device buffers, stream and events: released on every way out
+struct EnsScope {
+  std::vector<void*> bufs;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[4] = {};
+  ~EnsScope() {
+    for (void* p : bufs) (void)hipFree(p);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  template <typename Tp>
+  bool alloc(Tp** p, size_t n) {
+    void* q = nullptr;
+    const size_t b = n * sizeof(Tp);
+    if (hipMalloc(&q, b ? b : 16) != hipSuccess) return false;
+    bufs.push_back(q);
+    *p = reinterpret_cast<Tp*>(q);
+    return true;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+const char* tsat_ensemble_last_error(void) { return g_err.c_str(); }
+
+int tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                        const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                        const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
+                        const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                        tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr,
+                        double* X_sim) {
+  g_err.clear();
+  if (!h || !o) return efail(-1, "null handle or options");
+  const std::string why = check_tv_options(*o);
+  if (!why.empty()) return efail(-1, why);
+  if (o->noise_mode != 1) return efail(-1, "noise_mode must be 1: the ensemble draws its noise in the kernel");
+  if (o->rate_as_written != 0) return efail(-1, "rate_as_written must be 0: the statistic is evaluated while the roll-out runs");
+  if (M < 1 || M > 65535) return efail(-1, "M must be in [1, 65535]");
+  if (T < 1 || T > 0x7fffffff || n_btab < 1) return efail(-1, "bad batch dimensions");
+  if (!X || !U || !xf || !Btab || !tau0 || !dtau || !dt || !Jmat || !Qd || !Qfd || !Rd || !x0_sim || !stats || !summary)
+    return efail(-1, "null array");
+  if (!btab_idx && n_btab != T) return efail(-1, "btab_idx is NULL but n_btab != T");
+  const int N = o->n_knots, n_tab = o->n_tab;
+  const size_t Tn = (size_t)T;
+  std::vector<int> bi(Tn);
+  for (int64_t t = 0; t < T; ++t) {
+    const int64_t v = btab_idx ? btab_idx[t] : t;
+    if (v < 0 || v >= n_btab) return efail(-1, "btab_idx out of range");
+    if (!(dt[t] > 0.0)) return efail(-1, "dt must be positive");
+    if (n_knots && (n_knots[t] < 2 || n_knots[t] > N)) return efail(-1, "n_knots[t] must be in [2, N]");
+    bi[(size_t)t] = (int)v;
+  }
+  // ---- 1. the handle: the library's own checks on slew 0 cut to two knots; its GPU becomes the thread's current device ----
+  {
+    tsat_tvlqr_options op = *o;
+    op.n_knots = 2; op.noise_mode = 0;
+    tsat_tvlqr_stats probe;
+    const int rc = tsat_tvlqr_batch(h, &op, 1, 1, X, U, xf, Btab + (size_t)bi[0] * n_tab * 3, nullptr, tau0, dtau, dt, Jmat, Qd, Qfd,
+                                    Rd, X, nullptr, nullptr, nullptr, nullptr, &probe, nullptr, nullptr);
+    if (rc) return efail(rc, std::string("tsat_tvlqr_batch: ") + tsat_last_error(h));
+  }
+  // ---- 2. upload ---------------------------------------------------------------------------------------------------
+  const int nw = ensemble_waves(M);
+  const size_t nX = Tn * N * 7, nU = Tn * (size_t)(N - 1) * 3, nB = (size_t)n_btab * n_tab, nXU = Tn * N * XUW,
+               nKD = Tn * (size_t)(N - 1) * KDW, nS = Tn * (size_t)M, nXS = X_sim ? nS * N * 7 : 0;
+  std::vector<double> P(Tn * PSTRIDE), x0n(Tn * 7);
+  for (size_t t = 0; t < Tn; ++t)
+    for (int i = 0; i < 7; ++i) x0n[7 * t + i] = X[t * N * 7 + i];
+  pack_tv_params<double>(T, x0n.data(), xf, tau0, dtau, dt, Jmat, Qd, Qfd, Rd, P.data());
+  const int cls = inertia_class(T, Jmat);
+  EnsScope s;
+  double *dP = nullptr, *dX = nullptr, *dU = nullptr, *dB = nullptr, *dBT = nullptr, *dXU = nullptr, *dKD = nullptr, *dX0 = nullptr,
+         *dXS = nullptr, *dK = nullptr;
+  int *dbi = nullptr, *dnk = nullptr;
+  long long* dnid = nullptr;
+  tsat_tvlqr_stats *dst = nullptr, *dsn = nullptr;
+  bool ok = s.alloc(&dP, P.size()) && s.alloc(&dX, nX) && s.alloc(&dU, nU) && s.alloc(&dB, nB * 3) && s.alloc(&dBT, nB * 4) &&
+            s.alloc(&dXU, nXU) && s.alloc(&dKD, nKD) && s.alloc(&dX0, nS * 7) && s.alloc(&dbi, Tn) && s.alloc(&dst, nS) &&
+            s.alloc(&dsn, Tn);
+  if (ok && n_knots) ok = s.alloc(&dnk, Tn);
+  if (ok && noise_id0) ok = s.alloc(&dnid, Tn);
+  if (ok && X_sim) ok = s.alloc(&dXS, nXS);
+  if (ok && K_lqr) ok = s.alloc(&dK, Tn * (size_t)(N - 1) * 18);
+  if (!ok) return efail(-10, "device allocation failed in tsat_tvlqr_ensemble");
+#define ENS_HIP(call)                                                                                   \
+  do {                                                                                                  \
+    hipError_t e_ = (call);                                                                             \
+    if (e_ != hipSuccess) return efail(-10, std::string(#call) + ": " + hipGetErrorString(e_));         \
+  } while (0)
+  ENS_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+  for (hipEvent_t& e : s.ev) ENS_HIP(hipEventCreate(&e));
+  ENS_HIP(hipMemcpy(dP, P.data(), P.size() * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dX, X, nX * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dU, U, nU * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dB, Btab, nB * 3 * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dX0, x0_sim, nS * 7 * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dbi, bi.data(), Tn * sizeof(int), hipMemcpyHostToDevice));
+  if (n_knots) ENS_HIP(hipMemcpy(dnk, n_knots, Tn * sizeof(int), hipMemcpyHostToDevice));
+  if (noise_id0) ENS_HIP(hipMemcpy(dnid, noise_id0, Tn * sizeof(long long), hipMemcpyHostToDevice));
+  // ---- 3. pack on the device, gains, 4. ensemble ---------------------------------------------------------------------
+  const int64_t n_rec = T * (int64_t)N;
+  hipLaunchKernelGGL(tsat_ensemble_pack_xu_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s.stream, n_rec, N, dX, dU, dXU);
+  hipLaunchKernelGGL(tsat_ensemble_pack_bt_kernel, dim3((unsigned)((nB + 255) / 256)), dim3(256), 0, s.stream, (int64_t)nB, dB, dBT);
+  ENS_HIP(hipGetLastError());
+  if (n_knots) {   // ragged: the slabs beyond a slew's own horizon stay zero
+    ENS_HIP(hipMemsetAsync(dKD, 0, nKD * 8, s.stream));
+    if (X_sim) ENS_HIP(hipMemsetAsync(dXS, 0, nXS * 8, s.stream));
+  }
+  ENS_HIP(hipEventRecord(s.ev[0], s.stream));
+  {
+    auto kern = cls == 2 ? tsat_ensemble_gains_kernel<double, 2>
+                         : (cls == 1 ? tsat_ensemble_gains_kernel<double, 1> : tsat_ensemble_gains_kernel<double, 0>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)T), dim3(64), 0, s.stream, dP, dBT, dbi, dnk, dXU, dKD, N, n_tab, o->u_scale,
+                       o->linearize_dt_sq);
+    ENS_HIP(hipGetLastError());
+  }
+  ENS_HIP(hipEventRecord(s.ev[1], s.stream));
+  {
+    EnsArgs<double> a;
+    a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.min_steps = o->min_steps;
+    a.us = o->u_scale; a.w_tol = o->w_tol; a.ang_tol = o->angle_tol;
+    a.P = dP; a.BT = dBT; a.bidx = dbi; a.nk = dnk; a.XUR = dXU; a.KD = dKD; a.X0 = dX0;
+    a.k0 = (unsigned)(o->noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o->noise_seed >> 32);
+    a.nid0 = dnid; a.sg = o->sigma_gyro; a.sa = o->sigma_att; a.fa = o->field_amp;
+    a.XS = dXS; a.stats = dst; a.stats_nom = dsn;
+    auto kern = cls == 2 ? tsat_ensemble_kernel<double, 2> : (cls == 1 ? tsat_ensemble_kernel<double, 1> : tsat_ensemble_kernel<double, 0>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)T, (unsigned)nw), dim3(64), 0, s.stream, a);
+    ENS_HIP(hipGetLastError());
+  }
+  ENS_HIP(hipEventRecord(s.ev[2], s.stream));
+  if (K_lqr) {
+    const int64_t n = T * (int64_t)(N - 1);
+    hipLaunchKernelGGL(tsat_ensemble_export_k_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, n, dKD, dK);
+    ENS_HIP(hipGetLastError());
+  }
+  ENS_HIP(hipStreamSynchronize(s.stream));
+  // ---- 5. download ---------------------------------------------------------------------------------------------------
+  ENS_HIP(hipMemcpy(stats, dst, nS * sizeof(tsat_tvlqr_stats), hipMemcpyDeviceToHost));
+  if (stats_nominal) ENS_HIP(hipMemcpy(stats_nominal, dsn, Tn * sizeof(tsat_tvlqr_stats), hipMemcpyDeviceToHost));
+  if (K_lqr) ENS_HIP(hipMemcpy(K_lqr, dK, Tn * (size_t)(N - 1) * 18 * 8, hipMemcpyDeviceToHost));
+  if (X_sim) ENS_HIP(hipMemcpy(X_sim, dXS, nXS * 8, hipMemcpyDeviceToHost));
+  ensemble_summary(T, M, stats, summary);
+  if (const char* v = std::getenv("TSAT_ENSEMBLE_TIMING")) {   // diagnostic (tools/ensemble_timing.py): HIP-event times of the two kernels
+    if (v[0] == '1') {
+      float g = 0, e = 0;
+      (void)hipEventElapsedTime(&g, s.ev[0], s.ev[1]);
+      (void)hipEventElapsedTime(&e, s.ev[1], s.ev[2]);
+      std::fprintf(stderr, "tsat_tvlqr_ensemble: gains_kernel_ms %.4f ensemble_kernel_ms %.4f\n", g, e);
+    }
+  }
+#undef ENS_HIP
+  return 0;
+}
+
+}  // extern "C"
