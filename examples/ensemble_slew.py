@@ -19,10 +19,8 @@ load_package()
 from tortoisesat_jl_amd import horizon, magnetic, slew_setup as ss, tracking, trajopt as to  # noqa: E402
 
 
-def main(M=256, sigma_scale=1.0, verbose=True):
-    say = print if verbose else (lambda *a, **k: None)
-    solver = to.AugmentedLagrangianSolver(None, None)
-    # the plan: examples/single_slew.py, line for line ----------------------------------------------------------
+def plan(solver, say=print):
+    """the plan: examples/single_slew.py, line for line. Returns (batch, res, N)."""
     kep = np.array([[0.0, 400.0 + 6371.0, 51.6, 0.0, 0.0, 90.0]])
     t0, tf, N_tab, cutoff, dt = 0.0, 5400.0, 5000, 20.0, 0.2
     B_coarse, _ = magnetic.magnetic_simulation(solver, kep, t0, tf, N_tab)
@@ -51,6 +49,13 @@ def main(M=256, sigma_scale=1.0, verbose=True):
     batch = to.BatchProblem([sat])
     res = to.solve_(batch, solver)
     say(f"plan: {N} knots of {dt} s, status {sat.stats['status']}, max violation {sat.stats['c_max']:.2e}")
+    return batch, res, N
+
+
+def main(M=256, sigma_scale=1.0, verbose=True):
+    say = print if verbose else (lambda *a, **k: None)
+    solver = to.AugmentedLagrangianSolver(None, None)
+    batch, res, N = plan(solver, say)
     # the ensemble ------------------------------------------------------------------------------------------------
     Ql, Qfl, Rl = tracking.tvlqr_weights(1)
     x0_lqr = tracking.ensemble_initial_states(batch.arrays.x0, M, np.random.default_rng(0))

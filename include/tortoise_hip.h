@@ -317,8 +317,37 @@ int  tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T,
                          const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
                          tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
                          double* K_lqr, double* X_sim);
-/* text of the last failure of tsat_tvlqr_ensemble on the calling thread ("" if none) */
+/* text of the last failure of tsat_tvlqr_ensemble / tsat_tvlqr_ensemble_dispersed on the calling thread ("" if none) */
 const char* tsat_ensemble_last_error(void);
+
+/* The same ensemble with a PLANT OF ITS OWN per realisation and the actuator's limit on the feedback command: what decides
+ * whether a magnetorquer-only slew arrives is plant / model mismatch, which the noise of tsat_tvlqr_ensemble does not contain.
+ * Realisation (t, m) is the closed loop of tsat_tvlqr_ensemble (same gains — computed once per slew from the MODEL inertia
+ * Jmat[t] —, same x0_sim, generator id, draw layout, noise injection, RK4 plant integrator and statistic) except that per knot
+ *   u_cmd = U_k - K_k dX_k                                    (units of u_scale A m^2, as before)
+ *   u_sat = min(max(u_cmd, sat_lo[t]), sat_hi[t])             component-wise; a knot counts as clipped when any component changed
+ *   dipole seen by the plant, all four RK4 stages of the knot = G[t,m] u_sat u_scale + m_res[t,m]   (A m^2)
+ * and the rigid body has inertia Jp[t,m] instead of Jmat[t].
+ *   plant      21 x M x T      per realisation: Jp (9, column-major 3x3, symmetric positive definite, kg m^2),
+ *                              G (9, column-major 3x3: applied dipole = G * limited command; identity = ideal),
+ *                              m_res (3, A m^2, body frame)
+ *   sat_lo, sat_hi  3 x T each, units of u_scale; both NULL = unlimited (an infinite entry leaves that side open)
+ *   n_clipped  M x T out, may be NULL    clipped knots of every realisation
+ *   everything else            exactly as tsat_tvlqr_ensemble
+ * stats_nominal is the noise-free MODEL plant (Jmat — taken as the symmetric tensor of its upper triangle —, G = I, m_res = 0)
+ * from X[:,1,t], with the limits applied.
+ * Rejected with -1 (text with the offending (t, m) in tsat_ensemble_last_error): plant NULL, a non-finite plant entry, Jp not
+ * symmetric (|Jp - Jp'| > 1e-12 max|Jp|) or not positive definite, exactly one of the two limit arrays NULL, sat_lo > sat_hi,
+ * and everything tsat_tvlqr_ensemble rejects. */
+#define TSAT_PLANT_W 21
+int  tsat_tvlqr_ensemble_dispersed(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                         const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* K_lqr, double* X_sim, int32_t* n_clipped);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Receding-horizon re-solve on the RESIDENT batch (BASELINE.json configs[4]). NOT in the reference —

@@ -333,6 +333,38 @@ function attitude_ensemble(s::HIPSolver, p::BatchProblem, x0_lqr::Array{Float64,
 end
 
 """
+attitude_ensemble_dispersed(s, p, x0_lqr, Q_lqr, Qf_lqr, R_lqr, plant; sat_lo, sat_hi, noise_id0, opts, want_K,
+want_trajectories) — `tsat_tvlqr_ensemble_dispersed`: `attitude_ensemble` with a plant of its own per realisation
+(plant 21 x M x T: Jp 9, G 9 — both column-major —, m_res 3) and the feedback command limited to [sat_lo, sat_hi] (3 x T each, units
+of u_scale; both empty = unlimited). The gains come once per slew from the model inertia `p.J`.
+Returns (stats M x T, summary 8 x T, nominal T, K or nothing, X_sim or nothing, n_clipped M x T).
+"""
+function attitude_ensemble_dispersed(s::HIPSolver, p::BatchProblem, x0_lqr::Array{Float64,3}, Q_lqr::Matrix{Float64},
+                                     Qf_lqr::Matrix{Float64}, R_lqr::Matrix{Float64}, plant::Array{Float64,3};
+                                     sat_lo::Matrix{Float64} = zeros(3, 0), sat_hi::Matrix{Float64} = zeros(3, 0),
+                                     noise_id0::Vector{Int64} = Int64[], opts::TvlqrOptions = TvlqrOptions(noise_mode = 1),
+                                     want_K::Bool = false, want_trajectories::Bool = false)
+    T = size(p.x0, 2); N = p.N; M = size(x0_lqr, 2)
+    size(plant) == (21, M, T) || error("plant must be 21 x M x T")
+    opts.n_knots = N; opts.n_tab = size(p.B_ECI, 2)
+    st = Matrix{TvlqrStats}(undef, M, T); nominal = Vector{TvlqrStats}(undef, T); summary = zeros(8, T)
+    n_clipped = zeros(Int32, M, T)
+    K = want_K ? zeros(3, 6, N - 1, T) : nothing
+    Xs = want_trajectories ? zeros(7, N, M, T) : nothing
+    rc = ccall((:tsat_tvlqr_ensemble_dispersed, LIB), Cint,
+        (Ptr{Cvoid}, Ref{TvlqrOptions}, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{TvlqrStats}, Ptr{Float64}, Ptr{TvlqrStats},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        s.handle, opts, T, size(p.B_ECI, 3), M, p.X, p.U, p.xf, p.B_ECI, p.btab_idx, p.tau0, p.dtau, p.dt, p.J,
+        Q_lqr, Qf_lqr, R_lqr, x0_lqr, isempty(noise_id0) ? C_NULL : noise_id0, isempty(p.n_knots) ? C_NULL : p.n_knots,
+        plant, isempty(sat_lo) ? C_NULL : sat_lo, isempty(sat_hi) ? C_NULL : sat_hi,
+        st, summary, nominal, K === nothing ? C_NULL : K, Xs === nothing ? C_NULL : Xs, n_clipped)
+    rc == 0 || error("tsat_tvlqr_ensemble_dispersed failed ($rc): " * unsafe_string(ccall((:tsat_ensemble_last_error, LIB), Cstring, ())))
+    return st, summary, nominal, K, Xs, n_clipped
+end
+
+"""
 receding_horizon!(s, p, n_steps; plant_integrator = 4) — `tsat_mpc_run` on the batch `p` (uploaded here): re-solve the
 horizon every control step with the budget of `s.opts`, apply U[:,1] to the noise-free plant, shift the plan.
 No reference equivalent (BASELINE.json configs[4]). Returns X_hist 7×(n_steps+1)×T, U_hist 3×n_steps×T.

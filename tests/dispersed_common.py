@@ -1,0 +1,205 @@
+"""Shared pieces of tests/test_dispersed.py (CPU tier) and tests/test_gpu_dispersed.py (GPU tier).
+
+THE REFERENCE of the dispersed ensemble (tsat_tvlqr_ensemble_dispersed) is a closed loop built here, knot by knot, from the
+unchanged oracle's primitives only: ``ol.tvlqr_batch`` for the gains K (model inertia), then per knot ``ol.qmult`` on the
+conjugate reference attitude for dX, the three rules of the entry point (u_cmd = U - K dX; u_sat = clip(u_cmd); the plant of all
+four RK4 stages sees G u_sat + m_res / u_scale and has inertia Jp), ``ol.plant_noise`` for the draws, the noise injection of
+src/simulator.jl:5-23, ``ol.dyn7(..., Jp)`` per stage, table rows floor((k + c) dtau + tau0) clamped. With the model's plant and
+no limits it has to reproduce ``ol.tvlqr_batch`` (test_dispersed.py::test_reference_is_pinned_to_the_oracle).
+
+Also: the bracket on the clipped-knot counter, the sampled (t, m) pairs with their replacement cap, the cases of
+tests/ensemble_common.py, and the ctypes binding of the emulated kernel (tests/emu/tsat_emu_dispersed.cpp)."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+
+import ensemble_common as ec
+from conftest import ROOT
+
+MARGIN = 1e-7            # as the ensemble tests: index equality only where the reference is not on a threshold
+CLIP_BAND = 1e-7         # relative width of the band around a limit inside which the clip decision is a matter of the last bit
+N_DRAWN, N_KEPT = 34, 32  # sampled realisations: at most 2 of 34 may be replaced (the cap of test_gpu_ensemble_at_size)
+LEVELS = dict(inertia_rel=0.01, axes_deg=0.2, gain_rel=0.01, misalign_deg=0.5, residual_dipole=2e-4)
+
+_fma = getattr(math, "fma", None)
+
+
+def _row(batch, t, k, c):
+    v = _fma(k + c, float(batch.dtau[t]), float(batch.tau0[t])) if _fma else (k + c) * float(batch.dtau[t]) + float(batch.tau0[t])
+    r = math.floor(v)
+    i = 0 if not r >= 0 else min(int(r), batch.n_tab - 1)
+    return batch.Btab[batch.btab_idx[t], i]
+
+
+def _noisy(ol, x, b, nz):
+    """the state and the field row a stage evaluates the dynamics at (src/simulator.jl:5-23)"""
+    if nz is None:
+        return x, b
+    q = x[3:7] / math.sqrt(float(x[3:7] @ x[3:7]))
+    th = math.sqrt(float(nz[3:6] @ nz[3:6]))
+    dq = np.r_[math.cos(th / 2), nz[3:6] * (math.sin(th / 2) / th)]
+    return np.r_[x[:3] + nz[:3], ol.qmult(q, dq)], b + nz[6:9]
+
+
+def reference_loop(ol, batch, t, Xr, Ur, K, x0, opts, gid, plant=None, lo=None, hi=None, noisy=True):
+    """one closed loop of slew t. Xr (N,7), Ur (N-1,3) the plan, K (N-1,6,3) the oracle's gains of it, plant (21,) or None for
+    the model's, lo / hi (3,) or None, gid the generator id. Returns X_sim (N,7) zero-filled beyond the slew's horizon,
+    (n_sure, n_maybe)."""
+    NS = batch.N
+    N = NS if batch.n_knots is None else int(batch.n_knots[t])
+    us, h = float(opts.u_scale), float(batch.dt[t])
+    if plant is None:
+        Jp, G, mres = np.asarray(batch.Jmat[t]).reshape(3, 3).T, np.eye(3), np.zeros(3)
+    else:
+        Jp, G, mres = plant[0:9].reshape(3, 3).T, plant[9:18].reshape(3, 3).T, plant[18:21]
+    Xs = np.zeros((NS, 7))
+    x = np.array(x0, dtype=np.float64)
+    n_sure = n_maybe = 0
+    for k in range(N - 1):
+        Xs[k] = x
+        xr = Xr[k]
+        qe = ol.qmult(np.r_[xr[3], -xr[4:7]], x[3:7])
+        dX = np.r_[x[:3] - xr[:3], qe[1:4]]
+        u = Ur[k] - K[k].T @ dX
+        if lo is not None:
+            bl, bh = CLIP_BAND * np.abs(lo), CLIP_BAND * np.abs(hi)
+            n_sure += bool(np.any((lo - u > bl) | (u - hi > bh)))          # beyond a limit by more than the band
+            n_maybe += bool(np.any((lo - u > -bl) | (u - hi > -bh)))       # within the band of a limit, or beyond
+            u = np.minimum(np.maximum(u, lo), hi)
+        ua = G @ u + mres / us
+        nz = [ol.plant_noise(int(opts.noise_seed), int(gid), k, s, opts.sigma_gyro, opts.sigma_att, opts.field_amp) if noisy else None
+              for s in range(4)]
+        b0, b1, b2 = _row(batch, t, k, 0.0), _row(batch, t, k, 0.5), _row(batch, t, k, 1.0)
+
+        def f(xx, bb, n):
+            xn, bn = _noisy(ol, xx, bb, n)
+            return h * ol.dyn7(xn, ua, bn, Jp, us)
+
+        k1 = f(x, b0, nz[0])
+        k2 = f(x + k1 / 2, b1, nz[1])
+        k3 = f(x + k2 / 2, b1, nz[2])
+        k4 = f(x + k3, b2, nz[3])
+        x = x + (k1 + 2 * k2 + 2 * k3 + k4) / 6
+    Xs[N - 1] = x
+    return Xs, (n_sure, n_maybe)
+
+
+def stats_of(abi, X_sim, xf, n_knots, dt, min_steps=10, w_tol=0.05, angle_tol=0.08727):
+    """the slew-time statistic (src/monte_carlo.jl:242-262) of trajectories X_sim (n, N, 7)"""
+    n = X_sim.shape[0]
+    st = np.zeros(n, dtype=abi.TVLQR_STATS_DTYPE)
+    for i in range(n):
+        N = int(n_knots[i])
+        X = X_sim[i, :N]
+        w = np.linalg.norm(X[:, :3], axis=1)
+        e0 = X[:, 3:7] @ xf[i, 3:7]
+        ang = 2.0 * np.arccos(np.minimum(e0, 1.0))
+        j = np.arange(1, N + 1)
+        hit = np.flatnonzero((j > min_steps) & (w < w_tol) & (ang < angle_tol))
+        first = int(j[hit[0]]) if hit.size else 0
+        st[i] = (first, 0 if first else 1, dt[i] * (first if first else N), w[-1], ang[-1])
+    return st
+
+
+def reference_pairs(ol, abi, batch, X, U, K, x0_sim, opts, pairs, plant=None, sat=None, noise_id0=None):
+    """the reference on the (t, m) pairs (n, 2); m = -1 is the noise-free MODEL plant from X[t, 0] (stats_nominal).
+    Returns dict(X_sim (n, N, 7), stats (n,), n_sure (n,), n_maybe (n,), xf (n, 7), n_knots (n,))."""
+    T, M = x0_sim.shape[:2]
+    id0 = np.arange(T, dtype=np.int64) * M if noise_id0 is None else np.asarray(noise_id0, dtype=np.int64)
+    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
+    ol.load()
+
+    def one(p):
+        t, m = int(p[0]), int(p[1])
+        if m < 0:
+            return reference_loop(ol, batch, t, X[t], U[t], K[t], X[t, 0], opts, 0, None, None if lo is None else lo[t],
+                                  None if hi is None else hi[t], noisy=False)
+        return reference_loop(ol, batch, t, X[t], U[t], K[t], x0_sim[t, m], opts, id0[t] + m, None if plant is None else plant[t, m],
+                              None if lo is None else lo[t], None if hi is None else hi[t])
+
+    res = [one(p) for p in pairs]
+    pairs = np.asarray(pairs)
+    Xs = np.stack([r[0] for r in res])
+    nk = ec.horizons(batch)[pairs[:, 0]]
+    xf = batch.xf[pairs[:, 0]]
+    st = stats_of(abi, Xs, xf, nk, batch.dt[pairs[:, 0]], opts.min_steps, opts.w_tol, opts.angle_tol)
+    return dict(X_sim=Xs, stats=st, n_sure=np.array([r[1][0] for r in res]), n_maybe=np.array([r[1][1] for r in res]), xf=xf, n_knots=nk)
+
+
+def all_pairs(T, M):
+    return np.stack(np.meshgrid(np.arange(T), np.arange(M), indexing="ij"), axis=-1).reshape(-1, 2)
+
+
+def sampled_pairs(T, M, seed=32):
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.integers(0, T, N_DRAWN), rng.integers(0, M, N_DRAWN)], axis=1)
+
+
+def kept(ref):
+    """indices of the first N_KEPT sampled realisations whose reference run meets the margin; asserts the replacement cap"""
+    ok = np.array([ec.margin(ref["X_sim"][i:i + 1], ref["xf"][i:i + 1], ref["n_knots"][i:i + 1]) > MARGIN for i in range(len(ref["stats"]))])
+    keep = np.flatnonzero(ok)[:N_KEPT]
+    print(f"sampled pairs that fail the margin: {int(np.count_nonzero(~ok))} of {len(ok)}; arrivals among the kept: "
+          f"{int(np.count_nonzero(ref['stats']['failed'][keep] == 0))}")
+    assert keep.size == N_KEPT, "more than 2 of 34 sampled realisations sit on a threshold"
+    return keep
+
+
+def compare(ref, got, pairs, idx=None, clipped=True):
+    """the bars: |dX_sim| < 1e-9, same_stats, n_sure <= n_clipped <= n_maybe — on the realisations `idx` of `pairs`"""
+    idx = np.arange(len(pairs)) if idx is None else idx
+    t, m = pairs[idx, 0], pairs[idx, 1]
+    if got.get("X_sim") is not None:
+        dX = float(np.max(np.abs(ref["X_sim"][idx] - got["X_sim"][t, m])))
+        print(f"max|dX_sim| against the reference {dX:.2e}")
+        assert dX < 1e-9
+    ec.same_stats(ref["stats"][idx], got["stats"][t, m])
+    assert np.array_equal(ref["stats"]["slew_time"][idx], got["stats"]["slew_time"][t, m])
+    if clipped:
+        n = got["n_clipped"][t, m]
+        print(f"clipped knots: sure {ref['n_sure'][idx].min()} .. {ref['n_sure'][idx].max()}, got {n.min()} .. {n.max()}, "
+              f"undecided knots up to {int((ref['n_maybe'][idx] - ref['n_sure'][idx]).max())}")
+        assert np.all(ref["n_sure"][idx] <= n) and np.all(n <= ref["n_maybe"][idx])
+
+
+def all_five_plants(pkg, batch, M):
+    """the plants of the parity tests: all five dispersions at LEVELS, default_rng(7)"""
+    return pkg.tracking.disperse_plant(batch.Jmat, M, np.random.default_rng(7), **LEVELS)
+
+
+class EmuDispersed:
+    """ctypes binding of tests/emu/libtsat_emu_dispersed.so, built here with `make -f dispersed.mk`"""
+
+    def __init__(self, abi):
+        d = os.path.join(ROOT, "tests", "emu")
+        subprocess.check_call(["make", "-f", "dispersed.mk", "-C", d, "libtsat_emu_dispersed.so"], stdout=subprocess.DEVNULL)
+        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_dispersed.so"))
+        self.abi = abi
+
+    def run(self, batch, X, U, Qd, Qfd, Rd, x0_sim, K, opts, plant, sat=None, noise_id0=None, want_trajectories=True):
+        T, N, M = batch.T, batch.N, x0_sim.shape[1]
+        o = self.abi.TvlqrOptions.from_buffer_copy(opts)
+        o.n_knots, o.n_tab = N, batch.n_tab
+        c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        X, U, Qd, Qfd, Rd, x0_sim, K, plant = c(X), c(U), c(Qd), c(Qfd), c(Rd), c(x0_sim), c(K), c(plant)
+        assert plant.shape == (T, M, 21)
+        lo, hi = (None, None) if sat is None else (c(np.broadcast_to(sat[0], (T, 3))), c(np.broadcast_to(sat[1], (T, 3))))
+        st = np.zeros((T, M), dtype=self.abi.TVLQR_STATS_DTYPE)
+        nom = np.zeros(T, dtype=self.abi.TVLQR_STATS_DTYPE)
+        summary = np.zeros((T, 8))
+        ncl = np.full((T, M), -1, dtype=np.int32)
+        Xs = np.full((T, M, N, 7), np.nan) if want_trajectories else None
+        d = self.abi.as_dp
+        id0 = None if noise_id0 is None else np.ascontiguousarray(noise_id0, dtype=np.int64)
+        nk = None if batch.n_knots is None else np.ascontiguousarray(batch.n_knots, dtype=np.int32)
+        rc = self.lib.emu_tvlqr_ensemble_dispersed(
+            C.byref(o), C.c_int64(T), C.c_int64(batch.Btab.shape[0]), C.c_int32(M), d(X), d(U), d(batch.xf), d(batch.Btab),
+            self.abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat), d(Qd), d(Qfd), d(Rd), d(x0_sim),
+            None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), self.abi.as_ip(nk), d(plant), d(lo), d(hi), d(K),
+            st.ctypes.data_as(C.c_void_p), d(summary), nom.ctypes.data_as(C.c_void_p), d(Xs), self.abi.as_ip(ncl))
+        if rc != 0:
+            raise RuntimeError(f"emu_tvlqr_ensemble_dispersed rc={rc}")
+        return dict(stats=st, summary=summary, nominal=nom, X_sim=Xs, n_clipped=ncl)

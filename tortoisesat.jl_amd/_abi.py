@@ -123,6 +123,9 @@ PROTOTYPES = {
                                       _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip, C.c_void_p, _dp, C.c_void_p,
                                       _dp, _dp]),
     "tsat_ensemble_last_error": (C.c_char_p, []),
+    "tsat_tvlqr_ensemble_dispersed": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp,
+                                                _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp,
+                                                C.c_void_p, _dp, C.c_void_p, _dp, _dp, _ip]),
 }
 
 LIB_NAME = "libtortoise_hip.so"

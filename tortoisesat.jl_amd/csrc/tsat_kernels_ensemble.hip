@@ -12,19 +12,35 @@
 //   4. the ensemble kernel: grid (T, ceil((M + 1) / 64)); the extra realisation is the noise-free plant from the plan's own
 //      first state (stats_nominal);
 //   5. statistics (and K / X_sim when asked for) come down; `summary` is formed on the host in realisation order.
+//
+// tsat_tvlqr_ensemble_dispersed is the same call with a plant per realisation and limits on the command (tsat_dispersed.hpp):
+// the host validates the plants, a pack kernel forms inv(Jp) and the per-lane records between steps 2 and 3, and step 4
+// launches the dispersed kernel instead. Steps 1-3 and 5 are one piece of code for both entry points (run_ensemble).
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 #include "tsat_host_pack.hpp"
 #include "tsat_ensemble.hpp"
+#include "tsat_dispersed.hpp"
 
 using namespace tsat;
 
 template <typename real, int DIAGJ>
 __global__ __launch_bounds__(64) void tsat_ensemble_kernel(EnsArgs<real> a) {
   ensemble_wave<real, DIAGJ>(a, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+template <typename real>
+__global__ __launch_bounds__(64) void tsat_dispersed_kernel(DispArgs<real> d) {
+  dispersed_wave<real>(d, (int)blockIdx.x, (int)blockIdx.y);
+}
+// plants 21 x M x T -> packed per-lane records [T][PLW][Mp], slot M = the model's plant; one thread per realisation
+__global__ __launch_bounds__(256) void tsat_dispersed_pack_kernel(const double* plant, const double* P, double us, double* PL, int64_t T,
+                                                                  int M, int Mp) {
+  dispersed_pack<double>(plant, P, us, PL, T, M, Mp, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 template <typename real, int DIAGJ>
@@ -89,18 +105,46 @@ struct EnsScope {
   }
 };
 
-}  // namespace
+// what tsat_tvlqr_ensemble_dispersed adds to the call
+struct Dispersion {
+  const double *plant, *sat_lo, *sat_hi;
+  int32_t* n_clipped;
+};
 
-extern "C" {
+std::string at_tm(int64_t t, int m) { return " at (t, m) = (" + std::to_string(t) + ", " + std::to_string(m) + ")"; }
 
-const char* tsat_ensemble_last_error(void) { return g_err.c_str(); }
+// the host only validates the plants: "" or the reason, with the offending (t, m)
+std::string check_dispersion(const Dispersion& d, int64_t T, int M) {
+  if (!d.plant) return "null plant array";
+  if ((d.sat_lo == nullptr) != (d.sat_hi == nullptr)) return "exactly one of sat_lo / sat_hi is NULL: give both limits or neither";
+  for (int64_t t = 0; t < T; ++t) {
+    if (d.sat_lo)
+      for (int c = 0; c < 3; ++c)
+        if (!(d.sat_lo[3 * t + c] <= d.sat_hi[3 * t + c])) return "sat_lo > sat_hi (or not a number) at t = " + std::to_string(t);
+    for (int m = 0; m < M; ++m) {
+      const double* p = d.plant + ((size_t)t * M + m) * TSAT_PLANT_W;
+      double big = 0;
+      for (int i = 0; i < TSAT_PLANT_W; ++i)
+        if (!std::isfinite(p[i])) return "non-finite plant entry" + at_tm(t, m);
+      for (int i = 0; i < 9; ++i) big = std::fmax(big, std::fabs(p[i]));
+      for (int r = 0; r < 3; ++r)
+        for (int c = r + 1; c < 3; ++c)
+          if (std::fabs(p[3 * c + r] - p[3 * r + c]) > 1e-12 * big) return "Jp is not symmetric" + at_tm(t, m);
+      const double a = p[0], b = p[3], c = p[6], dd = p[4], e = p[7], f = p[8];
+      const double m2 = a * dd - b * b, m3 = a * (dd * f - e * e) + (b * (c * e - b * f) + c * (b * e - c * dd));
+      if (!(a > 0 && m2 > 0 && m3 > 0)) return "Jp is not positive definite" + at_tm(t, m);
+    }
+  }
+  return "";
+}
 
-int tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
-                        const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
-                        const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
-                        const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
-                        tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr,
-                        double* X_sim) {
+// both entry points: `disp` == nullptr is tsat_tvlqr_ensemble
+int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                 const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                 const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
+                 const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                 tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr,
+                 double* X_sim, const Dispersion* disp) {
   g_err.clear();
   if (!h || !o) return efail(-1, "null handle or options");
   const std::string why = check_tv_options(*o);
@@ -121,6 +165,10 @@ int tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, 
     if (!(dt[t] > 0.0)) return efail(-1, "dt must be positive");
     if (n_knots && (n_knots[t] < 2 || n_knots[t] > N)) return efail(-1, "n_knots[t] must be in [2, N]");
     bi[(size_t)t] = (int)v;
+  }
+  if (disp) {
+    const std::string bad = check_dispersion(*disp, T, M);
+    if (!bad.empty()) return efail(-1, bad);
   }
   // ---- 1. the handle: the library's own checks on slew 0 cut to two knots; its GPU becomes the thread's current device ----
   {
@@ -153,7 +201,13 @@ int tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, 
   if (ok && noise_id0) ok = s.alloc(&dnid, Tn);
   if (ok && X_sim) ok = s.alloc(&dXS, nXS);
   if (ok && K_lqr) ok = s.alloc(&dK, Tn * (size_t)(N - 1) * 18);
-  if (!ok) return efail(-10, "device allocation failed in tsat_tvlqr_ensemble");
+  // the dispersed call: raw plants, packed per-lane records, limits, clipped-knot counters
+  const int Mp = nw * WAVE;
+  double *dPlant = nullptr, *dPL = nullptr, *dSat = nullptr;
+  int* dClip = nullptr;
+  if (ok && disp) ok = s.alloc(&dPlant, nS * TSAT_PLANT_W) && s.alloc(&dPL, Tn * PLW * (size_t)Mp) && s.alloc(&dSat, Tn * SATW);
+  if (ok && disp && disp->n_clipped) ok = s.alloc(&dClip, nS);
+  if (!ok) return efail(-10, std::string("device allocation failed in ") + name);
 #define ENS_HIP(call)                                                                                   \
   do {                                                                                                  \
     hipError_t e_ = (call);                                                                             \
@@ -178,6 +232,21 @@ int tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, 
     ENS_HIP(hipMemsetAsync(dKD, 0, nKD * 8, s.stream));
     if (X_sim) ENS_HIP(hipMemsetAsync(dXS, 0, nXS * 8, s.stream));
   }
+  if (disp) {
+    std::vector<double> sat(Tn * SATW);
+    for (size_t t = 0; t < Tn; ++t)
+      for (int c = 0; c < 3; ++c) {
+        sat[SATW * t + c] = disp->sat_lo ? disp->sat_lo[3 * t + c] : -HUGE_VAL;
+        sat[SATW * t + 3 + c] = disp->sat_hi ? disp->sat_hi[3 * t + c] : HUGE_VAL;
+      }
+    ENS_HIP(hipMemcpy(dPlant, disp->plant, nS * TSAT_PLANT_W * 8, hipMemcpyHostToDevice));
+    ENS_HIP(hipMemcpy(dSat, sat.data(), sat.size() * 8, hipMemcpyHostToDevice));
+    ENS_HIP(hipEventRecord(s.ev[3], s.stream));
+    const int64_t n = T * (int64_t)(M + 1);
+    hipLaunchKernelGGL(tsat_dispersed_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, dPlant, dP, o->u_scale, dPL,
+                       T, M, Mp);
+    ENS_HIP(hipGetLastError());
+  }
   ENS_HIP(hipEventRecord(s.ev[0], s.stream));
   {
     auto kern = cls == 2 ? tsat_ensemble_gains_kernel<double, 2>
@@ -195,8 +264,14 @@ int tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, 
     a.k0 = (unsigned)(o->noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o->noise_seed >> 32);
     a.nid0 = dnid; a.sg = o->sigma_gyro; a.sa = o->sigma_att; a.fa = o->field_amp;
     a.XS = dXS; a.stats = dst; a.stats_nom = dsn;
-    auto kern = cls == 2 ? tsat_ensemble_kernel<double, 2> : (cls == 1 ? tsat_ensemble_kernel<double, 1> : tsat_ensemble_kernel<double, 0>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)T, (unsigned)nw), dim3(64), 0, s.stream, a);
+    if (disp) {
+      DispArgs<double> d;
+      d.e = a; d.PL = dPL; d.Mp = Mp; d.SAT = dSat; d.nclip = dClip;
+      hipLaunchKernelGGL(tsat_dispersed_kernel<double>, dim3((unsigned)T, (unsigned)nw), dim3(64), 0, s.stream, d);
+    } else {
+      auto kern = cls == 2 ? tsat_ensemble_kernel<double, 2> : (cls == 1 ? tsat_ensemble_kernel<double, 1> : tsat_ensemble_kernel<double, 0>);
+      hipLaunchKernelGGL(kern, dim3((unsigned)T, (unsigned)nw), dim3(64), 0, s.stream, a);
+    }
     ENS_HIP(hipGetLastError());
   }
   ENS_HIP(hipEventRecord(s.ev[2], s.stream));
@@ -211,17 +286,52 @@ int tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, 
   if (stats_nominal) ENS_HIP(hipMemcpy(stats_nominal, dsn, Tn * sizeof(tsat_tvlqr_stats), hipMemcpyDeviceToHost));
   if (K_lqr) ENS_HIP(hipMemcpy(K_lqr, dK, Tn * (size_t)(N - 1) * 18 * 8, hipMemcpyDeviceToHost));
   if (X_sim) ENS_HIP(hipMemcpy(X_sim, dXS, nXS * 8, hipMemcpyDeviceToHost));
+  if (dClip) ENS_HIP(hipMemcpy(disp->n_clipped, dClip, nS * sizeof(int32_t), hipMemcpyDeviceToHost));
   ensemble_summary(T, M, stats, summary);
   if (const char* v = std::getenv("TSAT_ENSEMBLE_TIMING")) {   // diagnostic (tools/ensemble_timing.py): HIP-event times of the two kernels
     if (v[0] == '1') {
       float g = 0, e = 0;
       (void)hipEventElapsedTime(&g, s.ev[0], s.ev[1]);
       (void)hipEventElapsedTime(&e, s.ev[1], s.ev[2]);
-      std::fprintf(stderr, "tsat_tvlqr_ensemble: gains_kernel_ms %.4f ensemble_kernel_ms %.4f\n", g, e);
+      if (disp) {
+        float p = 0;
+        (void)hipEventElapsedTime(&p, s.ev[3], s.ev[0]);
+        std::fprintf(stderr, "%s: pack_kernel_ms %.4f gains_kernel_ms %.4f ensemble_kernel_ms %.4f\n", name, p, g, e);
+      } else {
+        std::fprintf(stderr, "tsat_tvlqr_ensemble: gains_kernel_ms %.4f ensemble_kernel_ms %.4f\n", g, e);
+      }
     }
   }
 #undef ENS_HIP
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* tsat_ensemble_last_error(void) { return g_err.c_str(); }
+
+int tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                        const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                        const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
+                        const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                        tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr,
+                        double* X_sim) {
+  return run_ensemble("tsat_tvlqr_ensemble", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, Qd, Qfd, Rd, x0_sim,
+                      noise_id0, n_knots, stats, summary, stats_nominal, K_lqr, X_sim, nullptr);
+}
+
+int tsat_tvlqr_ensemble_dispersed(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                                  const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                                  const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
+                                  const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                                  const double* plant, const double* sat_lo, const double* sat_hi, tsat_tvlqr_stats* stats,
+                                  double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr, double* X_sim,
+                                  int32_t* n_clipped) {
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  return run_ensemble("tsat_tvlqr_ensemble_dispersed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, Qd, Qfd, Rd,
+                      x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, K_lqr, X_sim, &d);
 }
 
 }  // extern "C"

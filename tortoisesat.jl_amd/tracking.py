@@ -207,3 +207,108 @@ def attitude_ensemble(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise
     if rc != 0:
         raise RuntimeError(f"tsat_tvlqr_ensemble failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
     return dict(stats=st, summary=summary, nominal=nom, K=K, X_sim=Xs)
+
+
+PLANT_W = 21
+
+
+def _rotation(v):
+    """rotation matrix of the rotation vector v (rad), Rodrigues' formula; exactly I for v = 0"""
+    th = float(np.linalg.norm(v))
+    if th == 0.0:
+        return np.eye(3)
+    k = np.asarray(v, dtype=np.float64) / th
+    Kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + np.sin(th) * Kx + (1.0 - np.cos(th)) * (Kx @ Kx)
+
+
+def disperse_plant(Jmat, M, rng, inertia_rel=0.0, axes_deg=0.0, gain_rel=0.0, misalign_deg=0.0, residual_dipole=0.0):
+    """Plants of M realisations per slew for ``attitude_ensemble_dispersed``, (T, M, 21) = [Jp (9), G (9), m_res (3)], around
+    the model inertias Jmat ((T, 9) column-major as ``SlewBatch.Jmat``, or (T, 3, 3)):
+      Jp    principal moments scaled by (1 + inertia_rel z), principal axes turned by a rotation vector of sigma axes_deg (per axis);
+      G     R(rotation vector of sigma misalign_deg) diag(1 + gain_rel z): per-axis gain error behind a misaligned mounting;
+      m_res residual dipole ~ N(0, residual_dipole^2) per axis, A m^2.
+    z is standard normal clipped to +-3, so Jp stays positive definite for inertia_rel < 1/3 (larger is rejected); Jp is
+    symmetrised exactly. All-zero levels return exactly (Jmat, I, 0). Every realisation consumes the same 15 normals per slew,
+    realisation after realisation: the first M' realisations of a larger ensemble are the ensemble of size M'."""
+    Jmat = np.asarray(Jmat, dtype=np.float64)
+    if Jmat.ndim == 2 and Jmat.shape[1] == 9:
+        Jmat = Jmat.reshape(-1, 3, 3).transpose(0, 2, 1)
+    if Jmat.ndim != 3 or Jmat.shape[1:] != (3, 3):
+        raise ValueError("Jmat must be (T, 9) or (T, 3, 3)")
+    if not (0.0 <= inertia_rel < 1.0 / 3.0):
+        raise ValueError("inertia_rel must be in [0, 1/3): with z clipped to +-3 a larger level can give a non-positive moment")
+    if not (0.0 <= gain_rel < 1.0 / 3.0):
+        raise ValueError("gain_rel must be in [0, 1/3)")
+    if min(axes_deg, misalign_deg, residual_dipole) < 0.0:
+        raise ValueError("dispersion levels must not be negative")
+    T = Jmat.shape[0]
+    out = np.zeros((T, int(M), PLANT_W))
+    lam, V = (None, None) if inertia_rel == 0.0 and axes_deg == 0.0 else np.linalg.eigh(0.5 * (Jmat + Jmat.transpose(0, 2, 1)))
+    for m in range(int(M)):
+        z = rng.standard_normal((T, 15))
+        zc = np.clip(z, -3.0, 3.0)
+        for t in range(T):
+            if lam is None:
+                Jp = Jmat[t]
+            else:
+                A = _rotation(np.deg2rad(axes_deg) * z[t, 3:6]) @ V[t]
+                Jp = (A * (lam[t] * (1.0 + inertia_rel * zc[t, 0:3]))) @ A.T
+                Jp = 0.5 * (Jp + Jp.T)
+            G = _rotation(np.deg2rad(misalign_deg) * z[t, 9:12]) * (1.0 + gain_rel * zc[t, 6:9])[None, :]
+            out[t, m, 0:9] = Jp.T.reshape(9)              # column-major
+            out[t, m, 9:18] = G.T.reshape(9)
+            out[t, m, 18:21] = residual_dipole * z[t, 12:15]
+    return out
+
+
+def attitude_ensemble_dispersed(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant, sat=None, noise_id0=None,
+                                sigma_scale=1.0, want_K=False, want_trajectories=False, linearize_dt_sq=True, u_scale=1e-2,
+                                min_steps=10, w_tol=0.05, angle_tol=0.08727):
+    """``attitude_ensemble`` with a plant of its own per realisation and the actuator's limit on the feedback command
+    (``tsat_tvlqr_ensemble_dispersed``): the gains once per slew from the MODEL inertia ``batch.Jmat``, then realisation (t, m)
+    flies inertia Jp, actuator matrix G and residual dipole m_res of ``plant[t, m]`` ((T, M, 21), ``disperse_plant``) under the
+    command ``clip(U - K dX, lo, hi)``. ``sat`` = (lo, hi), each (T, 3) or (3,), in units of ``u_scale`` A m^2 — the plan's own
+    box is ``(batch.ulo, batch.uhi)`` — or None for an unlimited command. Everything else as ``attitude_ensemble``; returns
+    its dict plus ``n_clipped`` (T, M), the knots at which the limit changed the command. ``nominal`` is the noise-free MODEL
+    plant under the same limits."""
+    lib = _abi.load()
+    T, N = batch.T, batch.N
+    c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    X, U, x0_sim, Qd, Qfd, Rd, plant = c(X), c(U), c(x0_sim), c(Qd), c(Qfd), c(Rd), c(plant)
+    if X.shape != (T, N, 7) or U.shape != (T, N - 1, 3) or Qd.shape != (T, 6) or Qfd.shape != (T, 6) or Rd.shape != (T, 3):
+        raise ValueError("array shapes do not match the batch")
+    if x0_sim.ndim != 3 or x0_sim.shape[0] != T or x0_sim.shape[2] != 7:
+        raise ValueError("x0_sim must be (T, M, 7)")
+    M = x0_sim.shape[1]
+    if plant.shape != (T, M, PLANT_W):
+        raise ValueError("plant must be (T, M, 21)")
+    lo = hi = None
+    if sat is not None:
+        lo, hi = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in sat)
+    o = _abi.TvlqrOptions()
+    lib.tsat_tvlqr_default_options(C.byref(o))
+    o.n_knots, o.n_tab, o.linearize_dt_sq, o.min_steps = N, batch.n_tab, int(bool(linearize_dt_sq)), int(min_steps)
+    o.u_scale, o.w_tol, o.angle_tol = float(u_scale), float(w_tol), float(angle_tol)
+    o.noise_mode, o.noise_seed = 1, int(noise_seed)
+    o.sigma_gyro, o.sigma_att = o.sigma_gyro * float(sigma_scale), o.sigma_att * float(sigma_scale)
+    id0 = None if noise_id0 is None else np.ascontiguousarray(noise_id0, dtype=np.int64)
+    if id0 is not None and id0.shape != (T,):
+        raise ValueError("noise_id0 must be (T,)")
+    nk = None if batch.n_knots is None else np.ascontiguousarray(batch.n_knots, dtype=np.int32)
+    st = np.zeros((T, M), dtype=_abi.TVLQR_STATS_DTYPE)
+    nom = np.zeros(T, dtype=_abi.TVLQR_STATS_DTYPE)
+    summary = np.zeros((T, 8))
+    ncl = np.zeros((T, M), dtype=np.int32)
+    K = np.empty((T, N - 1, 6, 3)) if want_K else None
+    Xs = np.empty((T, M, N, 7)) if want_trajectories else None
+    d = _abi.as_dp
+    rc = lib.tsat_tvlqr_ensemble_dispersed(solver._h, C.byref(o), T, batch.Btab.shape[0], M, d(X), d(U), d(batch.xf), d(batch.Btab),
+                                           _abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat),
+                                           d(Qd), d(Qfd), d(Rd), d(x0_sim),
+                                           None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), _abi.as_ip(nk),
+                                           d(plant), d(lo), d(hi), st.ctypes.data_as(C.c_void_p), d(summary),
+                                           nom.ctypes.data_as(C.c_void_p), d(K), d(Xs), _abi.as_ip(ncl))
+    if rc != 0:
+        raise RuntimeError(f"tsat_tvlqr_ensemble_dispersed failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
+    return dict(stats=st, summary=summary, nominal=nom, K=K, X_sim=Xs, n_clipped=ncl)
