@@ -7,17 +7,13 @@ four RK4 stages sees G u_sat + m_res / u_scale and has inertia Jp), ``ol.plant_n
 src/simulator.jl:5-23, ``ol.dyn7(..., Jp)`` per stage, table rows floor((k + c) dtau + tau0) clamped. With the model's plant and
 no limits it has to reproduce ``ol.tvlqr_batch`` (test_dispersed.py::test_reference_is_pinned_to_the_oracle).
 
-Also: the bracket on the clipped-knot counter, the sampled (t, m) pairs with their replacement cap, the cases of
-tests/ensemble_common.py, and the ctypes binding of the emulated kernel (tests/emu/tsat_emu_dispersed.cpp)."""
-import ctypes as C
+Also: the bracket on the clipped-knot counter, the sampled (t, m) pairs with their replacement cap and the cases of
+tests/ensemble_common.py, which also holds the ctypes binding of the emulated kernel (``EmuEnsemble.run(..., plant=...)``)."""
 import math
-import os
-import subprocess
 
 import numpy as np
 
 import ensemble_common as ec
-from conftest import ROOT
 
 MARGIN = 1e-7            # as the ensemble tests: index equality only where the reference is not on a threshold
 CLIP_BAND = 1e-7         # relative width of the band around a limit inside which the clip decision is a matter of the last bit
@@ -169,37 +165,3 @@ def all_five_plants(pkg, batch, M):
     """the plants of the parity tests: all five dispersions at LEVELS, default_rng(7)"""
     return pkg.tracking.disperse_plant(batch.Jmat, M, np.random.default_rng(7), **LEVELS)
 
-
-class EmuDispersed:
-    """ctypes binding of tests/emu/libtsat_emu_dispersed.so, built here with `make -f dispersed.mk`"""
-
-    def __init__(self, abi):
-        d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-f", "dispersed.mk", "-C", d, "libtsat_emu_dispersed.so"], stdout=subprocess.DEVNULL)
-        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_dispersed.so"))
-        self.abi = abi
-
-    def run(self, batch, X, U, Qd, Qfd, Rd, x0_sim, K, opts, plant, sat=None, noise_id0=None, want_trajectories=True):
-        T, N, M = batch.T, batch.N, x0_sim.shape[1]
-        o = self.abi.TvlqrOptions.from_buffer_copy(opts)
-        o.n_knots, o.n_tab = N, batch.n_tab
-        c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        X, U, Qd, Qfd, Rd, x0_sim, K, plant = c(X), c(U), c(Qd), c(Qfd), c(Rd), c(x0_sim), c(K), c(plant)
-        assert plant.shape == (T, M, 21)
-        lo, hi = (None, None) if sat is None else (c(np.broadcast_to(sat[0], (T, 3))), c(np.broadcast_to(sat[1], (T, 3))))
-        st = np.zeros((T, M), dtype=self.abi.TVLQR_STATS_DTYPE)
-        nom = np.zeros(T, dtype=self.abi.TVLQR_STATS_DTYPE)
-        summary = np.zeros((T, 8))
-        ncl = np.full((T, M), -1, dtype=np.int32)
-        Xs = np.full((T, M, N, 7), np.nan) if want_trajectories else None
-        d = self.abi.as_dp
-        id0 = None if noise_id0 is None else np.ascontiguousarray(noise_id0, dtype=np.int64)
-        nk = None if batch.n_knots is None else np.ascontiguousarray(batch.n_knots, dtype=np.int32)
-        rc = self.lib.emu_tvlqr_ensemble_dispersed(
-            C.byref(o), C.c_int64(T), C.c_int64(batch.Btab.shape[0]), C.c_int32(M), d(X), d(U), d(batch.xf), d(batch.Btab),
-            self.abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat), d(Qd), d(Qfd), d(Rd), d(x0_sim),
-            None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), self.abi.as_ip(nk), d(plant), d(lo), d(hi), d(K),
-            st.ctypes.data_as(C.c_void_p), d(summary), nom.ctypes.data_as(C.c_void_p), d(Xs), self.abi.as_ip(ncl))
-        if rc != 0:
-            raise RuntimeError(f"emu_tvlqr_ensemble_dispersed rc={rc}")
-        return dict(stats=st, summary=summary, nominal=nom, X_sim=Xs, n_clipped=ncl)

@@ -1,7 +1,7 @@
 """Shared pieces of tests/test_ensemble.py (CPU tier) and tests/test_gpu_ensemble.py (GPU tier): the cases, the oracle side of
 every comparison (the unchanged ``oracle_lib.tvlqr_batch`` on the batch replicated M times), the margin condition that keeps
 index equality meaningful, the bars of ``tests/test_tracking.py::_same_tracking`` per realisation, and the ctypes binding of the
-emulated ensemble kernel (tests/emu/tsat_emu_ensemble.cpp)."""
+emulated ensemble kernels, nominal and dispersed (tests/emu/tsat_emu_ensemble.cpp)."""
 import ctypes as C
 import dataclasses
 import os
@@ -123,15 +123,17 @@ def horizons(batch, n=None):
 
 
 class EmuEnsemble:
-    """ctypes binding of tests/emu/libtsat_emu_ensemble.so, built here with `make -f ensemble.mk`"""
+    """ctypes binding of tests/emu/libtsat_emu_ensemble.so (both emulated ensemble kernels), built here by the emulator Makefile"""
 
     def __init__(self, abi):
         d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-f", "ensemble.mk", "-C", d, "libtsat_emu_ensemble.so"], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", d, "libtsat_emu_ensemble.so"], stdout=subprocess.DEVNULL)
         self.lib = C.CDLL(os.path.join(d, "libtsat_emu_ensemble.so"))
         self.abi = abi
 
-    def run(self, batch, X, U, Qd, Qfd, Rd, x0_sim, K, opts, noise_id0=None, want_trajectories=True):
+    def run(self, batch, X, U, Qd, Qfd, Rd, x0_sim, K, opts, plant=None, sat=None, noise_id0=None, want_trajectories=True):
+        """emu_tvlqr_ensemble, or — with ``plant`` (T, M, 21) and optionally ``sat`` = (lo, hi) — emu_tvlqr_ensemble_dispersed,
+        whose result has ``n_clipped`` too"""
         T, N, M = batch.T, batch.N, x0_sim.shape[1]
         o = self.abi.TvlqrOptions.from_buffer_copy(opts)
         o.n_knots, o.n_tab = N, batch.n_tab
@@ -144,14 +146,24 @@ class EmuEnsemble:
         d = self.abi.as_dp
         id0 = None if noise_id0 is None else np.ascontiguousarray(noise_id0, dtype=np.int64)
         nk = None if batch.n_knots is None else np.ascontiguousarray(batch.n_knots, dtype=np.int32)
-        rc = self.lib.emu_tvlqr_ensemble(C.byref(o), C.c_int64(T), C.c_int64(batch.Btab.shape[0]), C.c_int32(M), d(X), d(U), d(batch.xf),
-                                         d(batch.Btab), self.abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt),
-                                         d(batch.Jmat), d(Qd), d(Qfd), d(Rd), d(x0_sim),
-                                         None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), self.abi.as_ip(nk), d(K),
-                                         st.ctypes.data_as(C.c_void_p), d(summary), nom.ctypes.data_as(C.c_void_p), d(Xs))
+        head = [C.byref(o), C.c_int64(T), C.c_int64(batch.Btab.shape[0]), C.c_int32(M), d(X), d(U), d(batch.xf), d(batch.Btab),
+                self.abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat), d(Qd), d(Qfd), d(Rd), d(x0_sim),
+                None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), self.abi.as_ip(nk)]
+        tail = [d(K), st.ctypes.data_as(C.c_void_p), d(summary), nom.ctypes.data_as(C.c_void_p), d(Xs)]
+        out = dict(stats=st, summary=summary, nominal=nom, X_sim=Xs)
+        if plant is None:
+            assert sat is None
+            name, rc = "emu_tvlqr_ensemble", self.lib.emu_tvlqr_ensemble(*head, *tail)
+        else:
+            plant = c(plant)
+            assert plant.shape == (T, M, 21)
+            lo, hi = (None, None) if sat is None else (c(np.broadcast_to(sat[0], (T, 3))), c(np.broadcast_to(sat[1], (T, 3))))
+            out["n_clipped"] = np.full((T, M), -1, dtype=np.int32)
+            name, rc = "emu_tvlqr_ensemble_dispersed", self.lib.emu_tvlqr_ensemble_dispersed(*head, d(plant), d(lo), d(hi), *tail,
+                                                                                               self.abi.as_ip(out["n_clipped"]))
         if rc != 0:
-            raise RuntimeError(f"emu_tvlqr_ensemble rc={rc}")
-        return dict(stats=st, summary=summary, nominal=nom, X_sim=Xs)
+            raise RuntimeError(f"{name} rc={rc}")
+        return out
 
     def summary(self, stats):
         T, M = stats.shape

@@ -16,7 +16,7 @@ import ensemble_common as ec
 
 @pytest.fixture(scope="module")
 def emu_disp(pkg):
-    return dc.EmuDispersed(pkg._abi)
+    return ec.EmuEnsemble(pkg._abi)
 
 
 @pytest.fixture(scope="module")

@@ -76,7 +76,7 @@ def test_gpu_dispersed_matches_reference_small(pkg, ol, gpu, ragged_case):
     # ragged horizons: zero beyond n_knots
     for t, n in enumerate(b.n_knots):
         assert np.all(got["X_sim"][t, :, n:] == 0) and np.all(got["K"][t, n - 1:] == 0)
-    emu = dc.EmuDispersed(pkg._abi).run(b, X, U, Qd, Qfd, Rd, x0s, got["K"], o, plant, sat=_box(b), noise_id0=ec.RAGGED_ID0)
+    emu = ec.EmuEnsemble(pkg._abi).run(b, X, U, Qd, Qfd, Rd, x0s, got["K"], o, plant, sat=_box(b), noise_id0=ec.RAGGED_ID0)
     d = float(np.max(np.abs(emu["X_sim"] - got["X_sim"])))
     print(f"[dispersed small] GPU against the emulator: max|dX_sim| {d:.2e}")
     assert d < 1e-9

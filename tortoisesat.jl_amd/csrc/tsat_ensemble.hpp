@@ -10,6 +10,10 @@
 // The per-lane noise is drawn where it is consumed, one RK4 stage at a time (3 Philox blocks + 3 Box-Muller pairs), so that
 // only nine noise values are live instead of 36.
 //
+// The roll-out (ensemble_rollout) is ONE function template over a small plant type: ModelPlant here, DispersedPlant in
+// tsat_dispersed.hpp (tsat_tvlqr_ensemble_dispersed). The statistic, the attitude error, the gain product, the table clock, the
+// noise draws and the RK4 stages exist once; ensemble_wave and dispersed_wave construct their plant and call it.
+//
 // Written over the lane abstraction of tsat_device.hpp (TSAT_DEV, TSAT_LANE, TSAT_CONSTMEM, ...) so that the CPU lane
 // emulator runs the same source (tests/emu/tsat_emu_ensemble.cpp). The plant, the generator and the table clock are the
 // device functions the tracking kernel uses: dyn_sim_h, plant_noise, brow_index, control_scale.
@@ -63,8 +67,27 @@ TSAT_DEV real ensemble_angle(const Traj<real>& tr, const real x[7]) {
   return 2 * acos_(e0 < 1 ? e0 : (real)1);
 }
 
-template <typename real, int DIAGJ>
-TSAT_DEV void ensemble_wave(const EnsArgs<real>& a, int traj, int wave) {
+// The MODEL plant: every realisation flies the satellite the plan was made for. A plant type answers what differs between the
+// entry points and nothing else (the other one is DispersedPlant, tsat_dispersed.hpp): the instantiation of dyn_sim_h /
+// control_scale it flies, what it loads once per lane, the Traj the dynamics read, what becomes of the feedback command on its
+// way to the torquers, and what it stores per realisation besides the statistic.
+template <typename real, int DIAGJ_>
+struct ModelPlant {
+  static constexpr int DIAGJ = DIAGJ_;
+  TSAT_DEV void load(const Traj<real>&, int, int) {}
+  TSAT_DEV const Traj<real>& traj(const Traj<real>& tr) const { return tr; }
+  TSAT_DEV real command(int, real v, real cs) { return v * cs; }          // component c of U - K dX, in the plant's units
+  TSAT_DEV void actuate(const real uc[3], real, real us[3]) {
+    for (int c = 0; c < 3; ++c) us[c] = uc[c];
+  }
+  TSAT_DEV void store(size_t) const {}
+};
+
+// One closed loop per lane: realisation 64 wave + lane of slew traj on the plant `plant` (the choice is a template argument:
+// nothing in the loop asks which entry point it serves).
+template <typename real, typename Plant>
+TSAT_DEV void ensemble_rollout(const EnsArgs<real>& a, Plant& plant, int traj, int wave) {
+  constexpr int DIAGJ = Plant::DIAGJ;
   const int lane = TSAT_LANE();
   const int NS = a.N, n_tab = a.n_tab, M = a.M;
   const int N = a.nk ? a.nk[traj] : a.N;                       // own horizon; slabs keep the stride NS
@@ -79,6 +102,8 @@ TSAT_DEV void ensemble_wave(const EnsArgs<real>& a, int traj, int wave) {
   const TSAT_CONSTMEM real* kdg = (const TSAT_CONSTMEM real*)(a.KD + (size_t)traj * (NS - 1) * KDW);
   const TSAT_CONSTMEM real* bt = (const TSAT_CONSTMEM real*)(a.BT + (size_t)a.bidx[traj] * n_tab * 4);
   const Traj<real> tr = ensemble_traj<real>(Pc, a.us, N, n_tab);
+  plant.load(tr, traj, r);
+  const Traj<real>& tp = plant.traj(tr);                       // what dyn_sim_h reads
   const long long gid = (a.nid0 ? a.nid0[traj] : (long long)traj * (long long)M) + (long long)r;
   TSAT_GLOBAL real* xs = (a.XS && live && noisy) ? (TSAT_GLOBAL real*)(a.XS + ((size_t)traj * M + r) * NS * 7) : nullptr;
   real x[7];
@@ -110,12 +135,13 @@ TSAT_DEV void ensemble_wave(const EnsArgs<real>& a, int traj, int wave) {
       dX[4] = s1 * x[5] + x[3] * a2 + (a3 * x[4] - a1 * x[6]);
       dX[5] = s1 * x[6] + x[3] * a3 + (a1 * x[5] - a2 * x[4]);
     }
-    real us[3];
+    real uc[3], us[3];
     for (int c = 0; c < 3; ++c) {
       real v = xr[7 + c];
       for (int j = 0; j < 6; ++j) v += kd[c * 7 + j] * dX[j];   // kd = -K_lqr
-      us[c] = v * cs;
+      uc[c] = plant.command(c, v, cs);
     }
+    plant.actuate(uc, cs, us);
     // rows at tau, tau + dtau/2, tau + dtau: wave-uniform indices, said so (the clock is fp64 arithmetic on the vector unit)
     const TSAT_CONSTMEM real* p0 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tr, k, 0.0)) * 4;
     const TSAT_CONSTMEM real* p1 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tr, k, 0.5)) * 4;
@@ -124,16 +150,16 @@ TSAT_DEV void ensemble_wave(const EnsArgs<real>& a, int traj, int wave) {
     real k1[7], k2[7], k3[7], k4[7], t[7], nz[9];
     for (int i = 0; i < 9; ++i) nz[i] = 0;
     if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 0, a.sg, a.sa, a.fa, nz);
-    dyn_sim_h<real, DIAGJ>(tr, x, us, b0, noisy, nz, k1);
+    dyn_sim_h<real, DIAGJ>(tp, x, us, b0, noisy, nz, k1);
     for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k1[i];
     if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 1, a.sg, a.sa, a.fa, nz);
-    dyn_sim_h<real, DIAGJ>(tr, t, us, b1, noisy, nz, k2);
+    dyn_sim_h<real, DIAGJ>(tp, t, us, b1, noisy, nz, k2);
     for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k2[i];
     if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 2, a.sg, a.sa, a.fa, nz);
-    dyn_sim_h<real, DIAGJ>(tr, t, us, b1, noisy, nz, k3);
+    dyn_sim_h<real, DIAGJ>(tp, t, us, b1, noisy, nz, k3);
     for (int i = 0; i < 7; ++i) t[i] = x[i] + k3[i];
     if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 3, a.sg, a.sa, a.fa, nz);
-    dyn_sim_h<real, DIAGJ>(tr, t, us, b2, noisy, nz, k4);
+    dyn_sim_h<real, DIAGJ>(tp, t, us, b2, noisy, nz, k4);
     for (int i = 0; i < 7; ++i) x[i] = x[i] + (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) * (real)(1.0 / 6.0);
   }
   // last sample j = N
@@ -149,9 +175,19 @@ TSAT_DEV void ensemble_wave(const EnsArgs<real>& a, int traj, int wave) {
     st.slew_time = (double)tr.h * (first ? (double)first : (double)N);
     st.final_w_norm = (double)wN;
     st.final_angle = (double)angN;
-    if (noisy) a.stats[(size_t)traj * M + r] = st;
-    else a.stats_nom[traj] = st;
+    if (noisy) {
+      a.stats[(size_t)traj * M + r] = st;
+      plant.store((size_t)traj * M + r);
+    } else {
+      a.stats_nom[traj] = st;
+    }
   }
+}
+
+template <typename real, int DIAGJ>
+TSAT_DEV void ensemble_wave(const EnsArgs<real>& a, int traj, int wave) {
+  ModelPlant<real, DIAGJ> plant;
+  ensemble_rollout<real>(a, plant, traj, wave);
 }
 
 // gains of one slew, exactly as tvlqr_trajectory computes them before its roll-out: terminal S = Qf_lqr, then chunks of

@@ -162,18 +162,11 @@ def ensemble_noise_ids(T, M, noise_id0=None):
     return id0[:, None] + np.arange(int(M), dtype=np.int64)[None, :]
 
 
-def attitude_ensemble(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, noise_id0=None, sigma_scale=1.0,
-                      want_K=False, want_trajectories=False, linearize_dt_sq=True, u_scale=1e-2, min_steps=10, w_tol=0.05,
-                      angle_tol=0.08727):
-    """Track every solved slew under M noise realisations in ONE call (``tsat_tvlqr_ensemble``): the TVLQR gains once per
-    slew, then M closed loops per slew on the noisy plant, one realisation per GPU lane — the failure probability and the
-    slew-time spread of a plan, where src/monte_carlo.jl:199-262 draws a single realisation per slew.
-    X (T,N,7), U (T,N-1,3) are the solved trajectories, x0_sim (T,M,7) the perturbed initial states
-    (``ensemble_initial_states``). Realisation m of slew t draws generator id ``noise_id0[t] + m`` (default t M + m) under
-    ``noise_seed``: it is the run ``attitude_simulation(..., x0_sim[:, m], noise_seed=noise_seed, noise_ids=noise_id0 + m)``
-    makes. ``sigma_scale`` multiplies the reference's gyro and attitude noise levels. Returns dict(stats (T,M) records, summary (T,8) =
-    [M, failures, mean / min / max slew time of the realisations that arrived, mean slew time of all, max final angle, max
-    final rate], nominal (T,) statistic of the noise-free plant from X[:,0], K (T,N-1,6,3) or None, X_sim (T,M,N,7) or None)."""
+def _ensemble_call(solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, noise_id0, sigma_scale, want_K, want_trajectories,
+                   linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol):
+    """What ``tsat_tvlqr_ensemble`` and ``tsat_tvlqr_ensemble_dispersed`` have in common: the shape checks, the option block and
+    the output buffers. Returns (lib, head, tail, out): the C arguments from the handle to ``n_knots`` and from ``stats`` to
+    ``X_sim`` — the dispersed call puts its own between and after them — and the dict the caller returns."""
     lib = _abi.load()
     T, N = batch.T, batch.N
     c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
@@ -199,14 +192,31 @@ def attitude_ensemble(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise
     K = np.empty((T, N - 1, 6, 3)) if want_K else None
     Xs = np.empty((T, M, N, 7)) if want_trajectories else None
     d = _abi.as_dp
-    rc = lib.tsat_tvlqr_ensemble(solver._h, C.byref(o), T, batch.Btab.shape[0], M, d(X), d(U), d(batch.xf), d(batch.Btab),
-                                 _abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat),
-                                 d(Qd), d(Qfd), d(Rd), d(x0_sim), None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)),
-                                 _abi.as_ip(nk), st.ctypes.data_as(C.c_void_p), d(summary), nom.ctypes.data_as(C.c_void_p),
-                                 d(K), d(Xs))
+    head = [solver._h, C.byref(o), T, batch.Btab.shape[0], M, d(X), d(U), d(batch.xf), d(batch.Btab), _abi.as_ip(batch.btab_idx),
+            d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat), d(Qd), d(Qfd), d(Rd), d(x0_sim),
+            None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), _abi.as_ip(nk)]
+    tail = [st.ctypes.data_as(C.c_void_p), d(summary), nom.ctypes.data_as(C.c_void_p), d(K), d(Xs)]
+    return lib, head, tail, dict(stats=st, summary=summary, nominal=nom, K=K, X_sim=Xs)
+
+
+def attitude_ensemble(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, noise_id0=None, sigma_scale=1.0,
+                      want_K=False, want_trajectories=False, linearize_dt_sq=True, u_scale=1e-2, min_steps=10, w_tol=0.05,
+                      angle_tol=0.08727):
+    """Track every solved slew under M noise realisations in ONE call (``tsat_tvlqr_ensemble``): the TVLQR gains once per
+    slew, then M closed loops per slew on the noisy plant, one realisation per GPU lane — the failure probability and the
+    slew-time spread of a plan, where src/monte_carlo.jl:199-262 draws a single realisation per slew.
+    X (T,N,7), U (T,N-1,3) are the solved trajectories, x0_sim (T,M,7) the perturbed initial states
+    (``ensemble_initial_states``). Realisation m of slew t draws generator id ``noise_id0[t] + m`` (default t M + m) under
+    ``noise_seed``: it is the run ``attitude_simulation(..., x0_sim[:, m], noise_seed=noise_seed, noise_ids=noise_id0 + m)``
+    makes. ``sigma_scale`` multiplies the reference's gyro and attitude noise levels. Returns dict(stats (T,M) records, summary (T,8) =
+    [M, failures, mean / min / max slew time of the realisations that arrived, mean slew time of all, max final angle, max
+    final rate], nominal (T,) statistic of the noise-free plant from X[:,0], K (T,N-1,6,3) or None, X_sim (T,M,N,7) or None)."""
+    lib, head, tail, out = _ensemble_call(solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, noise_id0, sigma_scale, want_K,
+                                          want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol)
+    rc = lib.tsat_tvlqr_ensemble(*head, *tail)
     if rc != 0:
         raise RuntimeError(f"tsat_tvlqr_ensemble failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
-    return dict(stats=st, summary=summary, nominal=nom, K=K, X_sim=Xs)
+    return out
 
 
 PLANT_W = 21
@@ -272,43 +282,19 @@ def attitude_ensemble_dispersed(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd,
     box is ``(batch.ulo, batch.uhi)`` — or None for an unlimited command. Everything else as ``attitude_ensemble``; returns
     its dict plus ``n_clipped`` (T, M), the knots at which the limit changed the command. ``nominal`` is the noise-free MODEL
     plant under the same limits."""
-    lib = _abi.load()
-    T, N = batch.T, batch.N
+    lib, head, tail, out = _ensemble_call(solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, noise_id0, sigma_scale, want_K,
+                                          want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol)
+    T, M = out["stats"].shape
     c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-    X, U, x0_sim, Qd, Qfd, Rd, plant = c(X), c(U), c(x0_sim), c(Qd), c(Qfd), c(Rd), c(plant)
-    if X.shape != (T, N, 7) or U.shape != (T, N - 1, 3) or Qd.shape != (T, 6) or Qfd.shape != (T, 6) or Rd.shape != (T, 3):
-        raise ValueError("array shapes do not match the batch")
-    if x0_sim.ndim != 3 or x0_sim.shape[0] != T or x0_sim.shape[2] != 7:
-        raise ValueError("x0_sim must be (T, M, 7)")
-    M = x0_sim.shape[1]
+    plant = c(plant)
     if plant.shape != (T, M, PLANT_W):
         raise ValueError("plant must be (T, M, 21)")
     lo = hi = None
     if sat is not None:
         lo, hi = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in sat)
-    o = _abi.TvlqrOptions()
-    lib.tsat_tvlqr_default_options(C.byref(o))
-    o.n_knots, o.n_tab, o.linearize_dt_sq, o.min_steps = N, batch.n_tab, int(bool(linearize_dt_sq)), int(min_steps)
-    o.u_scale, o.w_tol, o.angle_tol = float(u_scale), float(w_tol), float(angle_tol)
-    o.noise_mode, o.noise_seed = 1, int(noise_seed)
-    o.sigma_gyro, o.sigma_att = o.sigma_gyro * float(sigma_scale), o.sigma_att * float(sigma_scale)
-    id0 = None if noise_id0 is None else np.ascontiguousarray(noise_id0, dtype=np.int64)
-    if id0 is not None and id0.shape != (T,):
-        raise ValueError("noise_id0 must be (T,)")
-    nk = None if batch.n_knots is None else np.ascontiguousarray(batch.n_knots, dtype=np.int32)
-    st = np.zeros((T, M), dtype=_abi.TVLQR_STATS_DTYPE)
-    nom = np.zeros(T, dtype=_abi.TVLQR_STATS_DTYPE)
-    summary = np.zeros((T, 8))
     ncl = np.zeros((T, M), dtype=np.int32)
-    K = np.empty((T, N - 1, 6, 3)) if want_K else None
-    Xs = np.empty((T, M, N, 7)) if want_trajectories else None
     d = _abi.as_dp
-    rc = lib.tsat_tvlqr_ensemble_dispersed(solver._h, C.byref(o), T, batch.Btab.shape[0], M, d(X), d(U), d(batch.xf), d(batch.Btab),
-                                           _abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat),
-                                           d(Qd), d(Qfd), d(Rd), d(x0_sim),
-                                           None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), _abi.as_ip(nk),
-                                           d(plant), d(lo), d(hi), st.ctypes.data_as(C.c_void_p), d(summary),
-                                           nom.ctypes.data_as(C.c_void_p), d(K), d(Xs), _abi.as_ip(ncl))
+    rc = lib.tsat_tvlqr_ensemble_dispersed(*head, d(plant), d(lo), d(hi), *tail, _abi.as_ip(ncl))
     if rc != 0:
         raise RuntimeError(f"tsat_tvlqr_ensemble_dispersed failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
-    return dict(stats=st, summary=summary, nominal=nom, K=K, X_sim=Xs, n_clipped=ncl)
+    return dict(out, n_clipped=ncl)
