@@ -374,6 +374,36 @@ int  tsat_mpc_run(tsat_handle* h, const tsat_options* o, int32_t n_steps, int32_
  * needs to price the loop's memory traffic without bringing per-step statistics to the host */
 int  tsat_mpc_tally(tsat_handle* h, int64_t* tally /* 4 x T */);
 
+/* The same receding-horizon loop on a NOISY, DISPERSED plant with limits: the plant of one realisation of
+ * tsat_tvlqr_ensemble_dispersed per trajectory, re-planned against instead of tracked with fixed gains. Steps 1 and 4 are those of
+ * tsat_mpc_run (the solver keeps the MODEL inertia of the uploaded batch; the gains play no part); per control step s
+ *   2. u_cmd = U[0], u_sat = min(max(u_cmd, sat_lo[t]), sat_hi[t]) component-wise — a step counts as clipped when any component
+ *      changed; x_t goes to X_hist, u_sat to U_hist;
+ *   3. the plant advances over dt by RK4 (the noise layout is per RK4 stage: no integrator argument) of the model dynamics with
+ *      inertia Jp[t] and dipole G[t] u_sat + m_res[t] / u_scale, field rows floor(fma(c, dtau, tau0)), c = 0, 1/2, 1, clamped;
+ *      with po->noise_mode = 1 the nine draws of (generator id noise_id[t], knot step0 + s, stage) enter every stage's state and
+ *      field row exactly as in the ensemble roll-out (draw layout at tsat_tvlqr_options); noise_mode = 0 is the noise-free plant;
+ *   5. the slew-time statistic of tsat_tvlqr_stats on the history, evaluated while the loop runs: sample j (1-based) is x_{j-1},
+ *      n_steps + 1 samples, slew_index = first j > po->min_steps with |w| < w_tol and error angle to the resident xf < angle_tol,
+ *      slew_time = dt * index (dt * (n_steps + 1) on failure), final_* from x_{n_steps}.
+ *   plant      21 x T (TSAT_PLANT_W: Jp 9, G 9, m_res 3, as tsat_tvlqr_ensemble_dispersed) or NULL = the model's plant
+ *              (Jmat as the symmetric tensor of its upper triangle, G = I, m_res = 0)
+ *   sat_lo, sat_hi   3 x T each, units of u_scale; both NULL = unlimited
+ *   noise_id   T or NULL (= t)
+ *   step0      knot of the first control step for the noise draws: a second call with step0 = the steps already made continues
+ *              the simulation as tsat_mpc_run does and draws the noise of the later steps; its statistic counts its own samples
+ *   X_hist, U_hist, stats_last, solve_ms   as tsat_mpc_run;  stats T out (may be NULL), n_clipped T out (may be NULL)
+ * Of `po` n_knots, n_tab and linearize_dt_sq are ignored. Rejected with -1 (text in tsat_last_error): rate_as_written != 0,
+ * noise_mode not 0 or 1, a non-finite plant entry, Jp not symmetric or not positive definite (the checks of
+ * tsat_tvlqr_ensemble_dispersed), exactly one limit array NULL, sat_lo > sat_hi, n_steps < 1, step0 < 0 or step0 + n_steps
+ * beyond the 32-bit knot counter of the generator, precision != 64, and everything tsat_mpc_run rejects. Afterwards the resident
+ * batch is in the state tsat_mpc_run leaves (advanced x0 / tau0 with the host copies refreshed, shifted warm start, last plan,
+ * tsat_mpc_tally). */
+int  tsat_mpc_run_dispersed(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                            const double* plant, const double* sat_lo, const double* sat_hi, const int64_t* noise_id,
+                            double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats, int32_t* n_clipped,
+                            float* solve_ms);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Sweep exchange across GPUs. The reference's Monte-Carlo is a serial loop whose iterations share nothing but the result
  * lists they append to (src/monte_carlo.jl:52-66, 199-235; src/paper_images/heatmap.jl:114-243). Here each rank — one

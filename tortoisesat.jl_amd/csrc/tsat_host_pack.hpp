@@ -224,6 +224,50 @@ inline std::string check_tv_options(const tsat_tvlqr_options& o) {
   return "";
 }
 
+// The host only validates dispersed plants (tsat_tvlqr_ensemble_dispersed, tsat_mpc_run_dispersed): "" or what is wrong with
+// one record of TSAT_PLANT_W doubles (Jp 9, G 9, m_res 3) — the caller says where
+inline std::string check_plant_record(const double* p) {
+  double big = 0;
+  for (int i = 0; i < TSAT_PLANT_W; ++i)
+    if (!std::isfinite(p[i])) return "non-finite plant entry";
+  for (int i = 0; i < 9; ++i) big = std::fmax(big, std::fabs(p[i]));
+  for (int r = 0; r < 3; ++r)
+    for (int c = r + 1; c < 3; ++c)
+      if (std::fabs(p[3 * c + r] - p[3 * r + c]) > 1e-12 * big) return "Jp is not symmetric";
+  const double a = p[0], b = p[3], c = p[6], dd = p[4], e = p[7], f = p[8];
+  const double m2 = a * dd - b * b, m3 = a * (dd * f - e * e) + (b * (c * e - b * f) + c * (b * e - c * dd));
+  if (!(a > 0 && m2 > 0 && m3 > 0)) return "Jp is not positive definite";
+  return "";
+}
+// ... and the limits of T slews (3 x T each, both or neither): "" or the reason
+inline std::string check_limits(const double* sat_lo, const double* sat_hi, int64_t T) {
+  if ((sat_lo == nullptr) != (sat_hi == nullptr)) return "exactly one of sat_lo / sat_hi is NULL: give both limits or neither";
+  if (sat_lo)
+    for (int64_t t = 0; t < T; ++t)
+      for (int c = 0; c < 3; ++c)
+        if (!(sat_lo[3 * t + c] <= sat_hi[3 * t + c])) return "sat_lo > sat_hi (or not a number) at t = " + std::to_string(t);
+  return "";
+}
+
+// what tsat_mpc_run_dispersed rejects beyond tsat_mpc_run's own checks: "" or the reason (plant 21 x T or null, limits 3 x T or null)
+inline std::string check_mpc_dispersed(const tsat_tvlqr_options& po, int32_t n_steps, int64_t step0, const double* plant,
+                                       const double* sat_lo, const double* sat_hi, int64_t T) {
+  if (n_steps < 1) return "n_steps must be >= 1";
+  if (step0 < 0 || step0 + (int64_t)n_steps > 0x7fffffffLL)
+    return "step0 must be >= 0 and step0 + n_steps within the generator's 32-bit knot counter";
+  if (po.noise_mode != 0 && po.noise_mode != 1) return "noise_mode must be 0 (noise-free plant) or 1 (generated)";
+  if (po.rate_as_written != 0) return "rate_as_written must be 0: the statistic is evaluated while the loop runs";
+  if (po.min_steps < 0) return "min_steps must be >= 0";
+  const std::string lim = check_limits(sat_lo, sat_hi, T);
+  if (!lim.empty()) return lim;
+  if (plant)
+    for (int64_t t = 0; t < T; ++t) {
+      const std::string bad = check_plant_record(plant + (size_t)t * TSAT_PLANT_W);
+      if (!bad.empty()) return bad + " at t = " + std::to_string(t);
+    }
+  return "";
+}
+
 // scales of the three draws of `simulator` (src/simulator.jl:5,10,22)
 inline void tv_noise_defaults(tsat_tvlqr_options& o) {
   const double deg = 3.14159265358979323846 / 180.0;

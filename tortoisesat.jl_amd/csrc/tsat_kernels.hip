@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 #include "tsat_host_pack.hpp"
+#include "tsat_mpc_dispersed.hpp"
 
 using namespace tsat;
 
@@ -34,6 +35,9 @@ hipError_t tsat_launch_solve_packed_mixed8(const KArgs<double>& a, int rk4, int 
 hipError_t tsat_launch_solve_packed_mixed8w(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
 hipError_t tsat_launch_solve_packed_mixed16w(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
 hipError_t tsat_launch_solve_packed_mixed4w(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
+
+// the plant step of tsat_mpc_run_dispersed (tsat_kernels_mpc_dispersed.hip); step 0 also packs the call's plant records
+hipError_t tsat_launch_mpc_dispersed(const MpcDispArgs<double>& a, const double* plant, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -123,7 +127,9 @@ struct tsat_handle {
          WS_HZ_B, WS_HZ_DT, WS_HZ_CUT, WS_HZ_C, WS_HZ_I, WS_BT_COEF, WS_BT_KEP, WS_BT_T0, WS_BT_TF, WS_BT_POS, WS_BT_B,
          WS_JW, WS_MPC_HX, WS_MPC_HU,
          WS_DL_X, WS_DL_U, WS_DL_K, WS_AG_X, WS_AG_U, WS_AG_ST, WS_AG_XA, WS_AG_UA, WS_AG_STA,   // staging: WS_DL_X .. WS_AG_STA (tsat_workspace_trim)
-         WS_AG_CHK, WS_MPC_TALLY, WS_ENDGAME, WS_COUNT };
+         WS_AG_CHK, WS_MPC_TALLY, WS_ENDGAME,
+         WS_MPCD_PLANT, WS_MPCD_PL, WS_MPCD_SAT, WS_MPCD_NID, WS_MPCD_REC, WS_MPCD_ST, WS_MPCD_CLIP,   // tsat_mpc_run_dispersed
+         WS_COUNT };
   void* ws[WS_COUNT] = {};
   size_t ws_bytes[WS_COUNT] = {};
   // RCCL communicator of the sweep (tsat_comm_init): one rank per handle / GPU
@@ -513,6 +519,31 @@ int tsat_set_endgame(tsat_handle* h, int32_t suspend_at) {
   return 0;
 }
 
+namespace {
+// the end of both receding-horizon loops, once their launches are queued (rc: what queueing them returned): wait, bring the
+// history and the last solve's statistics down, refresh the host mirrors of x0 / tau0
+int mpc_collect(tsat_handle* h, int rc, const char* name, const double* dHX, const double* dHU, size_t nX, size_t nU, double* X_hist,
+                double* U_hist, tsat_stats* stats_last, float* solve_ms) {
+  const size_t T = (size_t)h->T;
+  if (!rc && (hipEventRecord(h->ev1, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)) rc = -10;
+  if (!rc && solve_ms && hipEventElapsedTime(solve_ms, h->ev0, h->ev1) != hipSuccess) rc = -10;
+  if (!rc && hipMemcpy(X_hist, dHX, nX * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = -10;
+  if (!rc && hipMemcpy(U_hist, dHU, nU * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = -10;
+  if (!rc && stats_last && hipMemcpy(stats_last, h->stats, T * sizeof(tsat_stats), hipMemcpyDeviceToHost) != hipSuccess) rc = -10;
+  // the loop advanced x0 and tau0 inside the device parameter records: refresh the host mirrors tsat_tvlqr_resident packs
+  // its own records from, so that tracking after an MPC run linearises against the field rows the last plan was solved on
+  std::vector<double> Pb(T * PSTRIDE);
+  if (!rc && hipMemcpy(Pb.data(), h->P, Pb.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = -10;
+  if (rc) { h->solved = false; return fail(h, rc, std::string("launch or copy failed in ") + name); }
+  for (size_t t = 0; t < T; ++t) {
+    for (int i = 0; i < 7; ++i) h->hx0[7 * t + i] = Pb[t * PSTRIDE + P_X0 + i];
+    h->htau0[t] = Pb[t * PSTRIDE + P_TAU0];
+  }
+  h->solved = true;
+  return 0;
+}
+}  // namespace
+
 int tsat_mpc_run(tsat_handle* h, const tsat_options* o, int32_t n_steps, int32_t plant_integrator, double* X_hist,
                  double* U_hist, tsat_stats* stats_last, float* solve_ms) {
   if (!h || !o) return -1;
@@ -548,22 +579,7 @@ int tsat_mpc_run(tsat_handle* h, const tsat_options* o, int32_t n_steps, int32_t
     hipLaunchKernelGGL(adv, dim3((unsigned)h->T), dim3(64), 0, h->stream, m);
     if (hipGetLastError() != hipSuccess) rc = -10;
   }
-  if (!rc && (hipEventRecord(h->ev1, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)) rc = -10;
-  if (!rc && solve_ms && hipEventElapsedTime(solve_ms, h->ev0, h->ev1) != hipSuccess) rc = -10;
-  if (!rc && hipMemcpy(X_hist, dHX, nX * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = -10;
-  if (!rc && hipMemcpy(U_hist, dHU, nU * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = -10;
-  if (!rc && stats_last && hipMemcpy(stats_last, h->stats, T * sizeof(tsat_stats), hipMemcpyDeviceToHost) != hipSuccess) rc = -10;
-  // the loop advanced x0 and tau0 inside the device parameter records: refresh the host mirrors tsat_tvlqr_resident packs
-  // its own records from, so that tracking after an MPC run linearises against the field rows the last plan was solved on
-  std::vector<double> Pb(T * PSTRIDE);
-  if (!rc && hipMemcpy(Pb.data(), h->P, Pb.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = -10;
-  if (rc) { h->solved = false; return fail(h, rc, "launch or copy failed in tsat_mpc_run"); }
-  for (size_t t = 0; t < T; ++t) {
-    for (int i = 0; i < 7; ++i) h->hx0[7 * t + i] = Pb[t * PSTRIDE + P_X0 + i];
-    h->htau0[t] = Pb[t * PSTRIDE + P_TAU0];
-  }
-  h->solved = true;
-  return 0;
+  return mpc_collect(h, rc, "tsat_mpc_run", dHX, dHU, nX, nU, X_hist, U_hist, stats_last, solve_ms);
 }
 
 int tsat_mpc_tally(tsat_handle* h, int64_t* tally) {
@@ -572,6 +588,71 @@ int tsat_mpc_tally(tsat_handle* h, int64_t* tally) {
   TSAT_HIP(h, hipSetDevice(h->dev));
   static_assert(sizeof(long long) == sizeof(int64_t), "tally element");
   TSAT_HIP(h, hipMemcpy(tally, h->ws[tsat_handle::WS_MPC_TALLY], (size_t)h->T * 4 * sizeof(int64_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int tsat_mpc_run_dispersed(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                           const double* plant, const double* sat_lo, const double* sat_hi, const int64_t* noise_id,
+                           double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats, int32_t* n_clipped,
+                           float* solve_ms) {
+  if (!h || !o || !po) return -1;
+  if (!h->uploaded) return fail(h, -1, "tsat_batch_upload has not been called");
+  const std::string why = check_options(*o, h->N, h->n_tab, h->max_ls);
+  if (!why.empty()) return fail(h, -1, why);
+  if (o->precision != 64) return fail(h, -1, "tsat_mpc_run_dispersed runs the fp64 build only (precision must be 64)");
+  const std::string bad = check_mpc_dispersed(*po, n_steps, step0, plant, sat_lo, sat_hi, h->T);
+  if (!bad.empty()) return fail(h, -1, bad);
+  if (!X_hist || !U_hist) return fail(h, -1, "null array");
+  TSAT_HIP(h, hipSetDevice(h->dev));
+  const size_t T = (size_t)h->T, nX = T * ((size_t)n_steps + 1) * 7, nU = T * (size_t)n_steps * 3;
+  double* dHX = (double*)ws_get(h, tsat_handle::WS_MPC_HX, nX * 8);
+  double* dHU = (double*)ws_get(h, tsat_handle::WS_MPC_HU, nU * 8);
+  long long* dTally = (long long*)ws_get(h, tsat_handle::WS_MPC_TALLY, T * 4 * sizeof(long long));
+  double* dPlant = plant ? (double*)ws_get(h, tsat_handle::WS_MPCD_PLANT, T * TSAT_PLANT_W * 8) : nullptr;
+  double* dPL = (double*)ws_get(h, tsat_handle::WS_MPCD_PL, T * PLW * 8);
+  double* dSat = (double*)ws_get(h, tsat_handle::WS_MPCD_SAT, T * SATW * 8);
+  long long* dNid = noise_id ? (long long*)ws_get(h, tsat_handle::WS_MPCD_NID, T * sizeof(long long)) : nullptr;
+  MpcDispRec* dRec = (MpcDispRec*)ws_get(h, tsat_handle::WS_MPCD_REC, T * sizeof(MpcDispRec));
+  tsat_tvlqr_stats* dSt = (tsat_tvlqr_stats*)ws_get(h, tsat_handle::WS_MPCD_ST, T * sizeof(tsat_tvlqr_stats));
+  int* dClip = (int*)ws_get(h, tsat_handle::WS_MPCD_CLIP, T * sizeof(int));
+  if (!dHX || !dHU || !dTally || (plant && !dPlant) || !dPL || !dSat || (noise_id && !dNid) || !dRec || !dSt || !dClip)
+    return fail(h, -10, "device allocation failed in tsat_mpc_run_dispersed");
+  std::vector<double> sat(T * SATW);               // a NULL limit is +-inf: the step has one code path
+  for (size_t t = 0; t < T; ++t)
+    for (int c = 0; c < 3; ++c) {
+      sat[SATW * t + c] = sat_lo ? sat_lo[3 * t + c] : -HUGE_VAL;
+      sat[SATW * t + 3 + c] = sat_hi ? sat_hi[3 * t + c] : HUGE_VAL;
+    }
+  TSAT_HIP(h, hipMemcpy(dSat, sat.data(), sat.size() * 8, hipMemcpyHostToDevice));
+  if (plant) TSAT_HIP(h, hipMemcpy(dPlant, plant, T * TSAT_PLANT_W * 8, hipMemcpyHostToDevice));
+  if (noise_id) TSAT_HIP(h, hipMemcpy(dNid, noise_id, T * sizeof(long long), hipMemcpyHostToDevice));
+  TSAT_HIP(h, hipMemsetAsync(dTally, 0, T * 4 * sizeof(long long), h->stream));
+  h->mpc_tally_T = (int64_t)T;
+  const KArgs<double> a = solve_args(h, o);
+  if (!a.JW && uses_packed_build(h, 64))     // a packed kernel launched with JW = nullptr would fault on the device
+    return fail(h, -10, "device allocation of the packed builds' Jacobian workspace failed");
+  MpcDispArgs<double> md = {};
+  MpcArgs<double>& m = md.m;
+  m.T = (int)h->T; m.N = h->N; m.n_tab = h->n_tab; m.plant_integ = 4; m.n_steps = n_steps; m.us = o->u_scale;
+  m.P = h->P; m.BT = h->BT; m.bidx = h->bidx; m.nk = h->ragged ? h->nk : nullptr; m.XU = h->XU; m.U0 = h->U0;
+  m.HX = dHX; m.HU = dHU; m.stats = h->stats; m.tally = dTally;
+  md.d.PL = dPL; md.d.Mp = 1; md.d.SAT = dSat; md.d.nclip = dClip;
+  EnsArgs<double>& e = md.d.e;
+  e.min_steps = po->min_steps; e.w_tol = po->w_tol; e.ang_tol = po->angle_tol;
+  e.k0 = (unsigned)(po->noise_seed & 0xFFFFFFFFull); e.k1 = (unsigned)(po->noise_seed >> 32);
+  e.nid0 = dNid; e.sg = po->sigma_gyro; e.sa = po->sigma_att; e.fa = po->field_amp; e.stats = dSt;
+  md.noisy = po->noise_mode; md.step0 = (long long)step0; md.rec = dRec;
+  int rc = 0;
+  if (hipEventRecord(h->ev0, h->stream) != hipSuccess) rc = -10;
+  for (int s = 0; s < n_steps && !rc; ++s) {   // 2 n_steps launches (+ the pack) queued back to back; the stream orders them
+    if (launch_solve(h, o, a) != hipSuccess) rc = -10;
+    m.step = s;
+    if (!rc && tsat_launch_mpc_dispersed(md, dPlant, h->stream) != hipSuccess) rc = -10;
+  }
+  rc = mpc_collect(h, rc, "tsat_mpc_run_dispersed", dHX, dHU, nX, nU, X_hist, U_hist, stats_last, solve_ms);
+  if (rc) return rc;
+  if (stats) TSAT_HIP(h, hipMemcpy(stats, dSt, T * sizeof(tsat_tvlqr_stats), hipMemcpyDeviceToHost));
+  if (n_clipped) TSAT_HIP(h, hipMemcpy(n_clipped, dClip, T * sizeof(int32_t), hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -116,25 +116,13 @@ std::string at_tm(int64_t t, int m) { return " at (t, m) = (" + std::to_string(t
 // the host only validates the plants: "" or the reason, with the offending (t, m)
 std::string check_dispersion(const Dispersion& d, int64_t T, int M) {
   if (!d.plant) return "null plant array";
-  if ((d.sat_lo == nullptr) != (d.sat_hi == nullptr)) return "exactly one of sat_lo / sat_hi is NULL: give both limits or neither";
-  for (int64_t t = 0; t < T; ++t) {
-    if (d.sat_lo)
-      for (int c = 0; c < 3; ++c)
-        if (!(d.sat_lo[3 * t + c] <= d.sat_hi[3 * t + c])) return "sat_lo > sat_hi (or not a number) at t = " + std::to_string(t);
+  const std::string lim = check_limits(d.sat_lo, d.sat_hi, T);
+  if (!lim.empty()) return lim;
+  for (int64_t t = 0; t < T; ++t)
     for (int m = 0; m < M; ++m) {
-      const double* p = d.plant + ((size_t)t * M + m) * TSAT_PLANT_W;
-      double big = 0;
-      for (int i = 0; i < TSAT_PLANT_W; ++i)
-        if (!std::isfinite(p[i])) return "non-finite plant entry" + at_tm(t, m);
-      for (int i = 0; i < 9; ++i) big = std::fmax(big, std::fabs(p[i]));
-      for (int r = 0; r < 3; ++r)
-        for (int c = r + 1; c < 3; ++c)
-          if (std::fabs(p[3 * c + r] - p[3 * r + c]) > 1e-12 * big) return "Jp is not symmetric" + at_tm(t, m);
-      const double a = p[0], b = p[3], c = p[6], dd = p[4], e = p[7], f = p[8];
-      const double m2 = a * dd - b * b, m3 = a * (dd * f - e * e) + (b * (c * e - b * f) + c * (b * e - c * dd));
-      if (!(a > 0 && m2 > 0 && m3 > 0)) return "Jp is not positive definite" + at_tm(t, m);
+      const std::string bad = check_plant_record(d.plant + ((size_t)t * M + m) * TSAT_PLANT_W);
+      if (!bad.empty()) return bad + at_tm(t, m);
     }
-  }
   return "";
 }
 

@@ -6,6 +6,7 @@ current state, warm-started with the previous plan shifted by one knot, apply th
 move on. The whole loop runs on the resident batch through ``tsat_mpc_run``; only the closed-loop history comes back.
 """
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -31,3 +32,95 @@ def receding_horizon(prob, solver, n_steps, plant_integrator=4, max_outer=1, max
                           st.ctypes.data_as(C.c_void_p), C.byref(ms))
     solver._check(rc, "tsat_mpc_run")
     return dict(X_hist=Xh, U_hist=Uh, stats=st, ms=float(ms.value))
+
+
+def _noise_options(lib, noise_opts):
+    """``tsat_tvlqr_options`` of the dispersed loop: None = the defaults with a noise-free plant, a dict of field values
+    (``noise_seed`` alone switches the generated noise on), or a ready ``_abi.TvlqrOptions``."""
+    if isinstance(noise_opts, _abi.TvlqrOptions):
+        return _abi.TvlqrOptions.from_buffer_copy(noise_opts)
+    po = _abi.TvlqrOptions()
+    lib.tsat_tvlqr_default_options(C.byref(po))
+    kw = dict(noise_opts or {})
+    if "noise_seed" in kw and "noise_mode" not in kw:
+        kw["noise_mode"] = 1
+    for k, v in kw.items():
+        if k not in dict(_abi.TvlqrOptions._fields_):
+            raise ValueError(f"unknown tsat_tvlqr_options field {k!r}")
+        setattr(po, k, v)
+    return po
+
+
+def receding_horizon_dispersed(prob, solver, n_steps, plant=None, sat=None, noise_opts=None, noise_id=None, step0=0,
+                               max_outer=1, max_inner=3, upload=True):
+    """``receding_horizon`` on a noisy, dispersed plant with limits (``tsat_mpc_run_dispersed``): trajectory t flies inertia Jp,
+    actuator matrix G and residual dipole m_res of ``plant[t]`` ((T, 21), one realisation of ``tracking.disperse_plant``; None =
+    the model's plant) under ``clip(U[0], lo, hi)`` — ``sat`` = (lo, hi), each (T, 3) or (3,), units of u_scale, or None —, with
+    the plant noise the ensemble roll-out injects when ``noise_opts`` switches it on (``dict(noise_seed=...)``, any further
+    ``tsat_tvlqr_options`` fields, e.g. min_steps / w_tol / angle_tol of the statistic), generator id ``noise_id[t]`` (default t),
+    knots ``step0 + s``. The plant integrator is RK4. ``upload=False`` continues the resident simulation (give ``step0``).
+    Returns dict(X_hist (T, n_steps+1, 7), U_hist (T, n_steps, 3) the limited commands, stats (last solve), tracking_stats (T,)
+    slew-time statistic of the closed-loop history, n_clipped (T,), ms)."""
+    lib = _abi.load()
+    b = prob.arrays
+    o = solver.opts.to_abi(b.N, b.n_tab, prob.integrator, prob.terminal_mask, error_state=prob.error_state)
+    o.max_outer, o.max_inner = int(max_outer), int(max_inner)
+    po = _noise_options(lib, noise_opts)
+    T = b.T
+    c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    if plant is not None:
+        plant = c(plant)
+        if plant.shape != (T, 21):
+            raise ValueError("plant must be (T, 21)")
+    lo = hi = None
+    if sat is not None:
+        lo, hi = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in sat)
+    ids = None
+    if noise_id is not None:
+        ids = np.ascontiguousarray(noise_id, dtype=np.int64)
+        if ids.shape != (T,):
+            raise ValueError("noise_id must be (T,)")
+    if upload:
+        solver.upload(b, o.max_linesearch)
+    Xh = np.empty((T, n_steps + 1, 7)); Uh = np.empty((T, n_steps, 3))
+    st = np.zeros(T, dtype=_abi.STATS_DTYPE)
+    ts = np.zeros(T, dtype=_abi.TVLQR_STATS_DTYPE)
+    ncl = np.zeros(T, dtype=np.int32)
+    ms = C.c_float(0.0)
+    d = _abi.as_dp
+    rc = lib.tsat_mpc_run_dispersed(solver._h, C.byref(o), C.byref(po), int(n_steps), int(step0), d(plant), d(lo), d(hi),
+                                    None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int64)), d(Xh), d(Uh),
+                                    st.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p), _abi.as_ip(ncl), C.byref(ms))
+    solver._check(rc, "tsat_mpc_run_dispersed")
+    return dict(X_hist=Xh, U_hist=Uh, stats=st, tracking_stats=ts, n_clipped=ncl, ms=float(ms.value))
+
+
+_PER_SLEW = ("x0", "xf", "btab_idx", "tau0", "dtau", "dt", "Jmat", "Qd", "Qfd", "Rd", "ulo", "uhi", "U0")
+
+
+def tile_realisations(batch, M, plant=None, noise_id0=None, sat=None):
+    """M realisations per slew laid out as one batch of T M trajectories, slew-major (t M + m): the per-slew arrays repeated, the
+    field tables shared through ``btab_idx``. ``plant`` (T, M, 21) straight from ``tracking.disperse_plant``; generator ids
+    ``noise_id0[t] + m`` (default t M + m). Realisation (t, m) of ``receding_horizon_dispersed(BatchProblem.from_arrays(tiled),
+    solver, n, **kw)`` then flies the plant and draws the noise of realisation (t, m) of ``tracking.attitude_ensemble_dispersed``.
+    Returns (tiled batch, kw) with kw = dict(plant (T M, 21) or None, noise_id (T M,), sat)."""
+    T, M = batch.T, int(M)
+    if batch.Btab is None:
+        raise ValueError("the tiled batch shares host field tables through btab_idx: batch.Btab must be an array")
+    idx = np.repeat(np.arange(T), M)
+    rep = {k: np.ascontiguousarray(getattr(batch, k)[idx]) for k in _PER_SLEW}
+    if batch.n_knots is not None:
+        rep["n_knots"] = np.ascontiguousarray(np.asarray(batch.n_knots)[idx])
+    tiled = dataclasses.replace(batch, **rep)
+    if plant is not None:
+        plant = np.asarray(plant, dtype=np.float64)
+        if plant.shape != (T, M, 21):
+            raise ValueError("plant must be (T, M, 21)")
+        plant = np.ascontiguousarray(plant.reshape(T * M, 21))
+    id0 = np.arange(T, dtype=np.int64) * M if noise_id0 is None else np.asarray(noise_id0, dtype=np.int64)
+    if id0.shape != (T,):
+        raise ValueError("noise_id0 must be (T,)")
+    ids = np.ascontiguousarray((id0[:, None] + np.arange(M, dtype=np.int64)[None, :]).reshape(T * M))
+    if sat is not None:
+        sat = tuple(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))[idx]) for v in sat)
+    return tiled, dict(plant=plant, noise_id=ids, sat=sat)
