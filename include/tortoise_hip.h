@@ -404,6 +404,37 @@ int  tsat_mpc_run_dispersed(tsat_handle* h, const tsat_options* o, const tsat_tv
                             double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats, int32_t* n_clipped,
                             float* solve_ms);
 
+/* tsat_mpc_run_dispersed that RE-PLANS EVERY replan_every = R CONTROL STEPS and flies the solver's own gains in between: the
+ * controller between TVLQR tracking of one stale plan and a re-solve at every step. Arguments, plant, noise draw layout,
+ * statistic and the state left in the resident batch are those of tsat_mpc_run_dispersed; the control steps are grouped into
+ * blocks. Block b starts at step s_b = b R and has r = min(R, n_steps - s_b) steps:
+ *   1. solve the horizon from the current x0, warm start and tau0 (exactly tsat_batch_run): plan X_j, U_j and gains K_j as
+ *      tsat_batch_download returns them;
+ *   2. for j = 0 .. r-1, control step s = s_b + j: sample s + 1 (the current state x) is judged; the command is
+ *        j = 0:                 u_cmd = U_0 (no gain product is evaluated)
+ *        j > 0, feedback = 1:   u_cmd[a] = U_j[a] + sum_{i < nh} K_j[a][i] dx[i], the sum started from U_j[a], i ascending, with the
+ *                               solver's own state difference dx: x - X_j, nh = 7 (error_state = 0), or [dw; v / (1 + s)] of
+ *                               conj(q_j) (x) q, nh = 6 (error_state = 1) — the policy of the solver's forward sweep at alpha = 0
+ *        j > 0, feedback = 0:   u_cmd = U_j, the open-loop hold
+ *      clipped to sat_lo / sat_hi (counted, x to X_hist, the limited command to U_hist), then one RK4 step of the dispersed plant
+ *      with the draws of (generator id, knot step0 + s, stage). The table clock of a step is the one the every-step loop has there:
+ *      rows floor(fma(c, dtau, tau)), c = 0, 1/2, 1, clamped, then tau <- tau + dtau — one rounded addition per step, so for a
+ *      given state and command the plant step is the same function of s for every R;
+ *   3. warm start of the next solve: U0[k] = U[min(k + r, n_t - 2)] inside each trajectory's own horizon n_t; x0 and tau0 as
+ *      advanced by the r steps.
+ * The last step of the call writes `stats` and `n_clipped`; tsat_mpc_tally afterwards holds the sums over the ceil(n_steps / R)
+ * solves that ran. replan_every = 1 reproduces tsat_mpc_run_dispersed bit for bit for either value of feedback. A call always
+ * begins with a solve: a continuation (step0 = the steps already made, no new upload) equals one longer run only when the first
+ * call's n_steps is a multiple of R.
+ * Rejected with -1 (text in tsat_last_error): replan_every < 1, replan_every > min_t n_knots[t] - 1 (gains exist for n_t - 1 knots
+ * only), feedback not 0 or 1, and everything tsat_mpc_run_dispersed rejects.
+ * UNSPECIFIED: the held commands (j > 0, feedback = 1) of a trajectory whose block solve ended TSAT_REG_FAIL or TSAT_DIVERGED — its
+ * K is undefined (tsat_batch_download); reading it is harmless. */
+int  tsat_mpc_run_held(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                       int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo, const double* sat_hi,
+                       const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
+                       int32_t* n_clipped, float* solve_ms);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Sweep exchange across GPUs. The reference's Monte-Carlo is a serial loop whose iterations share nothing but the result
  * lists they append to (src/monte_carlo.jl:52-66, 199-235; src/paper_images/heatmap.jl:114-243). Here each rank — one

@@ -421,6 +421,40 @@ function receding_horizon_dispersed!(s::HIPSolver, p::BatchProblem, n_steps::Int
     return Xh, Uh, st, n_clipped
 end
 
+"""
+receding_horizon_held!(s, p, n_steps, replan_every; feedback, plant, sat_lo, sat_hi, noise_id, step0, opts) — `tsat_mpc_run_held`:
+`receding_horizon_dispersed!` that re-solves every `replan_every` control steps and in between flies the plan's controls with the
+solver's own gains around the plan (`feedback = true`) or the plan's controls alone (`feedback = false`). `replan_every = 1` is
+`receding_horizon_dispersed!`. Returns (X_hist, U_hist, stats, n_clipped) as that function.
+"""
+function receding_horizon_held!(s::HIPSolver, p::BatchProblem, n_steps::Integer, replan_every::Integer; feedback::Bool = true,
+                                plant::Matrix{Float64} = zeros(21, 0), sat_lo::Matrix{Float64} = zeros(3, 0),
+                                sat_hi::Matrix{Float64} = zeros(3, 0), noise_id::Vector{Int64} = Int64[], step0::Integer = 0,
+                                opts::TvlqrOptions = TvlqrOptions(noise_mode = 1), upload::Bool = true)
+    T = size(p.x0, 2); N = p.N
+    isempty(plant) || size(plant) == (21, T) || error("plant must be 21 x T")
+    o = s.opts; o.n_knots = N; o.n_tab = size(p.B_ECI, 2)
+    if upload
+        check(s, ccall((:tsat_batch_reserve, LIB), Cint, (Ptr{Cvoid}, Int64, Int32, Int32, Int64, Int32),
+                       s.handle, T, N, o.n_tab, size(p.B_ECI, 3), o.max_linesearch), "tsat_batch_reserve")
+        check(s, ccall((:tsat_batch_upload, LIB), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            s.handle, p.x0, p.xf, p.B_ECI, p.btab_idx, p.tau0, p.dtau, p.dt, p.J, p.Q, p.Qf, p.R, p.u_min, p.u_max, p.U0),
+            "tsat_batch_upload")
+        isempty(p.n_knots) || check(s, ccall((:tsat_batch_knots, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}), s.handle, p.n_knots), "tsat_batch_knots")
+    end
+    Xh = zeros(7, n_steps + 1, T); Uh = zeros(3, n_steps, T)
+    st = Vector{TvlqrStats}(undef, T); n_clipped = zeros(Int32, T)
+    check(s, ccall((:tsat_mpc_run_held, LIB), Cint,
+        (Ptr{Cvoid}, Ref{Options}, Ref{TvlqrOptions}, Int32, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Stats}, Ptr{TvlqrStats}, Ptr{Int32}, Ptr{Cfloat}),
+        s.handle, o, opts, n_steps, step0, replan_every, feedback ? 1 : 0, isempty(plant) ? C_NULL : plant,
+        isempty(sat_lo) ? C_NULL : sat_lo, isempty(sat_hi) ? C_NULL : sat_hi, isempty(noise_id) ? C_NULL : noise_id, Xh, Uh, C_NULL, st,
+        n_clipped, C_NULL), "tsat_mpc_run_held")
+    return Xh, Uh, st, n_clipped
+end
+
 "mpc_tally(s, T) — executed counts of the last receding_horizon! summed over its control steps: 4×T [backward, forward, dual updates, inner iterations]"
 function mpc_tally(s::HIPSolver, T::Integer)
     t = zeros(Int64, 4, T)

@@ -109,6 +109,8 @@ PROTOTYPES = {
     "tsat_mpc_tally": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "tsat_mpc_run_dispersed": (C.c_int, [C.c_void_p, C.POINTER(Options), C.POINTER(TvlqrOptions), C.c_int32, C.c_int64, _dp, _dp, _dp,
                                          C.POINTER(C.c_int64), _dp, _dp, C.c_void_p, C.c_void_p, _ip, C.POINTER(C.c_float)]),
+    "tsat_mpc_run_held": (C.c_int, [C.c_void_p, C.POINTER(Options), C.POINTER(TvlqrOptions), C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                    _dp, _dp, _dp, C.POINTER(C.c_int64), _dp, _dp, C.c_void_p, C.c_void_p, _ip, C.POINTER(C.c_float)]),
     "tsat_comm_unique_id": (C.c_int, [C.c_void_p]),
     "tsat_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "tsat_sweep_allgather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),

@@ -268,6 +268,15 @@ inline std::string check_mpc_dispersed(const tsat_tvlqr_options& po, int32_t n_s
   return "";
 }
 
+// what tsat_mpc_run_held rejects beyond tsat_mpc_run_dispersed's checks: "" or the reason. min_nk: the shortest horizon of the batch
+inline std::string check_mpc_held(int32_t replan_every, int32_t feedback, int min_nk) {
+  if (replan_every < 1) return "replan_every must be >= 1";
+  if (replan_every > min_nk - 1)
+    return "replan_every must be <= min n_knots - 1 = " + std::to_string(min_nk - 1) + ": a plan has gains for n_knots - 1 knots only";
+  if (feedback != 0 && feedback != 1) return "feedback must be 0 (hold the plan's controls) or 1 (the plan's controls + K dx)";
+  return "";
+}
+
 // scales of the three draws of `simulator` (src/simulator.jl:5,10,22)
 inline void tv_noise_defaults(tsat_tvlqr_options& o) {
   const double deg = 3.14159265358979323846 / 180.0;

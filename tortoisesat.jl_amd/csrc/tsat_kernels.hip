@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 #include "tsat_host_pack.hpp"
-#include "tsat_mpc_dispersed.hpp"
+#include "tsat_mpc_held.hpp"
 
 using namespace tsat;
 
@@ -38,6 +38,9 @@ hipError_t tsat_launch_solve_packed_mixed4w(const KArgs<double>& a, int rk4, int
 
 // the plant step of tsat_mpc_run_dispersed (tsat_kernels_mpc_dispersed.hip); step 0 also packs the call's plant records
 hipError_t tsat_launch_mpc_dispersed(const MpcDispArgs<double>& a, const double* plant, hipStream_t stream);
+// the pack, and hold + plan shift after every solve, of tsat_mpc_run_held (tsat_kernels_mpc_held.hip)
+hipError_t tsat_launch_mpc_held_pack(const MpcHeldArgs<double>& a, const double* plant, hipStream_t stream);
+hipError_t tsat_launch_mpc_held(const MpcHeldArgs<double>& a, int error_state, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -591,32 +594,46 @@ int tsat_mpc_tally(tsat_handle* h, int64_t* tally) {
   return 0;
 }
 
-int tsat_mpc_run_dispersed(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
-                           const double* plant, const double* sat_lo, const double* sat_hi, const int64_t* noise_id,
-                           double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats, int32_t* n_clipped,
-                           float* solve_ms) {
+namespace {
+// the loop of tsat_mpc_run_dispersed (replan_every = 0: a solve and the one-wavefront-per-trajectory step kernel per control step)
+// and of tsat_mpc_run_held (replan_every >= 1: a solve, the lane-per-trajectory hold and the plan shift per block)
+int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps,
+                   int64_t step0, int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo,
+                   const double* sat_hi, const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last,
+                   tsat_tvlqr_stats* stats, int32_t* n_clipped, float* solve_ms) {
   if (!h || !o || !po) return -1;
+  const bool held = replan_every != 0;
   if (!h->uploaded) return fail(h, -1, "tsat_batch_upload has not been called");
   const std::string why = check_options(*o, h->N, h->n_tab, h->max_ls);
   if (!why.empty()) return fail(h, -1, why);
-  if (o->precision != 64) return fail(h, -1, "tsat_mpc_run_dispersed runs the fp64 build only (precision must be 64)");
+  if (o->precision != 64) return fail(h, -1, std::string(name) + " runs the fp64 build only (precision must be 64)");
   const std::string bad = check_mpc_dispersed(*po, n_steps, step0, plant, sat_lo, sat_hi, h->T);
   if (!bad.empty()) return fail(h, -1, bad);
   if (!X_hist || !U_hist) return fail(h, -1, "null array");
   TSAT_HIP(h, hipSetDevice(h->dev));
+  if (held) {
+    int min_nk = h->N;
+    if (h->ragged) {
+      std::vector<int> nk((size_t)h->T);
+      TSAT_HIP(h, hipMemcpy(nk.data(), h->nk, nk.size() * sizeof(int), hipMemcpyDeviceToHost));
+      min_nk = *std::min_element(nk.begin(), nk.end());
+    }
+    const std::string hold = check_mpc_held(replan_every, feedback, min_nk);
+    if (!hold.empty()) return fail(h, -1, hold);
+  }
   const size_t T = (size_t)h->T, nX = T * ((size_t)n_steps + 1) * 7, nU = T * (size_t)n_steps * 3;
   double* dHX = (double*)ws_get(h, tsat_handle::WS_MPC_HX, nX * 8);
   double* dHU = (double*)ws_get(h, tsat_handle::WS_MPC_HU, nU * 8);
   long long* dTally = (long long*)ws_get(h, tsat_handle::WS_MPC_TALLY, T * 4 * sizeof(long long));
   double* dPlant = plant ? (double*)ws_get(h, tsat_handle::WS_MPCD_PLANT, T * TSAT_PLANT_W * 8) : nullptr;
-  double* dPL = (double*)ws_get(h, tsat_handle::WS_MPCD_PL, T * PLW * 8);
+  double* dPL = (double*)ws_get(h, tsat_handle::WS_MPCD_PL, T * (held ? HELD_W : PLW) * 8);
   double* dSat = (double*)ws_get(h, tsat_handle::WS_MPCD_SAT, T * SATW * 8);
   long long* dNid = noise_id ? (long long*)ws_get(h, tsat_handle::WS_MPCD_NID, T * sizeof(long long)) : nullptr;
   MpcDispRec* dRec = (MpcDispRec*)ws_get(h, tsat_handle::WS_MPCD_REC, T * sizeof(MpcDispRec));
   tsat_tvlqr_stats* dSt = (tsat_tvlqr_stats*)ws_get(h, tsat_handle::WS_MPCD_ST, T * sizeof(tsat_tvlqr_stats));
   int* dClip = (int*)ws_get(h, tsat_handle::WS_MPCD_CLIP, T * sizeof(int));
   if (!dHX || !dHU || !dTally || (plant && !dPlant) || !dPL || !dSat || (noise_id && !dNid) || !dRec || !dSt || !dClip)
-    return fail(h, -10, "device allocation failed in tsat_mpc_run_dispersed");
+    return fail(h, -10, std::string("device allocation failed in ") + name);
   std::vector<double> sat(T * SATW);               // a NULL limit is +-inf: the step has one code path
   for (size_t t = 0; t < T; ++t)
     for (int c = 0; c < 3; ++c) {
@@ -631,7 +648,8 @@ int tsat_mpc_run_dispersed(tsat_handle* h, const tsat_options* o, const tsat_tvl
   const KArgs<double> a = solve_args(h, o);
   if (!a.JW && uses_packed_build(h, 64))     // a packed kernel launched with JW = nullptr would fault on the device
     return fail(h, -10, "device allocation of the packed builds' Jacobian workspace failed");
-  MpcDispArgs<double> md = {};
+  MpcHeldArgs<double> mh = {};
+  MpcDispArgs<double>& md = mh.s;
   MpcArgs<double>& m = md.m;
   m.T = (int)h->T; m.N = h->N; m.n_tab = h->n_tab; m.plant_integ = 4; m.n_steps = n_steps; m.us = o->u_scale;
   m.P = h->P; m.BT = h->BT; m.bidx = h->bidx; m.nk = h->ragged ? h->nk : nullptr; m.XU = h->XU; m.U0 = h->U0;
@@ -642,18 +660,47 @@ int tsat_mpc_run_dispersed(tsat_handle* h, const tsat_options* o, const tsat_tvl
   e.k0 = (unsigned)(po->noise_seed & 0xFFFFFFFFull); e.k1 = (unsigned)(po->noise_seed >> 32);
   e.nid0 = dNid; e.sg = po->sigma_gyro; e.sa = po->sigma_att; e.fa = po->field_amp; e.stats = dSt;
   md.noisy = po->noise_mode; md.step0 = (long long)step0; md.rec = dRec;
+  mh.KD = h->KD; mh.feedback = feedback;
   int rc = 0;
   if (hipEventRecord(h->ev0, h->stream) != hipSuccess) rc = -10;
-  for (int s = 0; s < n_steps && !rc; ++s) {   // 2 n_steps launches (+ the pack) queued back to back; the stream orders them
-    if (launch_solve(h, o, a) != hipSuccess) rc = -10;
-    m.step = s;
-    if (!rc && tsat_launch_mpc_dispersed(md, dPlant, h->stream) != hipSuccess) rc = -10;
+  if (held) {   // the pack, then solve, hold and shift per block queued back to back; the stream orders them
+    if (tsat_launch_mpc_held_pack(mh, dPlant, h->stream) != hipSuccess) rc = -10;
+    for (int s = 0; s < n_steps && !rc; s += replan_every) {
+      if (launch_solve(h, o, a) != hipSuccess) rc = -10;
+      m.step = s;
+      mh.r = std::min<int>(replan_every, n_steps - s);
+      if (!rc && tsat_launch_mpc_held(mh, o->error_state, h->stream) != hipSuccess) rc = -10;
+    }
+  } else {
+    for (int s = 0; s < n_steps && !rc; ++s) {   // 2 n_steps launches (+ the pack) queued back to back; the stream orders them
+      if (launch_solve(h, o, a) != hipSuccess) rc = -10;
+      m.step = s;
+      if (!rc && tsat_launch_mpc_dispersed(md, dPlant, h->stream) != hipSuccess) rc = -10;
+    }
   }
-  rc = mpc_collect(h, rc, "tsat_mpc_run_dispersed", dHX, dHU, nX, nU, X_hist, U_hist, stats_last, solve_ms);
+  rc = mpc_collect(h, rc, name, dHX, dHU, nX, nU, X_hist, U_hist, stats_last, solve_ms);
   if (rc) return rc;
   if (stats) TSAT_HIP(h, hipMemcpy(stats, dSt, T * sizeof(tsat_tvlqr_stats), hipMemcpyDeviceToHost));
   if (n_clipped) TSAT_HIP(h, hipMemcpy(n_clipped, dClip, T * sizeof(int32_t), hipMemcpyDeviceToHost));
   return 0;
+}
+}  // namespace
+
+int tsat_mpc_run_dispersed(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                           const double* plant, const double* sat_lo, const double* sat_hi, const int64_t* noise_id,
+                           double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats, int32_t* n_clipped,
+                           float* solve_ms) {
+  return mpc_plant_loop(h, "tsat_mpc_run_dispersed", o, po, n_steps, step0, 0, 0, plant, sat_lo, sat_hi, noise_id, X_hist, U_hist,
+                        stats_last, stats, n_clipped, solve_ms);
+}
+
+int tsat_mpc_run_held(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                      int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo, const double* sat_hi,
+                      const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
+                      int32_t* n_clipped, float* solve_ms) {
+  if (replan_every < 1) return fail(h, -1, check_mpc_held(replan_every, feedback, 2));
+  return mpc_plant_loop(h, "tsat_mpc_run_held", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id, X_hist,
+                        U_hist, stats_last, stats, n_clipped, solve_ms);
 }
 
 int tsat_batch_export_device(tsat_handle* h, void* X_dev, void* U_dev, void* K_dev, void* stats_dev) {

@@ -51,16 +51,8 @@ def _noise_options(lib, noise_opts):
     return po
 
 
-def receding_horizon_dispersed(prob, solver, n_steps, plant=None, sat=None, noise_opts=None, noise_id=None, step0=0,
-                               max_outer=1, max_inner=3, upload=True):
-    """``receding_horizon`` on a noisy, dispersed plant with limits (``tsat_mpc_run_dispersed``): trajectory t flies inertia Jp,
-    actuator matrix G and residual dipole m_res of ``plant[t]`` ((T, 21), one realisation of ``tracking.disperse_plant``; None =
-    the model's plant) under ``clip(U[0], lo, hi)`` — ``sat`` = (lo, hi), each (T, 3) or (3,), units of u_scale, or None —, with
-    the plant noise the ensemble roll-out injects when ``noise_opts`` switches it on (``dict(noise_seed=...)``, any further
-    ``tsat_tvlqr_options`` fields, e.g. min_steps / w_tol / angle_tol of the statistic), generator id ``noise_id[t]`` (default t),
-    knots ``step0 + s``. The plant integrator is RK4. ``upload=False`` continues the resident simulation (give ``step0``).
-    Returns dict(X_hist (T, n_steps+1, 7), U_hist (T, n_steps, 3) the limited commands, stats (last solve), tracking_stats (T,)
-    slew-time statistic of the closed-loop history, n_clipped (T,), ms)."""
+def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload):
+    """``tsat_mpc_run_dispersed`` (``replan_every`` None) or ``tsat_mpc_run_held`` on ``prob``: marshalling of both"""
     lib = _abi.load()
     b = prob.arrays
     o = solver.opts.to_abi(b.N, b.n_tab, prob.integrator, prob.terminal_mask, error_state=prob.error_state)
@@ -88,11 +80,41 @@ def receding_horizon_dispersed(prob, solver, n_steps, plant=None, sat=None, nois
     ncl = np.zeros(T, dtype=np.int32)
     ms = C.c_float(0.0)
     d = _abi.as_dp
-    rc = lib.tsat_mpc_run_dispersed(solver._h, C.byref(o), C.byref(po), int(n_steps), int(step0), d(plant), d(lo), d(hi),
-                                    None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int64)), d(Xh), d(Uh),
-                                    st.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p), _abi.as_ip(ncl), C.byref(ms))
-    solver._check(rc, "tsat_mpc_run_dispersed")
+    head = (solver._h, C.byref(o), C.byref(po), int(n_steps), int(step0))
+    tail = (d(plant), d(lo), d(hi), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int64)), d(Xh), d(Uh),
+            st.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p), _abi.as_ip(ncl), C.byref(ms))
+    if replan_every is None:
+        solver._check(lib.tsat_mpc_run_dispersed(*head, *tail), "tsat_mpc_run_dispersed")
+    else:
+        solver._check(lib.tsat_mpc_run_held(*head, int(replan_every), int(feedback), *tail), "tsat_mpc_run_held")
     return dict(X_hist=Xh, U_hist=Uh, stats=st, tracking_stats=ts, n_clipped=ncl, ms=float(ms.value))
+
+
+def receding_horizon_dispersed(prob, solver, n_steps, plant=None, sat=None, noise_opts=None, noise_id=None, step0=0,
+                               max_outer=1, max_inner=3, upload=True):
+    """``receding_horizon`` on a noisy, dispersed plant with limits (``tsat_mpc_run_dispersed``): trajectory t flies inertia Jp,
+    actuator matrix G and residual dipole m_res of ``plant[t]`` ((T, 21), one realisation of ``tracking.disperse_plant``; None =
+    the model's plant) under ``clip(U[0], lo, hi)`` — ``sat`` = (lo, hi), each (T, 3) or (3,), units of u_scale, or None —, with
+    the plant noise the ensemble roll-out injects when ``noise_opts`` switches it on (``dict(noise_seed=...)``, any further
+    ``tsat_tvlqr_options`` fields, e.g. min_steps / w_tol / angle_tol of the statistic), generator id ``noise_id[t]`` (default t),
+    knots ``step0 + s``. The plant integrator is RK4. ``upload=False`` continues the resident simulation (give ``step0``).
+    Returns dict(X_hist (T, n_steps+1, 7), U_hist (T, n_steps, 3) the limited commands, stats (last solve), tracking_stats (T,)
+    slew-time statistic of the closed-loop history, n_clipped (T,), ms)."""
+    return _plant_loop(prob, solver, n_steps, None, 0, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload)
+
+
+def receding_horizon_held(prob, solver, n_steps, replan_every, feedback=True, plant=None, sat=None, noise_opts=None, noise_id=None,
+                          step0=0, max_outer=1, max_inner=3, upload=True):
+    """``receding_horizon_dispersed`` that re-solves every ``replan_every`` control steps only (``tsat_mpc_run_held``): in between,
+    step j > 0 of a block flies the plan's control U[j] plus the solver's own gains on the state difference to the plan
+    (``feedback=True``; the policy of the solver's forward sweep) or U[j] alone (``feedback=False``, the open-loop hold). Same plant,
+    limits, noise draws and statistic; ``replan_every=1`` is ``receding_horizon_dispersed`` bit for bit. ``replan_every`` is at most
+    the shortest horizon - 1. A continuation (``upload=False``, ``step0``) begins with a solve: it equals one longer run only when
+    the first call's ``n_steps`` is a multiple of ``replan_every``. Returns the dict of ``receding_horizon_dispersed`` plus
+    ``n_solves`` = ceil(n_steps / replan_every)."""
+    r = _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload)
+    r["n_solves"] = -(-int(n_steps) // int(replan_every))
+    return r
 
 
 _PER_SLEW = ("x0", "xf", "btab_idx", "tau0", "dtau", "dt", "Jmat", "Qd", "Qfd", "Rd", "ulo", "uhi", "U0")
