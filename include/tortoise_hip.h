@@ -90,7 +90,10 @@ typedef struct tsat_stats {
   int32_t ls_trials;    /* line-search candidates a sequential backtracking search would
                            have rolled out (index of accepted alpha + 1, summed)          */
   int32_t n_backward;   /* backward sweeps executed (incl. regularisation restarts)       */
-  int32_t n_forward;    /* forward sweeps executed on this backend                        */
+  int32_t n_forward;    /* forward sweeps executed on this backend: 1 + one per line search,
+                           + one for each search whose winner the sweep had not kept
+                           (tsat_set_store_policy; none below 2048 trajectories when the
+                           searches that follow a deep one are deep too)                  */
   int32_t bp_restarts;  /* backward sweeps abandoned on a non-PD Quu                      */
   int32_t fp_fails;     /* line searches in which no alpha was accepted                   */
   double  cost;         /* LQR objective of the returned trajectory (no AL terms)         */
@@ -276,6 +279,20 @@ int  tsat_set_kernel_variant(tsat_handle* h, int32_t variant);
  * Results do not depend on it (X, U, K, costs, iteration counts: bit-identical); `n_forward`, the sweeps that were executed,
  * does. For tuning and for the tests. */
 int  tsat_set_endgame(tsat_handle* h, int32_t suspend_at);
+
+/* Keep rule of the one-trajectory builds (variants 1 and 2, and the continuation of a packed launch's last trajectories). One
+ * forward sweep rolls out every candidate of a line search at once; how many of the roll-outs it keeps in HBM (80 B per knot
+ * each) decides whether the accepted one is at hand or takes another sweep — half an iteration, on the trajectory the whole
+ * launch may be waiting for. A sweep keeps
+ *   `few` roll-outs                while the trajectory's line searches end early (default 4), and
+ *   every reserved slot            in the iteration after a search that accepted index >= few - 1 or none at all, and in the
+ *                                  `hold` iterations after that one (default 8; 0: that iteration only; negative: in every
+ *                                  iteration that follows, to the end of the solve).
+ * few >= max_linesearch keeps every roll-out always. Batches of fewer than 2048 trajectories reserve a slot for each of the
+ * max_linesearch candidates (tsat_batch_reserve), larger ones 12 at most: there a deeper search still takes a further sweep.
+ * Results do not depend on the rule (X, U, K, costs, iteration counts: bit-identical); `n_forward`, the sweeps that were
+ * executed, does. For tuning and for the tests. */
+int  tsat_set_store_policy(tsat_handle* h, int32_t few, int32_t hold);
 
 /* What the next tsat_batch_run / tsat_mpc_run with options `o` will launch on the reserved batch: *build = 1 wide, 2 dense,
  * 3 packed, 4 packed8, 5 packed8w, 6 packed16w, 7 packed4w (of the precision `o` names), *endgame_at = the live count at which a packed launch parks its trajectories

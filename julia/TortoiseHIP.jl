@@ -84,6 +84,10 @@ set_kernel_variant!(s::HIPSolver, v::Integer) =
 set_endgame!(s::HIPSolver, n::Integer) =
     check(s, ccall((:tsat_set_endgame, LIB), Cint, (Ptr{Cvoid}, Int32), s.handle, n), "tsat_set_endgame")
 
+"set_store_policy!(s, few, hold) — one-trajectory builds: roll-outs kept per sweep, and iterations all are kept after a deep search"
+set_store_policy!(s::HIPSolver, few::Integer, hold::Integer) =
+    check(s, ccall((:tsat_set_store_policy, LIB), Cint, (Ptr{Cvoid}, Int32, Int32), s.handle, few, hold), "tsat_set_store_policy")
+
 "selected_build(s, o) — (build, endgame_at) the next run launches on the reserved batch: 1 wide, 2 dense, 3 packed, 4 packed8, 5 packed8w, 6 packed16w, 7 packed4w"
 function selected_build(s::HIPSolver, o::Options)
     b = Ref{Int32}(0); e = Ref{Int32}(0)

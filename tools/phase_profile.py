@@ -31,6 +31,9 @@ o = opts.to_abi(b.N, b.n_tab, 3, error_state=es)
 o.precision = prec
 solver.set_kernel_variant(variant)
 solver.set_endgame(0)     # one kernel: the stamps of a wavefront cover its trajectories from start to end
+if len(sys.argv) > 7:     # keep rule of the one-trajectory builds' line search (tsat_set_store_policy): few, hold
+    solver.set_store_policy(int(sys.argv[6]), int(sys.argv[7]))
+    print(f"store policy: few = {sys.argv[6]}, hold = {sys.argv[7]}")
 solver.upload(b, o.max_linesearch); solver.trace(1)
 ms = solver.run(o); ms = solver.run(o)
 tr = solver.trace_download()[:, 0, :]
@@ -52,5 +55,19 @@ if variant >= 3 or (variant == 0 and T >= 3072):   # a sweep serves the whole wa
     sw = nfw.reshape(-1, G).max(1)
     print(f"  forward sweep, per executed sweep of a wavefront and knot: {np.mean(tr[:, 0] / np.maximum(sw, 1)) / N:7.1f} cycles ({sw.mean():.1f} sweeps per wavefront)")
 print(f"  slowest wave: {tot.max()/1e6:.1f} Mcycles, {int(it[np.argmax(tot)])} iterations (the launch ends with it); mean wave {tot.mean()/1e6:.1f}")
+if not (variant >= 3 or (variant == 0 and T >= 2048)):
+    # The launch ends with its slowest wavefront: what the slowest ten did. A line search takes one forward sweep, and one more
+    # whenever the sweep had not kept the roll-out that is accepted (repeated = executed - 1 - iterations); its candidates' costs
+    # are evaluated CG at a time, one `cost pass` each (columns 6 and 7 of the stamp row: passes, cycles in them).
+    npass, cpass = tr[:, 6], tr[:, 7]
+    print(f"  cost passes: {npass.mean():.1f} per wave, {cpass.sum() / max(npass.sum(), 1) / 1e3:.1f} kcycles each, "
+          f"{100 * cpass.sum() / tot.sum():.2f} % of the stamped cycles (inside `parallel passes`)")
+    print(f"  executed forward sweeps: {nfw.mean():.2f} per wave, repeated {np.mean(nfw - 1 - it):.3f} (max {int(np.max(nfw - 1 - it))})")
+    print("  the ten slowest waves:")
+    print("    traj   Mcycles  iterations  sweeps  repeated  cost passes (Mcycles, %)     forward  jacobian   riccati  parallel")
+    for t in np.argsort(-tot)[:10]:
+        print(f"    {t:4d}  {tot[t]/1e6:8.1f}  {int(it[t]):10d}  {int(nfw[t]):6d}  {int(nfw[t] - 1 - it[t]):8d}  {int(npass[t]):11d} ({cpass[t]/1e6:5.2f}, {100*cpass[t]/tot[t]:4.1f})"
+              f"  {tr[t, 0]/1e6:10.1f}  {tr[t, 1]/1e6:8.1f}  {tr[t, 2]/1e6:8.1f}  {tr[t, 3]/1e6:8.1f}")
+    print(f"  percentiles of a wave's Mcycles: p50 {np.percentile(tot, 50)/1e6:.1f}, p90 {np.percentile(tot, 90)/1e6:.1f}, p99 {np.percentile(tot, 99)/1e6:.1f}, max {tot.max()/1e6:.1f}")
 print(f"  sum of stamped phases {tot.mean()/1e6:.1f} Mcycles/wave = {tot.mean()/ (ms*1e-3)/1e9:.2f} GHz-equivalent of the kernel time")
 solver.close()

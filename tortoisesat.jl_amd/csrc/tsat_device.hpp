@@ -138,12 +138,17 @@ constexpr int CK = 16;    // knots per forward-sweep LDS chunk
 constexpr int CK = 32;
 #endif
 constexpr int PSTRIDE = 64;
-// line-search candidates whose rollouts are kept in HBM. A deeper winner is re-rolled on its own (a second sweep)
-// instead of every sweep streaming all max_linesearch candidate trajectories to memory. The launch ends with its
-// slowest wavefront, so re-rolls must stay rare: on the reference Monte-Carlo workload the accepted step is
-// alpha = 2^-j with j <= 5 in 99.8 % and j <= 11 in 99.96 % of the iterations.
+// Line-search candidates whose rollouts are kept in HBM: the candidate slabs a batch reserves per trajectory (tsat_batch_reserve).
+// Batches small enough for a one-trajectory build (fewer than 2048 trajectories) reserve one slab for EVERY candidate, so that no
+// line search, however deep, rolls anything out twice: the launch ends with its slowest wavefront, and a repeated sweep is half
+// an iteration of pure waiting for the rest of the machine. Larger batches (the packed builds keep PK_STORE roll-outs at most)
+// reserve NSTORE at most; there a deeper winner is re-rolled on its own (a second sweep).
 constexpr int NSTORE = 12;
-constexpr int N_FEW = 4;    // roll-outs a sweep keeps while the trajectory's line searches end early (solve_trajectory)
+// Keep rule of solve_trajectory (tsat_set_store_policy): a sweep keeps N_FEW roll-outs while the trajectory's line searches end
+// early, and every slot for the iteration after a deep search (accepted index >= N_FEW - 1, or none accepted) and LS_HOLD more.
+constexpr int N_FEW = 4;
+constexpr int LS_HOLD = 8;
+constexpr int LS_SHALLOW = 1 << 30;   // Resume::since_deep / the counter of solve_trajectory: no deep search so far
 // per-trajectory parameter record (reals)
 enum { P_X0 = 0, P_XF = 7, P_QD = 14, P_QFD = 21, P_RD = 28, P_ULO = 31, P_UHI = 34, P_J = 37, P_JI = 46,
        P_TAU0 = 55, P_DTAU = 56, P_DT = 57,
@@ -207,7 +212,7 @@ template <typename real> constexpr size_t u0_stride(int NS) { return (size_t)(NS
 
 template <typename real>
 struct KArgs {
-  int T, N, n_tab, max_ls;   // max_ls: candidate slots reserved per trajectory (<= NSTORE)
+  int T, N, n_tab, max_ls;   // max_ls: candidate slots reserved per trajectory (any number >= 1; tsat_batch_reserve)
   tsat_options opt;
   const real* P;      // [T][PSTRIDE]
   const real* BT;     // [n_btab][n_tab][4]
@@ -226,6 +231,9 @@ struct KArgs {
   // iterating, every wavefront parks its live ones — id and Resume record appended to the lists below — and leaves; a second
   // launch gives each parked trajectory a wavefront of its own in the one-trajectory mapping (tsat_resume_kernel_*).
   int pk_few = 0;               // packed builds: roll-outs kept per sweep while line searches end early (0: PK_FEW; tuning)
+  // one-trajectory builds: roll-outs kept per sweep while line searches end early, and for how many further iterations after a
+  // deep search every slot is kept (negative: for the rest of the solve) — tsat_set_store_policy
+  int ls_few = N_FEW, ls_hold = LS_HOLD;
   int suspend_at = 0;           // 0: never
   int* live = nullptr;          // [1] trajectories that have not finished (set to T before the launch)
   int* susp_n = nullptr;        // [1] parked so far
@@ -1933,7 +1941,8 @@ struct Resume {
   acc_t Jprev;
   real mu, rho, drho, grad, nu[7];
   int outer, it, djz, inner_iters, ls_trials, n_backward, n_forward, bp_restarts, fp_fails, trow;
-  int cur, pad;     // slab that holds the nominal trajectory (cand_slab numbering; both mappings use the launch's a.max_ls slots)
+  int cur;          // slab that holds the nominal trajectory (cand_slab numbering; both mappings use the launch's a.max_ls slots)
+  int since_deep;   // iterations since the last deep or failed line search (LS_SHALLOW: none so far): the keep rule's memory
 };
 
 template <typename real, int INTEG, int DIAGJ, int ES>
@@ -1965,14 +1974,17 @@ TSAT_DEV int solve_trajectory(const KArgs<real>& a, int traj, const Resume<real>
   int status = TSAT_MAX_OUTER, outer_iters = 0, inner_iters = 0, ls_trials = 0, n_backward = 0, n_forward = 0,
       bp_restarts = 0, fp_fails = 0;
   real grad = 0;
-  int last_jw = 0;                  // accepted line-search index of the previous iteration (first iteration: a shallow search is assumed)
-  unsigned long long pc_fwd = 0, pc_par = 0;
+  int since_deep = LS_SHALLOW;      // iterations since the last deep or failed line search (first iteration: shallow searches are assumed)
+  const int ls_few = (a.ls_few >= 1) ? a.ls_few : N_FEW;
+  unsigned long long pc_fwd = 0, pc_par = 0, pc_cost = 0;
+  int n_cost = 0;                   // candidate_costs passes of the line searches (diagnostic build)
   bool start_ok = true;
 
   if (rs) {
     // carry on: the nominal trajectory, gains' inputs and multipliers are in HBM; counters and terminal multipliers come along
     trow = rs->trow; mu = rs->mu; grad = rs->grad;
     p.cur = rs->cur; p.XU = slab_ptr<real>(p, N, p.cur);
+    since_deep = rs->since_deep;
     inner_iters = rs->inner_iters; ls_trials = rs->ls_trials; n_backward = rs->n_backward; n_forward = rs->n_forward;
     bp_restarts = rs->bp_restarts; fp_fails = rs->fp_fails;
     if (lane < 7) lds[L_NU + lane] = rs->nu[lane];
@@ -2032,7 +2044,7 @@ TSAT_DEV int solve_trajectory(const KArgs<real>& a, int traj, const Resume<real>
               for (int i = 0; i < 7; ++i) r.nu[i] = lds[L_NU + i];
               r.outer = outer; r.it = it; r.djz = djz; r.inner_iters = inner_iters; r.ls_trials = ls_trials;
               r.n_backward = n_backward; r.n_forward = n_forward; r.bp_restarts = bp_restarts; r.fp_fails = fp_fails; r.trow = trow;
-              r.cur = p.cur; r.pad = 0;
+              r.cur = p.cur; r.since_deep = since_deep;
             }
             TSAT_SYNC();
             return 1;
@@ -2065,14 +2077,17 @@ TSAT_DEV int solve_trajectory(const KArgs<real>& a, int traj, const Resume<real>
         // ones (max_linesearch > n_store) take another sweep with the next n_store.
         const unsigned long long t_f0 = tick_();
         // How many roll-outs a sweep keeps costs nothing in time (the stores are never waited on) but is most of the launch's HBM
-        // writes, so a trajectory whose last accepted step was among the first few keeps only N_FEW at first and takes the rest in
-        // a further sweep if it has to; one that has been searching deep keeps all the slots at once. The accepted candidate — and
-        // with it every result — is the same either way.
+        // writes, so a trajectory whose accepted steps have been among the first few keeps only ls_few at first and takes the rest
+        // in a further sweep if it has to. Deep searches come in runs, and a further sweep is half an iteration the whole launch
+        // may end up waiting for: after a deep or failed search the sweeps of the next 1 + ls_hold iterations keep all the slots
+        // at once (ls_hold < 0: of every iteration that follows). The accepted candidate — and with it every result — is the
+        // same either way.
         const int n_slots = (o.max_linesearch < a.max_ls) ? o.max_linesearch : a.max_ls;
         int jw = WAVE, slot = 0;
         acc_t Jw = 0;
         unsigned long long t_cost = 0;
-        int n_store = (last_jw >= N_FEW - 1 || n_slots < N_FEW) ? n_slots : N_FEW;
+        const bool keep_all = (a.ls_hold < 0) ? since_deep < LS_SHALLOW : since_deep <= a.ls_hold;
+        int n_store = (keep_all || n_slots < ls_few) ? n_slots : ls_few;
         for (int shift = 0; shift < o.max_linesearch && jw == WAVE; shift += n_store, n_store = n_slots) {
           const int n_here = (o.max_linesearch - shift < n_store) ? o.max_linesearch - shift : n_store;
           forward_sweep<real, INTEG, DIAGJ, ES>(p, N, n_tab, 1, n_here, shift);
@@ -2082,6 +2097,7 @@ TSAT_DEV int solve_trajectory(const KArgs<real>& a, int traj, const Resume<real>
           for (int c0 = 0; c0 < n_here && jw == WAVE; c0 += CG) {
             const int nc = (n_here - c0 < CG) ? n_here - c0 : CG;
             const FwdOut<real> fw = candidate_costs<real>(p, N, c0, nc, mu, tmask, max_state);
+            n_cost++;
             const int ci = shift + c0 + lane;            // this lane's candidate (lanes < nc)
             acc_t alpha = 1;
             for (int j = 0; j < ci && j < TSAT_MAX_LINESEARCH; ++j) alpha *= (acc_t)0.5;
@@ -2101,9 +2117,11 @@ TSAT_DEV int solve_trajectory(const KArgs<real>& a, int traj, const Resume<real>
         const unsigned long long t_f1 = tick_();
         pc_fwd += (t_f1 - t_f0) - t_cost;
         pc_par += t_cost;
+        pc_cost += t_cost;
         acc_t J;
         TSAT_SYNC();
-        last_jw = (jw < WAVE) ? jw : o.max_linesearch;
+        if (jw >= ls_few - 1) since_deep = 0;            // (jw == WAVE: no candidate accepted)
+        else if (since_deep < LS_SHALLOW) since_deep++;
         if (jw < WAVE) {
           J = Jw;
           ls_trials += jw + 1;
@@ -2173,9 +2191,12 @@ TSAT_DEV int solve_trajectory(const KArgs<real>& a, int traj, const Resume<real>
     if (trace && a.trace_rows > 0) {  // diagnostic build only: row 0 carries the phase clocks instead of iteration 1
       trace[0] = (double)pc_fwd; trace[1] = (double)lds[L_PC + 1]; trace[2] = (double)lds[L_PC + 2];
       trace[3] = (double)pc_par; trace[4] = (double)inner_iters; trace[5] = (double)n_backward;
+#ifndef TSAT_PACKED      // (the packed builds stamp columns 6 and 7 themselves)
+      trace[6] = (double)n_cost; trace[7] = (double)pc_cost;      // cost passes of the line searches, and the cycles in them
+#endif
     }
 #else
-    (void)pc_fwd; (void)pc_par;
+    (void)pc_fwd; (void)pc_par; (void)pc_cost; (void)n_cost;
 #endif
   }
   return 0;

@@ -94,6 +94,20 @@ inline std::string check_options(const tsat_options& o, int N, int n_tab, int ma
   return "";
 }
 
+// Candidate slabs a batch reserves per trajectory. The automatic choice gives batches of fewer than TSAT_PACKED_MIN_T trajectories
+// to a one-trajectory build: they get a slab for every candidate of the line search, so that solve_trajectory never has to repeat
+// a sweep. The batches of the packed builds, which keep PK_STORE roll-outs at most, stay at NSTORE: 65536 x 1000 must not grow.
+constexpr int64_t TSAT_PACKED_MIN_T = 2048;
+inline int reserved_slots(int64_t T, int max_linesearch) {
+  return (T < TSAT_PACKED_MIN_T || max_linesearch < NSTORE) ? max_linesearch : NSTORE;
+}
+
+// validate the keep rule of tsat_set_store_policy; returns "" or an error text (any `hold` has a meaning)
+inline std::string check_store_policy(int few) {
+  if (few < 1) return "few must be >= 1 (roll-outs a sweep keeps while the line searches end early)";
+  return "";
+}
+
 // pack per-trajectory parameters into [T][PSTRIDE] records
 template <typename real>
 void pack_params(int64_t T, const double* x0, const double* xf, const double* tau0, const double* dtau,

@@ -108,6 +108,8 @@ struct tsat_handle {
   // reserved batch
   int64_t T = 0, n_btab = 0;
   int N = 0, n_tab = 0, max_ls = 0, trace_rows = 0;
+  int slots = 0;              // candidate slabs reserved per trajectory (tsat_batch_reserve): what every launch gets as a.max_ls
+  int store_few = N_FEW, store_hold = LS_HOLD;     // keep rule of the one-trajectory builds (tsat_set_store_policy)
   bool uploaded = false, solved = false;
   int inertia_class = 0;      // 0 full, 1 every uploaded inertia tensor diagonal, 2 every one isotropic -> DIAGJ variant
   double *P = nullptr, *BT = nullptr, *U0 = nullptr, *XU = nullptr, *KD = nullptr, *LAM = nullptr, *CAND = nullptr;
@@ -289,12 +291,15 @@ int tsat_batch_reserve(tsat_handle* h, int64_t T, int32_t n_knots, int32_t n_tab
   rc |= dev_alloc(h, &h->XU, Tn * N * XUW);
   rc |= dev_alloc(h, &h->KD, Tn * (N - 1) * KDW);
   rc |= dev_alloc(h, &h->LAM, Tn * (N - 1) * LMW);
-  const int slots = max_linesearch < NSTORE ? max_linesearch : NSTORE;   // stored candidates (tsat_device.hpp)
+  // stored candidates (tsat_device.hpp): one slab for every candidate where the automatic choice runs a one-trajectory build, so
+  // that no line search repeats a sweep; the large batches of the packed builds (which keep PK_STORE at most) stay at NSTORE
+  const int slots = reserved_slots(T, max_linesearch);
   rc |= dev_alloc(h, &h->CAND, Tn * (size_t)slots * N * XUW);
   rc |= dev_alloc(h, &h->stats, Tn);
   if (trows > 0) rc |= dev_alloc(h, &h->trace, Tn * (size_t)trows * 8);
   if (rc) { release(h); return -10; }
   h->T = T; h->N = n_knots; h->n_tab = n_tab; h->n_btab = n_btab; h->max_ls = max_linesearch;
+  h->slots = slots;
   h->trace_rows = trows;
   return 0;
 }
@@ -394,7 +399,7 @@ solve_kern_t solve_variant(const tsat_handle* h, const tsat_options* o) {
 // between 8192 and 16384, and from there on with a long iteration budget, eight per wavefront at two wavefronts per SIMD
 // (packed8: selected_build). packed (four per wavefront at two per SIMD) is no longer chosen automatically.
 constexpr int64_t TSAT_WIDE_MAX_T = 1024;
-constexpr int64_t TSAT_PACKED_MIN_T = 2048, TSAT_PACKED4W_MAX_T = 4096;
+constexpr int64_t TSAT_PACKED4W_MAX_T = 4096;     // (TSAT_PACKED_MIN_T = 2048: tsat_host_pack.hpp, which sizes the candidate slabs by it)
 constexpr int64_t TSAT_PACKED8W_MAX_T = 8192;
 constexpr int64_t TSAT_PACKED16W_MIN_T = 16384, TSAT_LONG_BUDGET = 100;     // (budget = max_outer x max_inner)
 // the build (1 wide, 2 dense, 3 packed, 4 packed8, 5 packed8w, 6 packed16w, 7 packed4w) that (h->variant, batch size, precision) selects.
@@ -465,7 +470,8 @@ EndgameArgs endgame_args(tsat_handle* h, const tsat_options* o) {
 
 KArgs<double> solve_args(tsat_handle* h, const tsat_options* o) {
   KArgs<double> a;
-  a.T = (int)h->T; a.N = h->N; a.n_tab = h->n_tab; a.max_ls = h->max_ls < NSTORE ? h->max_ls : NSTORE; a.opt = *o;
+  a.T = (int)h->T; a.N = h->N; a.n_tab = h->n_tab; a.max_ls = h->slots; a.opt = *o;
+  a.ls_few = h->store_few; a.ls_hold = h->store_hold;
   a.P = h->P; a.BT = h->BT; a.bidx = h->bidx; a.nk = h->ragged ? h->nk : nullptr; a.U0 = h->U0;
   a.XU = h->XU; a.KD = h->KD; a.LAM = h->LAM; a.CAND = h->CAND;
   a.stats = h->stats; a.trace = h->trace; a.trace_rows = h->trace ? h->trace_rows : 0;
@@ -519,6 +525,15 @@ int tsat_set_endgame(tsat_handle* h, int32_t suspend_at) {
   if (!h) return -1;
   if (suspend_at < -1) return fail(h, -1, "suspend_at must be -1 (automatic), 0 (never) or the live count at which the packed builds park their trajectories");
   h->endgame = suspend_at;
+  return 0;
+}
+
+int tsat_set_store_policy(tsat_handle* h, int32_t few, int32_t hold) {
+  if (!h) return -1;
+  const std::string why = check_store_policy(few);
+  if (!why.empty()) return fail(h, -1, why);
+  h->store_few = few;
+  h->store_hold = hold;
   return 0;
 }
 

@@ -852,7 +852,7 @@ TSAT_DEV void solve_group(const KArgs<real>& a, int wave) {
     for (int i = 0; i < 7; ++i) r.nu[i] = u.nu[i];
     r.outer = u.outer; r.it = u.it; r.djz = u.djz; r.inner_iters = u.inner_iters; r.ls_trials = u.ls_trials;
     r.n_backward = u.n_backward; r.n_forward = u.n_forward; r.bp_restarts = u.bp_restarts; r.fp_fails = u.fp_fails; r.trow = u.trow;
-        r.cur = u.cur;
+        r.cur = u.cur; r.since_deep = (u.last_jw >= ((a.ls_few >= 1) ? a.ls_few : N_FEW) - 1) ? 0 : LS_SHALLOW;
     TSAT_SYNC();
     const int parked = continue_trajectory<real, INTEG, DIAGJ, ES>(a, traj0 + gl, r);
     TSAT_SYNC();
@@ -885,7 +885,7 @@ TSAT_DEV void solve_group(const KArgs<real>& a, int wave) {
         for (int i = 0; i < 7; ++i) r.nu[i] = u.nu[i];
         r.outer = u.outer; r.it = u.it; r.djz = u.djz; r.inner_iters = u.inner_iters; r.ls_trials = u.ls_trials;
         r.n_backward = u.n_backward; r.n_forward = u.n_forward; r.bp_restarts = u.bp_restarts; r.fp_fails = u.fp_fails; r.trow = u.trow;
-        r.cur = u.cur;
+        r.cur = u.cur; r.since_deep = (u.last_jw >= ((a.ls_few >= 1) ? a.ls_few : N_FEW) - 1) ? 0 : LS_SHALLOW;
       }
       if (myg == g) { mine.active = 0; mine.need_bwd = 0; }
     }

@@ -272,6 +272,12 @@ class AugmentedLagrangianSolver:
         (-1 automatic, 0 never): see tsat_set_endgame. Results do not depend on it."""
         self._check(self._lib.tsat_set_endgame(self._h, int(suspend_at)), "tsat_set_endgame")
 
+    def set_store_policy(self, few, hold):
+        """one-trajectory builds: roll-outs a forward sweep keeps while line searches end early (`few`), and for how many
+        further iterations after a deep search it keeps all of them (`hold`; 0 the next iteration only, negative: to the end
+        of the solve): see tsat_set_store_policy. Results do not depend on it, only n_forward does."""
+        self._check(self._lib.tsat_set_store_policy(self._h, int(few), int(hold)), "tsat_set_store_policy")
+
     def selected_build(self, abi_opts):
         """(build, endgame_at) the next run with these options launches on the reserved batch: build 1 wide, 2 dense, 3 packed,
         4 packed8, 5 packed8w, 6 packed16w, 7 packed4w; endgame_at = live count at which a packed launch parks its trajectories (0: none). tsat_selected_build."""
