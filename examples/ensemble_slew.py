@@ -19,8 +19,8 @@ load_package()
 from tortoisesat_jl_amd import horizon, magnetic, slew_setup as ss, tracking, trajopt as to  # noqa: E402
 
 
-def plan(solver, say=print):
-    """the plan: examples/single_slew.py, line for line. Returns (batch, res, N)."""
+def plan(solver, say=print, J=None):
+    """the plan: examples/single_slew.py, line for line (J: another inertia than its 1P preset). Returns (batch, res, N)."""
     kep = np.array([[0.0, 400.0 + 6371.0, 51.6, 0.0, 0.0, 90.0]])
     t0, tf, N_tab, cutoff, dt = 0.0, 5400.0, 5000, 20.0, 0.2
     B_coarse, _ = magnetic.magnetic_simulation(solver, kep, t0, tf, N_tab)
@@ -29,7 +29,7 @@ def plan(solver, say=print):
     t_final, N = float(t_final[0]), int(N[0])
     B_ECI, _ = magnetic.magnetic_simulation(solver, kep, t0, t_final, N)
     n, m = 8, 3
-    J = ss.INERTIA["1P"]
+    J = ss.INERTIA["1P"] if J is None else J
     x0 = np.r_[0.0, 0.0, 0.0, ss.axis_angle_quat([1.0, 0.0, 1.0], np.deg2rad(90.0)), 0.0]
     xf = np.r_[0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
     model_d = to.rk3(to.Model(to.DerivFunction(J, B_ECI[0]), n, m))

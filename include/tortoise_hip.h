@@ -334,7 +334,7 @@ int  tsat_tvlqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T,
                          const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
                          tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
                          double* K_lqr, double* X_sim);
-/* text of the last failure of tsat_tvlqr_ensemble / tsat_tvlqr_ensemble_dispersed on the calling thread ("" if none) */
+/* text of the last failure of tsat_tvlqr_ensemble / tsat_tvlqr_ensemble_dispersed / tsat_tvlqr_ensemble_gg on the calling thread ("" if none) */
 const char* tsat_ensemble_last_error(void);
 
 /* The same ensemble with a PLANT OF ITS OWN per realisation and the actuator's limit on the feedback command: what decides
@@ -365,6 +365,36 @@ int  tsat_tvlqr_ensemble_dispersed(tsat_handle* h, const tsat_tvlqr_options* o, 
                          const double* plant, const double* sat_lo, const double* sat_hi,
                          tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
                          double* K_lqr, double* X_sim, int32_t* n_clipped);
+
+/* tsat_tvlqr_ensemble_dispersed UNDER GRAVITY-GRADIENT TORQUE: the one external disturbance torque of the library. Every plant
+ * above feels m x B alone; for an elongated body in low orbit the gravity gradient is the largest missing term (3 GM / r^3 =
+ * 3.85e-6 s^-2 at 400 km: 8e-8 N m on a 3U inertia, a fifth of the authority of 0.01 A m^2 in 4e-5 T). It depends on the
+ * realisation's own inertia Jp, so it is a dispersion like the others; the solver's model and the gains do NOT contain it.
+ *   Rtab   3 x n_tab x n_btab   orbit positions, km, ECI: row i is the position at which field row i of Btab was evaluated
+ *                               (`pos` of tsat_btable_batch); indexed exactly like Btab — same btab_idx, same row
+ *                               floor(fma(c, dtau, tau)) clamped to [0, n_tab - 1]
+ *   gm     km^3 / s^2           (3.986004418e5 for the Earth); 0 switches the term off
+ * A pack launch turns row i into r^ = r / |r| and g = 3 gm / |r|^3 (s^-2). In every RK4 stage of a plant step, with x the stage's
+ * state as integrated (BEFORE the noise injection), q = x[3:7] / |x[3:7]| and the row of the stage (c = 0, 1/2, 1/2, 1: the index of
+ * the stage's field row):
+ *   r_b    = qrot(q, r^)                     the rotation the field row gets
+ *   tau_gg = g (r_b x (Jp r_b))              N m, Jp the realisation's inertia in kg m^2
+ *   k[0:3] += (h inv(Jp)) tau_gg             added to the stage's increment after the plant's own evaluation
+ * Everything else of realisation (t, m) is that of tsat_tvlqr_ensemble_dispersed: command rule, limits, G, m_res, noise draws and
+ * their injection, statistic, table clock. stats_nominal is the noise-free MODEL plant flying through the same gravity field with
+ * Jmat: the environment is not the model's choice. gm = 0 reproduces tsat_tvlqr_ensemble_dispersed bit for bit (through the same
+ * kernel as any other gm). The packed rows (32 n_tab n_btab bytes) are a grow-only workspace of the handle: counted by
+ * tsat_workspace_bytes, freed by tsat_workspace_trim(h, 1).
+ * Rejected with -1 (text in tsat_ensemble_last_error): Rtab NULL, a non-finite entry of Rtab, a row with |r| = 0, gm non-finite or
+ * negative, and everything tsat_tvlqr_ensemble_dispersed rejects. */
+int  tsat_tvlqr_ensemble_gg(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                         const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* K_lqr, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Receding-horizon re-solve on the RESIDENT batch (BASELINE.json configs[4]). NOT in the reference —
@@ -451,6 +481,18 @@ int  tsat_mpc_run_held(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_o
                        int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo, const double* sat_hi,
                        const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
                        int32_t* n_clipped, float* solve_ms);
+
+/* tsat_mpc_run_held with the gravity-gradient torque of tsat_tvlqr_ensemble_gg in every plant step (all four RK4 stages, the rows
+ * of the step's table clock, Jp of the trajectory's plant — the model's inertia when `plant` is NULL). The solve does not see the
+ * term: the question is whether re-planning survives it. Rtab is 3 x n_tab x n_btab of the RESIDENT batch (its btab_idx), gm as
+ * above; replan_every = 1 is the every-step loop under gravity gradient. gm = 0 reproduces tsat_mpc_run_held bit for bit (through
+ * the same kernel as any other gm). The packed rows share the handle's workspace with tsat_tvlqr_ensemble_gg.
+ * Rejected with -1 (text in tsat_last_error): Rtab NULL, a non-finite entry of Rtab, a row with |r| = 0, gm non-finite or negative,
+ * and everything tsat_mpc_run_held rejects. */
+int  tsat_mpc_run_held_gg(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                       int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo, const double* sat_hi,
+                       const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
+                       int32_t* n_clipped, float* solve_ms, const double* Rtab, double gm);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Sweep exchange across GPUs. The reference's Monte-Carlo is a serial loop whose iterations share nothing but the result

@@ -369,6 +369,40 @@ function attitude_ensemble_dispersed(s::HIPSolver, p::BatchProblem, x0_lqr::Arra
 end
 
 """
+attitude_ensemble_gg(s, p, x0_lqr, Q_lqr, Qf_lqr, R_lqr, plant, Rtab; gm, sat_lo, sat_hi, noise_id0, opts, want_K,
+want_trajectories) — `tsat_tvlqr_ensemble_gg`: `attitude_ensemble_dispersed` under gravity-gradient torque. Rtab 3 x n_tab x n_btab
+holds the orbit position (km, ECI) of every row of `p.B_ECI` and follows `p.btab_idx`; gm in km^3 / s^2 (0 switches the term off).
+The torque acts with each realisation's own inertia; the plan and the gains do not know of it. Returns as
+`attitude_ensemble_dispersed`.
+"""
+function attitude_ensemble_gg(s::HIPSolver, p::BatchProblem, x0_lqr::Array{Float64,3}, Q_lqr::Matrix{Float64},
+                              Qf_lqr::Matrix{Float64}, R_lqr::Matrix{Float64}, plant::Array{Float64,3}, Rtab::Array{Float64,3};
+                              gm::Float64 = 3.986004418e5,
+                              sat_lo::Matrix{Float64} = zeros(3, 0), sat_hi::Matrix{Float64} = zeros(3, 0),
+                              noise_id0::Vector{Int64} = Int64[], opts::TvlqrOptions = TvlqrOptions(noise_mode = 1),
+                              want_K::Bool = false, want_trajectories::Bool = false)
+    T = size(p.x0, 2); N = p.N; M = size(x0_lqr, 2)
+    size(plant) == (21, M, T) || error("plant must be 21 x M x T")
+    size(Rtab) == size(p.B_ECI) || error("Rtab must have the shape of B_ECI: 3 x n_tab x n_btab")
+    opts.n_knots = N; opts.n_tab = size(p.B_ECI, 2)
+    st = Matrix{TvlqrStats}(undef, M, T); nominal = Vector{TvlqrStats}(undef, T); summary = zeros(8, T)
+    n_clipped = zeros(Int32, M, T)
+    K = want_K ? zeros(3, 6, N - 1, T) : nothing
+    Xs = want_trajectories ? zeros(7, N, M, T) : nothing
+    rc = ccall((:tsat_tvlqr_ensemble_gg, LIB), Cint,
+        (Ptr{Cvoid}, Ref{TvlqrOptions}, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{TvlqrStats}, Ptr{Float64}, Ptr{TvlqrStats},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Float64),
+        s.handle, opts, T, size(p.B_ECI, 3), M, p.X, p.U, p.xf, p.B_ECI, p.btab_idx, p.tau0, p.dtau, p.dt, p.J,
+        Q_lqr, Qf_lqr, R_lqr, x0_lqr, isempty(noise_id0) ? C_NULL : noise_id0, isempty(p.n_knots) ? C_NULL : p.n_knots,
+        plant, isempty(sat_lo) ? C_NULL : sat_lo, isempty(sat_hi) ? C_NULL : sat_hi,
+        st, summary, nominal, K === nothing ? C_NULL : K, Xs === nothing ? C_NULL : Xs, n_clipped, Rtab, gm)
+    rc == 0 || error("tsat_tvlqr_ensemble_gg failed ($rc): " * unsafe_string(ccall((:tsat_ensemble_last_error, LIB), Cstring, ())))
+    return st, summary, nominal, K, Xs, n_clipped
+end
+
+"""
 receding_horizon!(s, p, n_steps; plant_integrator = 4) — `tsat_mpc_run` on the batch `p` (uploaded here): re-solve the
 horizon every control step with the budget of `s.opts`, apply U[:,1] to the noise-free plant, shift the plan.
 No reference equivalent (BASELINE.json configs[4]). Returns X_hist 7×(n_steps+1)×T, U_hist 3×n_steps×T.
@@ -456,6 +490,42 @@ function receding_horizon_held!(s::HIPSolver, p::BatchProblem, n_steps::Integer,
         s.handle, o, opts, n_steps, step0, replan_every, feedback ? 1 : 0, isempty(plant) ? C_NULL : plant,
         isempty(sat_lo) ? C_NULL : sat_lo, isempty(sat_hi) ? C_NULL : sat_hi, isempty(noise_id) ? C_NULL : noise_id, Xh, Uh, C_NULL, st,
         n_clipped, C_NULL), "tsat_mpc_run_held")
+    return Xh, Uh, st, n_clipped
+end
+
+"""
+receding_horizon_held_gg!(s, p, n_steps, replan_every, Rtab; gm, feedback, plant, sat_lo, sat_hi, noise_id, step0, opts) —
+`tsat_mpc_run_held_gg`: `receding_horizon_held!` with the gravity-gradient torque of `attitude_ensemble_gg` in every plant step
+(Rtab 3 x n_tab x n_btab, km; gm in km^3 / s^2). The solve does not see the term. `replan_every = 1` is the every-step loop under
+gravity gradient. Returns (X_hist, U_hist, stats, n_clipped).
+"""
+function receding_horizon_held_gg!(s::HIPSolver, p::BatchProblem, n_steps::Integer, replan_every::Integer, Rtab::Array{Float64,3};
+                                   gm::Float64 = 3.986004418e5, feedback::Bool = true,
+                                   plant::Matrix{Float64} = zeros(21, 0), sat_lo::Matrix{Float64} = zeros(3, 0),
+                                   sat_hi::Matrix{Float64} = zeros(3, 0), noise_id::Vector{Int64} = Int64[], step0::Integer = 0,
+                                   opts::TvlqrOptions = TvlqrOptions(noise_mode = 1), upload::Bool = true)
+    T = size(p.x0, 2); N = p.N
+    isempty(plant) || size(plant) == (21, T) || error("plant must be 21 x T")
+    size(Rtab) == size(p.B_ECI) || error("Rtab must have the shape of B_ECI: 3 x n_tab x n_btab")
+    o = s.opts; o.n_knots = N; o.n_tab = size(p.B_ECI, 2)
+    if upload
+        check(s, ccall((:tsat_batch_reserve, LIB), Cint, (Ptr{Cvoid}, Int64, Int32, Int32, Int64, Int32),
+                       s.handle, T, N, o.n_tab, size(p.B_ECI, 3), o.max_linesearch), "tsat_batch_reserve")
+        check(s, ccall((:tsat_batch_upload, LIB), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            s.handle, p.x0, p.xf, p.B_ECI, p.btab_idx, p.tau0, p.dtau, p.dt, p.J, p.Q, p.Qf, p.R, p.u_min, p.u_max, p.U0),
+            "tsat_batch_upload")
+        isempty(p.n_knots) || check(s, ccall((:tsat_batch_knots, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}), s.handle, p.n_knots), "tsat_batch_knots")
+    end
+    Xh = zeros(7, n_steps + 1, T); Uh = zeros(3, n_steps, T)
+    st = Vector{TvlqrStats}(undef, T); n_clipped = zeros(Int32, T)
+    check(s, ccall((:tsat_mpc_run_held_gg, LIB), Cint,
+        (Ptr{Cvoid}, Ref{Options}, Ref{TvlqrOptions}, Int32, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Stats}, Ptr{TvlqrStats}, Ptr{Int32}, Ptr{Cfloat}, Ptr{Float64}, Float64),
+        s.handle, o, opts, n_steps, step0, replan_every, feedback ? 1 : 0, isempty(plant) ? C_NULL : plant,
+        isempty(sat_lo) ? C_NULL : sat_lo, isempty(sat_hi) ? C_NULL : sat_hi, isempty(noise_id) ? C_NULL : noise_id, Xh, Uh, C_NULL, st,
+        n_clipped, C_NULL, Rtab, gm), "tsat_mpc_run_held_gg")
     return Xh, Uh, st, n_clipped
 end
 

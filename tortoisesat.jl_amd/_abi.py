@@ -131,6 +131,12 @@ PROTOTYPES = {
     "tsat_tvlqr_ensemble_dispersed": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp,
                                                 _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp,
                                                 C.c_void_p, _dp, C.c_void_p, _dp, _dp, _ip]),
+    "tsat_tvlqr_ensemble_gg": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp,
+                                         _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp,
+                                         C.c_void_p, _dp, C.c_void_p, _dp, _dp, _ip, _dp, C.c_double]),
+    "tsat_mpc_run_held_gg": (C.c_int, [C.c_void_p, C.POINTER(Options), C.POINTER(TvlqrOptions), C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                       _dp, _dp, _dp, C.POINTER(C.c_int64), _dp, _dp, C.c_void_p, C.c_void_p, _ip, C.POINTER(C.c_float),
+                                       _dp, C.c_double]),
 }
 
 LIB_NAME = "libtortoise_hip.so"

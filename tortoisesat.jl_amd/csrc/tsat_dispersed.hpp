@@ -108,6 +108,7 @@ struct DispersedPlant {
     hit = 0;
     for (int c = 0; c < 3; ++c) us[c] = (G[3 * c] * uc[0] + G[3 * c + 1] * uc[1] + G[3 * c + 2] * uc[2] + mr[c]) * cs;
   }
+  TSAT_DEV void disturb(const Traj<real>&, int, double, const real*, real*) const {}
   TSAT_DEV void store(size_t i) const {
     if (d.nclip) d.nclip[i] = clipped;
   }

@@ -70,7 +70,9 @@ TSAT_DEV real ensemble_angle(const Traj<real>& tr, const real x[7]) {
 // The MODEL plant: every realisation flies the satellite the plan was made for. A plant type answers what differs between the
 // entry points and nothing else (the other one is DispersedPlant, tsat_dispersed.hpp): the instantiation of dyn_sim_h /
 // control_scale it flies, what it loads once per lane, the Traj the dynamics read, what becomes of the feedback command on its
-// way to the torquers, and what it stores per realisation besides the statistic.
+// way to the torquers, what besides m x B acts on the body in an RK4 stage (`disturb`: knot, stage fraction c of the table
+// clock, the stage state as integrated, the stage's increment — GgPlant of tsat_gg.hpp adds the gravity-gradient term there),
+// and what it stores per realisation besides the statistic.
 template <typename real, int DIAGJ_>
 struct ModelPlant {
   static constexpr int DIAGJ = DIAGJ_;
@@ -80,6 +82,7 @@ struct ModelPlant {
   TSAT_DEV void actuate(const real uc[3], real, real us[3]) {
     for (int c = 0; c < 3; ++c) us[c] = uc[c];
   }
+  TSAT_DEV void disturb(const Traj<real>&, int, double, const real*, real*) const {}   // no torque besides m x B
   TSAT_DEV void store(size_t) const {}
 };
 
@@ -151,15 +154,19 @@ TSAT_DEV void ensemble_rollout(const EnsArgs<real>& a, Plant& plant, int traj, i
     for (int i = 0; i < 9; ++i) nz[i] = 0;
     if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 0, a.sg, a.sa, a.fa, nz);
     dyn_sim_h<real, DIAGJ>(tp, x, us, b0, noisy, nz, k1);
+    plant.disturb(tr, k, 0.0, x, k1);
     for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k1[i];
     if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 1, a.sg, a.sa, a.fa, nz);
     dyn_sim_h<real, DIAGJ>(tp, t, us, b1, noisy, nz, k2);
+    plant.disturb(tr, k, 0.5, t, k2);
     for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k2[i];
     if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 2, a.sg, a.sa, a.fa, nz);
     dyn_sim_h<real, DIAGJ>(tp, t, us, b1, noisy, nz, k3);
+    plant.disturb(tr, k, 0.5, t, k3);
     for (int i = 0; i < 7; ++i) t[i] = x[i] + k3[i];
     if (noisy) plant_noise<real>(a.k0, a.k1, gid, k, 3, a.sg, a.sa, a.fa, nz);
     dyn_sim_h<real, DIAGJ>(tp, t, us, b2, noisy, nz, k4);
+    plant.disturb(tr, k, 1.0, t, k4);
     for (int i = 0; i < 7; ++i) x[i] = x[i] + (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) * (real)(1.0 / 6.0);
   }
   // last sample j = N

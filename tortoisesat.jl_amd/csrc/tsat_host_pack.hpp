@@ -291,6 +291,21 @@ inline std::string check_mpc_held(int32_t replan_every, int32_t feedback, int mi
   return "";
 }
 
+// what the gravity-gradient entry points (tsat_tvlqr_ensemble_gg, tsat_mpc_run_held_gg) reject beyond their parents' checks: ""
+// or the reason. Rtab: `rows` orbit positions of 3 doubles (km)
+inline std::string check_gravity(const double* Rtab, double gm, int64_t rows) {
+  if (!Rtab) return "null Rtab";
+  if (!std::isfinite(gm) || gm < 0.0) return "gm must be finite and >= 0";
+  for (int64_t e = 0; e < rows; ++e) {
+    const double* r = Rtab + (size_t)e * 3;
+    if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2])) return "non-finite Rtab entry in row " + std::to_string(e);
+    const double n2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];     // what the pack kernel divides by
+    if (!(n2 > 0.0)) return "Rtab row " + std::to_string(e) + " has |r| = 0";
+    if (!std::isfinite(n2)) return "Rtab row " + std::to_string(e) + " has |r|^2 beyond the range of a double";
+  }
+  return "";
+}
+
 // scales of the three draws of `simulator` (src/simulator.jl:5,10,22)
 inline void tv_noise_defaults(tsat_tvlqr_options& o) {
   const double deg = 3.14159265358979323846 / 180.0;

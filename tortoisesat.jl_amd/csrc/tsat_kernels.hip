@@ -16,6 +16,7 @@
 #include <vector>
 #include "tsat_host_pack.hpp"
 #include "tsat_mpc_held.hpp"
+#include "tsat_gg.hpp"
 
 using namespace tsat;
 
@@ -41,6 +42,10 @@ hipError_t tsat_launch_mpc_dispersed(const MpcDispArgs<double>& a, const double*
 // the pack, and hold + plan shift after every solve, of tsat_mpc_run_held (tsat_kernels_mpc_held.hip)
 hipError_t tsat_launch_mpc_held_pack(const MpcHeldArgs<double>& a, const double* plant, hipStream_t stream);
 hipError_t tsat_launch_mpc_held(const MpcHeldArgs<double>& a, int error_state, hipStream_t stream);
+hipError_t tsat_launch_mpc_held_shift(const MpcArgs<double>& m, int r, hipStream_t stream);
+// the pack of the orbit table and the hold under gravity-gradient torque of tsat_mpc_run_held_gg (tsat_kernels_gg.hip)
+hipError_t tsat_launch_gg_pack(const double* R, double gm, double* GT, int64_t rows, hipStream_t stream);
+hipError_t tsat_launch_mpc_held_gg(const MpcHeldGgArgs<double>& a, int error_state, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -134,6 +139,7 @@ struct tsat_handle {
          WS_DL_X, WS_DL_U, WS_DL_K, WS_AG_X, WS_AG_U, WS_AG_ST, WS_AG_XA, WS_AG_UA, WS_AG_STA,   // staging: WS_DL_X .. WS_AG_STA (tsat_workspace_trim)
          WS_AG_CHK, WS_MPC_TALLY, WS_ENDGAME,
          WS_MPCD_PLANT, WS_MPCD_PL, WS_MPCD_SAT, WS_MPCD_NID, WS_MPCD_REC, WS_MPCD_ST, WS_MPCD_CLIP,   // tsat_mpc_run_dispersed
+         WS_GG_GT,             // packed gravity rows of tsat_tvlqr_ensemble_gg / tsat_mpc_run_held_gg
          WS_COUNT };
   void* ws[WS_COUNT] = {};
   size_t ws_bytes[WS_COUNT] = {};
@@ -191,6 +197,10 @@ int dev_alloc(tsat_handle* h, Tp** p, size_t n) {
 }
 
 }  // namespace
+
+// the packed gravity rows of the gravity-gradient entry points: the handle's grow-only slot, for the ensemble's translation
+// unit too (to which `struct tsat_handle` is opaque); nullptr on failure
+double* tsat_ws_gravity(tsat_handle* h, size_t bytes) { return (double*)ws_get(h, tsat_handle::WS_GG_GT, bytes); }
 
 extern "C" {
 
@@ -611,11 +621,13 @@ int tsat_mpc_tally(tsat_handle* h, int64_t* tally) {
 
 namespace {
 // the loop of tsat_mpc_run_dispersed (replan_every = 0: a solve and the one-wavefront-per-trajectory step kernel per control step)
-// and of tsat_mpc_run_held (replan_every >= 1: a solve, the lane-per-trajectory hold and the plan shift per block)
+// and of tsat_mpc_run_held (replan_every >= 1: a solve, the lane-per-trajectory hold and the plan shift per block); with
+// `gravity` the hold is the one of tsat_mpc_run_held_gg (Rtab [n_btab][n_tab][3] of the resident batch, gm)
 int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps,
                    int64_t step0, int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo,
                    const double* sat_hi, const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last,
-                   tsat_tvlqr_stats* stats, int32_t* n_clipped, float* solve_ms) {
+                   tsat_tvlqr_stats* stats, int32_t* n_clipped, float* solve_ms, bool gravity = false, const double* Rtab = nullptr,
+                   double gm = 0.0) {
   if (!h || !o || !po) return -1;
   const bool held = replan_every != 0;
   if (!h->uploaded) return fail(h, -1, "tsat_batch_upload has not been called");
@@ -624,6 +636,11 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   if (o->precision != 64) return fail(h, -1, std::string(name) + " runs the fp64 build only (precision must be 64)");
   const std::string bad = check_mpc_dispersed(*po, n_steps, step0, plant, sat_lo, sat_hi, h->T);
   if (!bad.empty()) return fail(h, -1, bad);
+  const size_t n_rows = (size_t)h->n_btab * (size_t)h->n_tab;
+  if (gravity) {
+    const std::string badg = check_gravity(Rtab, gm, (int64_t)n_rows);
+    if (!badg.empty()) return fail(h, -1, badg);
+  }
   if (!X_hist || !U_hist) return fail(h, -1, "null array");
   TSAT_HIP(h, hipSetDevice(h->dev));
   if (held) {
@@ -647,6 +664,14 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   MpcDispRec* dRec = (MpcDispRec*)ws_get(h, tsat_handle::WS_MPCD_REC, T * sizeof(MpcDispRec));
   tsat_tvlqr_stats* dSt = (tsat_tvlqr_stats*)ws_get(h, tsat_handle::WS_MPCD_ST, T * sizeof(tsat_tvlqr_stats));
   int* dClip = (int*)ws_get(h, tsat_handle::WS_MPCD_CLIP, T * sizeof(int));
+  // the gravity call: the packed rows are the handle's, the raw orbit table lives until the pack has run
+  double* dGT = gravity ? tsat_ws_gravity(h, n_rows * 4 * 8) : nullptr;
+  struct Raw {
+    double* p = nullptr;
+    ~Raw() { if (p) (void)hipFree(p); }
+  } dR;
+  if (gravity && (!dGT || hipMalloc((void**)&dR.p, n_rows * 3 * 8) != hipSuccess))
+    return fail(h, -10, std::string("device allocation failed in ") + name);
   if (!dHX || !dHU || !dTally || (plant && !dPlant) || !dPL || !dSat || (noise_id && !dNid) || !dRec || !dSt || !dClip)
     return fail(h, -10, std::string("device allocation failed in ") + name);
   std::vector<double> sat(T * SATW);               // a NULL limit is +-inf: the step has one code path
@@ -658,6 +683,7 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   TSAT_HIP(h, hipMemcpy(dSat, sat.data(), sat.size() * 8, hipMemcpyHostToDevice));
   if (plant) TSAT_HIP(h, hipMemcpy(dPlant, plant, T * TSAT_PLANT_W * 8, hipMemcpyHostToDevice));
   if (noise_id) TSAT_HIP(h, hipMemcpy(dNid, noise_id, T * sizeof(long long), hipMemcpyHostToDevice));
+  if (gravity) TSAT_HIP(h, hipMemcpy(dR.p, Rtab, n_rows * 3 * 8, hipMemcpyHostToDevice));
   TSAT_HIP(h, hipMemsetAsync(dTally, 0, T * 4 * sizeof(long long), h->stream));
   h->mpc_tally_T = (int64_t)T;
   const KArgs<double> a = solve_args(h, o);
@@ -676,15 +702,23 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   e.nid0 = dNid; e.sg = po->sigma_gyro; e.sa = po->sigma_att; e.fa = po->field_amp; e.stats = dSt;
   md.noisy = po->noise_mode; md.step0 = (long long)step0; md.rec = dRec;
   mh.KD = h->KD; mh.feedback = feedback;
+  MpcHeldGgArgs<double> mg = {};
   int rc = 0;
   if (hipEventRecord(h->ev0, h->stream) != hipSuccess) rc = -10;
   if (held) {   // the pack, then solve, hold and shift per block queued back to back; the stream orders them
     if (tsat_launch_mpc_held_pack(mh, dPlant, h->stream) != hipSuccess) rc = -10;
+    if (!rc && gravity && tsat_launch_gg_pack(dR.p, gm, dGT, (int64_t)n_rows, h->stream) != hipSuccess) rc = -10;
     for (int s = 0; s < n_steps && !rc; s += replan_every) {
       if (launch_solve(h, o, a) != hipSuccess) rc = -10;
       m.step = s;
       mh.r = std::min<int>(replan_every, n_steps - s);
-      if (!rc && tsat_launch_mpc_held(mh, o->error_state, h->stream) != hipSuccess) rc = -10;
+      if (gravity) {   // the hold through the gravity rows, then the held loop's own plan shift
+        mg.h = mh; mg.GT = dGT;
+        if (!rc && tsat_launch_mpc_held_gg(mg, o->error_state, h->stream) != hipSuccess) rc = -10;
+        if (!rc && tsat_launch_mpc_held_shift(m, mh.r, h->stream) != hipSuccess) rc = -10;
+      } else {
+        if (!rc && tsat_launch_mpc_held(mh, o->error_state, h->stream) != hipSuccess) rc = -10;
+      }
     }
   } else {
     for (int s = 0; s < n_steps && !rc; ++s) {   // 2 n_steps launches (+ the pack) queued back to back; the stream orders them
@@ -716,6 +750,15 @@ int tsat_mpc_run_held(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_op
   if (replan_every < 1) return fail(h, -1, check_mpc_held(replan_every, feedback, 2));
   return mpc_plant_loop(h, "tsat_mpc_run_held", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id, X_hist,
                         U_hist, stats_last, stats, n_clipped, solve_ms);
+}
+
+int tsat_mpc_run_held_gg(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                         int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo, const double* sat_hi,
+                         const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
+                         int32_t* n_clipped, float* solve_ms, const double* Rtab, double gm) {
+  if (replan_every < 1) return fail(h, -1, check_mpc_held(replan_every, feedback, 2));
+  return mpc_plant_loop(h, "tsat_mpc_run_held_gg", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id,
+                        X_hist, U_hist, stats_last, stats, n_clipped, solve_ms, true, Rtab, gm);
 }
 
 int tsat_batch_export_device(tsat_handle* h, void* X_dev, void* U_dev, void* K_dev, void* stats_dev) {

@@ -15,7 +15,10 @@
 //
 // tsat_tvlqr_ensemble_dispersed is the same call with a plant per realisation and limits on the command (tsat_dispersed.hpp):
 // the host validates the plants, a pack kernel forms inv(Jp) and the per-lane records between steps 2 and 3, and step 4
-// launches the dispersed kernel instead. Steps 1-3 and 5 are one piece of code for both entry points (run_ensemble).
+// launches the dispersed kernel instead. tsat_tvlqr_ensemble_gg is the dispersed call under gravity-gradient torque
+// (tsat_gg.hpp): the host validates the orbit table, a pack kernel turns it into gravity rows in a grow-only workspace of the
+// handle, and step 4 launches the kernel of tsat_kernels_gg.hip. Steps 1-3 and 5 are one piece of code for all entry points
+// (run_ensemble).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -25,8 +28,15 @@
 #include "tsat_host_pack.hpp"
 #include "tsat_ensemble.hpp"
 #include "tsat_dispersed.hpp"
+#include "tsat_gg.hpp"
 
 using namespace tsat;
+
+// pack and roll-out of tsat_tvlqr_ensemble_gg (tsat_kernels_gg.hip); the handle's workspace for the packed gravity rows,
+// counted by tsat_workspace_bytes (tsat_kernels.hip)
+hipError_t tsat_launch_gg_pack(const double* R, double gm, double* GT, int64_t rows, hipStream_t stream);
+hipError_t tsat_launch_ensemble_gg(const GgEnsArgs<double>& g, int waves, hipStream_t stream);
+double* tsat_ws_gravity(tsat_handle* h, size_t bytes);
 
 template <typename real, int DIAGJ>
 __global__ __launch_bounds__(64) void tsat_ensemble_kernel(EnsArgs<real> a) {
@@ -111,6 +121,12 @@ struct Dispersion {
   int32_t* n_clipped;
 };
 
+// ... and tsat_tvlqr_ensemble_gg to the dispersed call
+struct Gravity {
+  const double* Rtab;
+  double gm;
+};
+
 std::string at_tm(int64_t t, int m) { return " at (t, m) = (" + std::to_string(t) + ", " + std::to_string(m) + ")"; }
 
 // the host only validates the plants: "" or the reason, with the offending (t, m)
@@ -126,13 +142,13 @@ std::string check_dispersion(const Dispersion& d, int64_t T, int M) {
   return "";
 }
 
-// both entry points: `disp` == nullptr is tsat_tvlqr_ensemble
+// all entry points: `disp` == nullptr is tsat_tvlqr_ensemble, `grav` != nullptr (with `disp`) tsat_tvlqr_ensemble_gg
 int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
                  const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
                  const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
                  const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
                  tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr,
-                 double* X_sim, const Dispersion* disp) {
+                 double* X_sim, const Dispersion* disp, const Gravity* grav = nullptr) {
   g_err.clear();
   if (!h || !o) return efail(-1, "null handle or options");
   const std::string why = check_tv_options(*o);
@@ -156,6 +172,10 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   }
   if (disp) {
     const std::string bad = check_dispersion(*disp, T, M);
+    if (!bad.empty()) return efail(-1, bad);
+  }
+  if (grav) {
+    const std::string bad = check_gravity(grav->Rtab, grav->gm, n_btab * (int64_t)o->n_tab);
     if (!bad.empty()) return efail(-1, bad);
   }
   // ---- 1. the handle: the library's own checks on slew 0 cut to two knots; its GPU becomes the thread's current device ----
@@ -195,6 +215,9 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   int* dClip = nullptr;
   if (ok && disp) ok = s.alloc(&dPlant, nS * TSAT_PLANT_W) && s.alloc(&dPL, Tn * PLW * (size_t)Mp) && s.alloc(&dSat, Tn * SATW);
   if (ok && disp && disp->n_clipped) ok = s.alloc(&dClip, nS);
+  // the gravity call: the raw orbit table is the call's, the packed rows are the handle's
+  double *dR = nullptr, *dGT = nullptr;
+  if (ok && grav) ok = s.alloc(&dR, nB * 3) && (dGT = tsat_ws_gravity(h, nB * 4 * 8)) != nullptr;
   if (!ok) return efail(-10, std::string("device allocation failed in ") + name);
 #define ENS_HIP(call)                                                                                   \
   do {                                                                                                  \
@@ -235,6 +258,10 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
                        T, M, Mp);
     ENS_HIP(hipGetLastError());
   }
+  if (grav) {
+    ENS_HIP(hipMemcpy(dR, grav->Rtab, nB * 3 * 8, hipMemcpyHostToDevice));
+    ENS_HIP(tsat_launch_gg_pack(dR, grav->gm, dGT, (int64_t)nB, s.stream));
+  }
   ENS_HIP(hipEventRecord(s.ev[0], s.stream));
   {
     auto kern = cls == 2 ? tsat_ensemble_gains_kernel<double, 2>
@@ -255,7 +282,13 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
     if (disp) {
       DispArgs<double> d;
       d.e = a; d.PL = dPL; d.Mp = Mp; d.SAT = dSat; d.nclip = dClip;
-      hipLaunchKernelGGL(tsat_dispersed_kernel<double>, dim3((unsigned)T, (unsigned)nw), dim3(64), 0, s.stream, d);
+      if (grav) {
+        GgEnsArgs<double> g;
+        g.d = d; g.GT = dGT;
+        ENS_HIP(tsat_launch_ensemble_gg(g, nw, s.stream));
+      } else {
+        hipLaunchKernelGGL(tsat_dispersed_kernel<double>, dim3((unsigned)T, (unsigned)nw), dim3(64), 0, s.stream, d);
+      }
     } else {
       auto kern = cls == 2 ? tsat_ensemble_kernel<double, 2> : (cls == 1 ? tsat_ensemble_kernel<double, 1> : tsat_ensemble_kernel<double, 0>);
       hipLaunchKernelGGL(kern, dim3((unsigned)T, (unsigned)nw), dim3(64), 0, s.stream, a);
@@ -320,6 +353,19 @@ int tsat_tvlqr_ensemble_dispersed(tsat_handle* h, const tsat_tvlqr_options* o, i
   const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
   return run_ensemble("tsat_tvlqr_ensemble_dispersed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, Qd, Qfd, Rd,
                       x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, K_lqr, X_sim, &d);
+}
+
+int tsat_tvlqr_ensemble_gg(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                           const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                           const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
+                           const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                           const double* plant, const double* sat_lo, const double* sat_hi, tsat_tvlqr_stats* stats,
+                           double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr, double* X_sim, int32_t* n_clipped,
+                           const double* Rtab, double gm) {
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  return run_ensemble("tsat_tvlqr_ensemble_gg", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, Qd, Qfd, Rd, x0_sim,
+                      noise_id0, n_knots, stats, summary, stats_nominal, K_lqr, X_sim, &d, &g);
 }
 
 }  // extern "C"

@@ -32,12 +32,17 @@ hipError_t tsat_launch_mpc_held_pack(const MpcHeldArgs<double>& a, const double*
   return hipGetLastError();
 }
 
-// the block of a.r control steps from step a.s.m.step on `stream`, then the plan shifted by a.r as the next warm start
+// the plan shifted by r as the next warm start (also after the hold of tsat_mpc_run_held_gg, tsat_kernels_gg.hip)
+hipError_t tsat_launch_mpc_held_shift(const MpcArgs<double>& m, int r, hipStream_t stream) {
+  hipLaunchKernelGGL(tsat_mpc_held_shift_kernel, dim3((unsigned)m.T), dim3(64), 0, stream, m, r);
+  return hipGetLastError();
+}
+
+// the block of a.r control steps from step a.s.m.step on `stream`, then the plan shift
 hipError_t tsat_launch_mpc_held(const MpcHeldArgs<double>& a, int error_state, hipStream_t stream) {
   const unsigned T = (unsigned)a.s.m.T;
   hipLaunchKernelGGL(error_state ? tsat_mpc_held_kernel<1> : tsat_mpc_held_kernel<0>, dim3((T + 63) / 64), dim3(64), 0, stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(tsat_mpc_held_shift_kernel, dim3(T), dim3(64), 0, stream, a.s.m, a.r);
-  return hipGetLastError();
+  return tsat_launch_mpc_held_shift(a.s.m, a.r, stream);
 }

@@ -83,24 +83,36 @@ TSAT_DEV void mpc_held_sample(const EnsArgs<real>& e, const Traj<real>& tr, cons
   }
 }
 
-// one RK4 step of the plant tp under the applied dipole us, field rows b0, b1, b2: the stage sequence of ensemble_rollout
-// (draw the stage's nine values of (gid, knot, stage), evaluate, combine)
-template <typename real>
+// what acts on the body in an RK4 stage besides m x B: nothing here (GgEnv of tsat_gg.hpp adds the gravity-gradient term).
+// `row`: the table row of the stage, x: the stage state as integrated, k: the stage's increment
+struct NoEnv {
+  template <typename real>
+  TSAT_DEV void stage(const Traj<real>&, int, const real*, real*) const {}
+};
+
+// one RK4 step of the plant tp under the applied dipole us, field rows b0, b1, b2 (table rows i0, i1, i2): the stage sequence of
+// ensemble_rollout (draw the stage's nine values of (gid, knot, stage), evaluate, combine)
+template <typename real, typename Env>
 TSAT_DEV void mpc_held_rk4(const Traj<real>& tp, const EnsArgs<real>& e, bool noisy, long long gid, int knot, const real x[7],
-                           const real us[3], const real b0[3], const real b1[3], const real b2[3], real xn[7]) {
+                           const real us[3], const real b0[3], const real b1[3], const real b2[3], const Env& env, int i0, int i1,
+                           int i2, real xn[7]) {
   real k1[7], k2[7], k3[7], k4[7], t[7], nz[9];
   for (int i = 0; i < 9; ++i) nz[i] = 0;
   if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 0, e.sg, e.sa, e.fa, nz);
   dyn_sim_h<real, 0>(tp, x, us, b0, noisy, nz, k1);
+  env.stage(tp, i0, x, k1);
   for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k1[i];
   if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 1, e.sg, e.sa, e.fa, nz);
   dyn_sim_h<real, 0>(tp, t, us, b1, noisy, nz, k2);
+  env.stage(tp, i1, t, k2);
   for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k2[i];
   if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 2, e.sg, e.sa, e.fa, nz);
   dyn_sim_h<real, 0>(tp, t, us, b1, noisy, nz, k3);
+  env.stage(tp, i1, t, k3);
   for (int i = 0; i < 7; ++i) t[i] = x[i] + k3[i];
   if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 3, e.sg, e.sa, e.fa, nz);
   dyn_sim_h<real, 0>(tp, t, us, b2, noisy, nz, k4);
+  env.stage(tp, i2, t, k4);
   for (int i = 0; i < 7; ++i) xn[i] = x[i] + (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) * (real)(1.0 / 6.0);
 }
 
@@ -156,8 +168,8 @@ TSAT_DEV real mpc_held_feedback(real u, const real kd[21], int c, const real dx[
 }
 
 // trajectory t through the a.r control steps of its block
-template <typename real, int ES>
-TSAT_DEV void mpc_held_block(const MpcHeldArgs<real>& a, int t) {
+template <typename real, int ES, typename Env = NoEnv>
+TSAT_DEV void mpc_held_block(const MpcHeldArgs<real>& a, int t, const Env& env = Env()) {
   const MpcArgs<real>& m = a.s.m;
   const EnsArgs<real>& e = a.s.d.e;
   if (t >= m.T) return;
@@ -202,12 +214,16 @@ TSAT_DEV void mpc_held_block(const MpcHeldArgs<real>& a, int t) {
     real uc[3], us[3], xn[7];
     for (int c = 0; c < 3; ++c) uc[c] = plant.command(c, v[c], cs);
     plant.actuate(uc, cs, us);
-    // rows at tau, tau + dtau / 2, tau + dtau of the current table clock
-    const TSAT_GLOBAL real* p0 = tr.bt + (size_t)brow_index(tr, 0, 0.0) * 4;
-    const TSAT_GLOBAL real* p1 = tr.bt + (size_t)brow_index(tr, 0, 0.5) * 4;
-    const TSAT_GLOBAL real* p2 = tr.bt + (size_t)brow_index(tr, 0, 1.0) * 4;
+    // rows at tau, tau + dtau / 2, tau + dtau of the current table clock (index, pointer, index, pointer, ...: with the three
+    // indices taken first the kernel keeps its length but not its register assignment — tools/isa_compare.py)
+    const int i0 = brow_index(tr, 0, 0.0);
+    const TSAT_GLOBAL real* p0 = tr.bt + (size_t)i0 * 4;
+    const int i1 = brow_index(tr, 0, 0.5);
+    const TSAT_GLOBAL real* p1 = tr.bt + (size_t)i1 * 4;
+    const int i2 = brow_index(tr, 0, 1.0);
+    const TSAT_GLOBAL real* p2 = tr.bt + (size_t)i2 * 4;
     const real b0[3] = {p0[0], p0[1], p0[2]}, b1[3] = {p1[0], p1[1], p1[2]}, b2[3] = {p2[0], p2[1], p2[2]};
-    mpc_held_rk4<real>(tp, e, noisy, gid, (int)(a.s.step0 + (long long)s), x, us, b0, b1, b2, xn);
+    mpc_held_rk4<real>(tp, e, noisy, gid, (int)(a.s.step0 + (long long)s), x, us, b0, b1, b2, env, i0, i1, i2, xn);
     for (int i = 0; i < 7; ++i) { hx[(size_t)j * 7 + i] = x[i]; x[i] = xn[i]; }
     for (int c = 0; c < 3; ++c) hu[(size_t)j * 3 + c] = uc[c];   // the limited command, units of u_scale
     tr.tau0 = tr.tau0 + tr.dtau;

@@ -36,6 +36,16 @@ def magnetic_simulation(solver, kep, t0, tf, N, mjd=58155.0, gm=3.986004418e5, a
     return B, pos
 
 
+def orbit_rows(pos, n_tab):
+    """The orbit table ``Rtab`` (n_btab, n_tab, 3) of the gravity-gradient entry points (``tracking.attitude_ensemble_gg``,
+    ``mpc.receding_horizon_held_gg``) from the ``pos`` (T, 2N+1, 3) km that ``magnetic_simulation`` returns: its first ``n_tab``
+    rows — row i is the position at which field row i was evaluated, so the table is indexed like ``Btab[:, :n_tab]``."""
+    pos = np.asarray(pos, dtype=np.float64)
+    if pos.ndim != 3 or pos.shape[2] != 3 or not 1 <= int(n_tab) <= pos.shape[1]:
+        raise ValueError("pos must be (T, rows, 3) with rows >= n_tab >= 1")
+    return np.ascontiguousarray(pos[:, :int(n_tab)])
+
+
 def attach_igrf_tables(solver, batch, kep=None, chunk=4096):
     """Replace the field tables of a workload batch by IGRF-12 tables generated on the GPU for its orbits — what the
     reference does before every solve (``magnetic_simulation(A[i,:], t0, t_final, N, ...)``, src/monte_carlo.jl:149): one

@@ -51,8 +51,10 @@ def _noise_options(lib, noise_opts):
     return po
 
 
-def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload):
-    """``tsat_mpc_run_dispersed`` (``replan_every`` None) or ``tsat_mpc_run_held`` on ``prob``: marshalling of both"""
+def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
+                gravity=None):
+    """``tsat_mpc_run_dispersed`` (``replan_every`` None), ``tsat_mpc_run_held`` or — with ``gravity`` = (Rtab, gm) —
+    ``tsat_mpc_run_held_gg`` on ``prob``: marshalling of all three"""
     lib = _abi.load()
     b = prob.arrays
     o = solver.opts.to_abi(b.N, b.n_tab, prob.integrator, prob.terminal_mask, error_state=prob.error_state)
@@ -83,7 +85,12 @@ def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise
     head = (solver._h, C.byref(o), C.byref(po), int(n_steps), int(step0))
     tail = (d(plant), d(lo), d(hi), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int64)), d(Xh), d(Uh),
             st.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p), _abi.as_ip(ncl), C.byref(ms))
-    if replan_every is None:
+    if gravity is not None:
+        from .tracking import orbit_table
+        Rtab = orbit_table(b, gravity[0])
+        solver._check(lib.tsat_mpc_run_held_gg(*head, int(replan_every), int(feedback), *tail, d(Rtab), float(gravity[1])),
+                      "tsat_mpc_run_held_gg")
+    elif replan_every is None:
         solver._check(lib.tsat_mpc_run_dispersed(*head, *tail), "tsat_mpc_run_dispersed")
     else:
         solver._check(lib.tsat_mpc_run_held(*head, int(replan_every), int(feedback), *tail), "tsat_mpc_run_held")
@@ -113,6 +120,19 @@ def receding_horizon_held(prob, solver, n_steps, replan_every, feedback=True, pl
     the first call's ``n_steps`` is a multiple of ``replan_every``. Returns the dict of ``receding_horizon_dispersed`` plus
     ``n_solves`` = ceil(n_steps / replan_every)."""
     r = _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload)
+    r["n_solves"] = -(-int(n_steps) // int(replan_every))
+    return r
+
+
+def receding_horizon_held_gg(prob, solver, n_steps, replan_every, Rtab, gm=3.986004418e5, feedback=True, plant=None, sat=None,
+                             noise_opts=None, noise_id=None, step0=0, max_outer=1, max_inner=3, upload=True):
+    """``receding_horizon_held`` under gravity-gradient torque (``tsat_mpc_run_held_gg``): every plant step also feels
+    3 gm / |r|^3 (r_b x Jp r_b) with the trajectory's own inertia; the solve does not see it. ``Rtab`` (n_btab, n_tab, 3) km holds
+    the orbit position of every field row of the batch (``magnetic.orbit_rows``) and follows its ``btab_idx`` — so it is shared by
+    the realisations of ``tile_realisations`` as the field tables are; ``gm`` in km^3 / s^2, 0 switches the term off.
+    ``replan_every=1`` is the every-step loop under gravity gradient."""
+    r = _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
+                    gravity=(Rtab, gm))
     r["n_solves"] = -(-int(n_steps) // int(replan_every))
     return r
 

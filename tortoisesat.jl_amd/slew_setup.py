@@ -169,6 +169,20 @@ def dipole_btable(n_tab, dt_row, a_km, inc_deg, raan_deg=0.0, nu_deg=0.0):
     return np.ascontiguousarray(B @ Rz.T)
 
 
+def circular_orbit_rows(n_tab, dt_row, a_km, inc_deg, raan_deg=0.0, nu_deg=0.0):
+    """(n_tab, 3) orbit positions in km, ECI, of the circular orbit ``dipole_btable`` samples its field on, row for row:
+    r(t) = Rz(RAAN) a [cos(w0 t + nu); sin(w0 t + nu) cos i; sin(w0 t + nu) sin i]. The orbit table of the gravity-gradient
+    entry points (``tracking.attitude_ensemble_gg``) for a workload on synthetic tables; with IGRF tables it is
+    ``magnetic.orbit_rows`` of the propagated positions."""
+    w0 = np.sqrt(GM_EARTH / (a_km * 1000.0)**3)
+    inc = np.deg2rad(inc_deg)
+    ph = w0 * dt_row * np.arange(n_tab) + np.deg2rad(nu_deg)
+    r = a_km * np.stack([np.cos(ph), np.sin(ph) * np.cos(inc), np.sin(ph) * np.sin(inc)], axis=1)
+    c, s = np.cos(np.deg2rad(raan_deg)), np.sin(np.deg2rad(raan_deg))
+    Rz = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    return np.ascontiguousarray(r @ Rz.T)
+
+
 # --------------------------------------------------------------------------------------------------
 # batch container
 # --------------------------------------------------------------------------------------------------

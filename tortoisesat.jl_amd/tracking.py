@@ -298,3 +298,41 @@ def attitude_ensemble_dispersed(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd,
     if rc != 0:
         raise RuntimeError(f"tsat_tvlqr_ensemble_dispersed failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
     return dict(out, n_clipped=ncl)
+
+
+GM_EARTH = 3.986004418e5    # km^3 / s^2
+
+
+def orbit_table(batch, Rtab):
+    """``Rtab`` as the C ABI takes it: (n_btab, n_tab, 3) float64, km, the shape of ``batch.Btab``"""
+    Rtab = np.ascontiguousarray(Rtab, dtype=np.float64)
+    if Rtab.shape != (batch.Btab.shape[0], batch.n_tab, 3):
+        raise ValueError("Rtab must be (n_btab, n_tab, 3): one orbit position per field row")
+    return Rtab
+
+
+def attitude_ensemble_gg(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant, Rtab, gm=GM_EARTH, sat=None,
+                         noise_id0=None, sigma_scale=1.0, want_K=False, want_trajectories=False, linearize_dt_sq=True, u_scale=1e-2,
+                         min_steps=10, w_tol=0.05, angle_tol=0.08727):
+    """``attitude_ensemble_dispersed`` under gravity-gradient torque (``tsat_tvlqr_ensemble_gg``): every realisation also feels
+    3 gm / |r|^3 (r_b x Jp r_b) with its own inertia Jp, r_b the orbit position in the body frame — a disturbance neither the plan
+    nor the gains know of. ``Rtab`` (n_btab, n_tab, 3) km holds the orbit position of every field row (``magnetic.orbit_rows``)
+    and follows ``batch.btab_idx``; ``gm`` in km^3 / s^2, 0 switches the term off (then the result is that of
+    ``attitude_ensemble_dispersed`` bit for bit). ``nominal`` is the noise-free MODEL plant in the same gravity field."""
+    lib, head, tail, out = _ensemble_call(solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, noise_id0, sigma_scale, want_K,
+                                          want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol)
+    T, M = out["stats"].shape
+    c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    plant = c(plant)
+    if plant.shape != (T, M, PLANT_W):
+        raise ValueError("plant must be (T, M, 21)")
+    Rtab = orbit_table(batch, Rtab)
+    lo = hi = None
+    if sat is not None:
+        lo, hi = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in sat)
+    ncl = np.zeros((T, M), dtype=np.int32)
+    d = _abi.as_dp
+    rc = lib.tsat_tvlqr_ensemble_gg(*head, d(plant), d(lo), d(hi), *tail, _abi.as_ip(ncl), d(Rtab), float(gm))
+    if rc != 0:
+        raise RuntimeError(f"tsat_tvlqr_ensemble_gg failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
+    return dict(out, n_clipped=ncl)
