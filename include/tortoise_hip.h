@@ -396,6 +396,56 @@ int  tsat_tvlqr_ensemble_gg(tsat_handle* h, const tsat_tvlqr_options* o, int64_t
                          tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
                          double* K_lqr, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm);
 
+/* The PROJECTION PD LAW on the plants of tsat_tvlqr_ensemble_gg: the baseline the tracked plans are compared against — the
+ * feedback every magnetorquer satellite carries needs no plan, no gains, no Jacobian pass and no Riccati recursion. The
+ * reference's form of it: psiaki_controller (src/comparison/psiaki_dynamics.jl:1-26), flown around a reference trajectory by
+ * src/comparison/psiaki2005.jl:139-164, with the direction-preserving limit nominal_input_psiaki (psiaki_dynamics.jl:127-143).
+ * Those scripts are experimental; this is the law as defined HERE (deviations: their rate term has the opposite sign of their
+ * attitude term, their q~ = q (x) q_guess has no inverse, they have no shortest-rotation rule, inv(J) is folded into kp here,
+ * and their m_limit is an unused argument).
+ * At knot k, x the realisation's current TRUE state (as the TVLQR feedback sees it), xr the reference record of the knot:
+ *   dw      = x[0:3] - xr[0:3]
+ *   e       = conj(xr[3:7]) (x) x[3:7]                 the product of the TVLQR feedback, with its scalar part e0
+ *   s       = (e0 < 0) ? -1 : 1                        shortest rotation
+ *   Treq[c] = -(kd[c] dw[c] + kp[c] (s e[1+c]))        N m
+ *   b       = qrot(x[3:7] / |x[3:7]|, field row floor(fma(k, dtau, tau0)) clamped)     the stage-0 row, no noise
+ *   m       = (b x Treq) / (b . b)                     A m^2;  m = 0 when b . b == 0 (the last row of a magnetic_simulation
+ *                                                      table is zero, and the clock clamps onto it)
+ *   u_cmd   = (feedforward ? U_k : 0) + m / o->u_scale        units of u_scale, as every command of this ABI
+ * then the limit:
+ *   limit_mode 0   the component clip of tsat_tvlqr_ensemble_dispersed
+ *   limit_mode 1   beta = max_c r_c, r_c = u_c / hi_c if u_c > 0, u_c / lo_c if u_c < 0, 0 if u_c == 0; if beta > 1 every component
+ *                  becomes u_c (1 / beta) (the direction is kept), otherwise the command is unchanged
+ * a knot counts as clipped when the limit changed any component; after it G u_sat + m_res / u_scale is held over the four RK4
+ * stages. Everything not named below keeps its meaning, shape, layout and validation from tsat_tvlqr_ensemble_gg: the plant
+ * record, the draw layout and its per-stage injection, the RK4 plant, the table clock, the gravity-gradient term, the statistic
+ * evaluated while the roll-out runs, summary, ragged n_knots, zero fill beyond a horizon. Of `o`, noise_mode must be 1 and
+ * rate_as_written 0; linearize_dt_sq is ignored.
+ *   X      7 x N x T or NULL       reference record of knot k = X[:,k,t]; NULL = REGULATION: the record of every knot is xf[:,t],
+ *                                  and nothing of size N is uploaded (N = 100 000 costs no device memory beyond X_sim, if asked for)
+ *   U      3 x (N-1) x T           read only when feedforward = 1; may be NULL otherwise
+ *   kd, kp 3 x T each              per-axis rate gain (N m s / rad) and attitude gain (N m), finite and >= 0; the reference's
+ *                                  form is kp = C2 / J_ii
+ *   feedforward  0 | 1             limit_mode  0 | 1
+ *   x0_nom 7 x T or NULL           start of the noise-free MODEL plant of stats_nominal; NULL = X[:,1,t]
+ *   plant  21 x M x T or NULL      NULL: every realisation flies the model's plant (Jmat as the symmetric tensor of its upper
+ *                                  triangle, G = I, m_res = 0), as in tsat_mpc_run_dispersed
+ *   Rtab   may be NULL only with gm == 0: then the kernel without the gravity rows is launched; with Rtab the one with them,
+ *                                  whatever gm is (gm = 0 gives the same states bit for bit)
+ * Rejected with -1 (text in tsat_ensemble_last_error; nothing is launched and no workspace grows): kd or kp NULL, non-finite or
+ * negative; feedforward not 0 or 1; feedforward = 1 with X or U NULL; limit_mode not 0 or 1; limit_mode = 1 with the limits NULL
+ * or without lo < 0 < hi in every component; X NULL with stats_nominal non-NULL and x0_nom NULL; Rtab NULL with gm != 0; and
+ * everything tsat_tvlqr_ensemble_gg rejects except the NULL plant and NULL Rtab above. */
+int  tsat_pd_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat,
+                         const double* kd, const double* kp, int32_t feedforward, int32_t limit_mode,
+                         const double* x0_sim, const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* X_sim, int32_t* n_clipped, const double* Rtab, double gm);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Receding-horizon re-solve on the RESIDENT batch (BASELINE.json configs[4]). NOT in the reference —
  * it tracks its plan with TVLQR (src/attitude_controller.jl:1-48); defined here as: n_steps times

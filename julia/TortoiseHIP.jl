@@ -403,6 +403,47 @@ function attitude_ensemble_gg(s::HIPSolver, p::BatchProblem, x0_lqr::Array{Float
 end
 
 """
+attitude_ensemble_pd(s, p, x0_lqr, kd, kp; X, U, plant, Rtab, gm, sat_lo, sat_hi, limit_mode, x0_nom, noise_id0, opts,
+want_trajectories) — `tsat_pd_ensemble`: the projection PD law (the reference's src/comparison/psiaki_dynamics.jl:1-26, as
+include/tortoise_hip.h defines it) on the plants of `attitude_ensemble_gg` — the baseline a tracked plan is compared against.
+kd, kp 3 x T (N m s / rad, N m). X 7 x N x T is the reference trajectory to track (empty: regulate to `p.xf`, nothing of size N
+is uploaded), U 3 x (N-1) x T its feed-forward (empty: the law alone). plant 21 x M x T (empty: the model's plant), Rtab as for
+`attitude_ensemble_gg` (empty, with gm = 0: no gravity rows). limit_mode 0 clips per component, 1 keeps the direction.
+x0_nom 7 x T starts the noise-free model plant (empty: X[:,1,t]). Returns (stats M x T, summary 8 x T, nominal T, X_sim or
+nothing, n_clipped M x T).
+"""
+function attitude_ensemble_pd(s::HIPSolver, p::BatchProblem, x0_lqr::Array{Float64,3}, kd::Matrix{Float64}, kp::Matrix{Float64};
+                              X::Array{Float64,3} = zeros(7, 0, 0), U::Array{Float64,3} = zeros(3, 0, 0),
+                              plant::Array{Float64,3} = zeros(21, 0, 0), Rtab::Array{Float64,3} = zeros(3, 0, 0), gm::Float64 = 0.0,
+                              sat_lo::Matrix{Float64} = zeros(3, 0), sat_hi::Matrix{Float64} = zeros(3, 0), limit_mode::Integer = 0,
+                              x0_nom::Matrix{Float64} = zeros(7, 0), noise_id0::Vector{Int64} = Int64[],
+                              opts::TvlqrOptions = TvlqrOptions(noise_mode = 1), want_trajectories::Bool = false)
+    T = size(p.x0, 2); N = p.N; M = size(x0_lqr, 2)
+    size(kd) == (3, T) && size(kp) == (3, T) || error("kd and kp must be 3 x T")
+    isempty(X) || size(X) == (7, N, T) || error("X must be 7 x N x T")
+    isempty(U) || size(U) == (3, N - 1, T) || error("U must be 3 x (N-1) x T")
+    isempty(plant) || size(plant) == (21, M, T) || error("plant must be 21 x M x T")
+    isempty(Rtab) || size(Rtab) == size(p.B_ECI) || error("Rtab must have the shape of B_ECI: 3 x n_tab x n_btab")
+    opts.n_knots = N; opts.n_tab = size(p.B_ECI, 2)
+    st = Matrix{TvlqrStats}(undef, M, T); nominal = Vector{TvlqrStats}(undef, T); summary = zeros(8, T)
+    n_clipped = zeros(Int32, M, T)
+    Xs = want_trajectories ? zeros(7, N, M, T) : nothing
+    rc = ccall((:tsat_pd_ensemble, LIB), Cint,
+        (Ptr{Cvoid}, Ref{TvlqrOptions}, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64},
+         Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{TvlqrStats}, Ptr{Float64}, Ptr{TvlqrStats},
+         Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Float64),
+        s.handle, opts, T, size(p.B_ECI, 3), M, isempty(X) ? C_NULL : X, isempty(U) ? C_NULL : U, p.xf, p.B_ECI, p.btab_idx,
+        p.tau0, p.dtau, p.dt, p.J, kd, kp, isempty(U) ? 0 : 1, limit_mode, x0_lqr, isempty(x0_nom) ? C_NULL : x0_nom,
+        isempty(noise_id0) ? C_NULL : noise_id0, isempty(p.n_knots) ? C_NULL : p.n_knots,
+        isempty(plant) ? C_NULL : plant, isempty(sat_lo) ? C_NULL : sat_lo, isempty(sat_hi) ? C_NULL : sat_hi,
+        st, summary, isempty(X) && isempty(x0_nom) ? C_NULL : nominal, Xs === nothing ? C_NULL : Xs, n_clipped,
+        isempty(Rtab) ? C_NULL : Rtab, gm)
+    rc == 0 || error("tsat_pd_ensemble failed ($rc): " * unsafe_string(ccall((:tsat_ensemble_last_error, LIB), Cstring, ())))
+    return st, summary, nominal, Xs, n_clipped
+end
+
+"""
 receding_horizon!(s, p, n_steps; plant_integrator = 4) — `tsat_mpc_run` on the batch `p` (uploaded here): re-solve the
 horizon every control step with the budget of `s.opts`, apply U[:,1] to the noise-free plant, shift the plan.
 No reference equivalent (BASELINE.json configs[4]). Returns X_hist 7×(n_steps+1)×T, U_hist 3×n_steps×T.

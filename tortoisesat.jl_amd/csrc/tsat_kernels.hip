@@ -201,6 +201,8 @@ int dev_alloc(tsat_handle* h, Tp** p, size_t n) {
 // the packed gravity rows of the gravity-gradient entry points: the handle's grow-only slot, for the ensemble's translation
 // unit too (to which `struct tsat_handle` is opaque); nullptr on failure
 double* tsat_ws_gravity(tsat_handle* h, size_t bytes) { return (double*)ws_get(h, tsat_handle::WS_GG_GT, bytes); }
+// the handle's GPU, for an entry point of that unit which makes no call into this one before it allocates (tsat_pd_ensemble)
+int tsat_handle_device(const tsat_handle* h) { return h->dev; }
 
 extern "C" {
 

@@ -19,6 +19,10 @@
 // (tsat_gg.hpp): the host validates the orbit table, a pack kernel turns it into gravity rows in a grow-only workspace of the
 // handle, and step 4 launches the kernel of tsat_kernels_gg.hip. Steps 1-3 and 5 are one piece of code for all entry points
 // (run_ensemble).
+//
+// tsat_pd_ensemble (tsat_pd.hpp) flies the projection PD law on the same plants (run_pd): no step 1 and no step 3 — there are no
+// gains —, the plan goes up only when the call tracks one (X == NULL regulates to xf and uploads nothing of size N), the plant
+// pack and the gravity-row pack are the ones above, and step 4 launches a kernel of tsat_kernels_pd.hip.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -29,6 +33,7 @@
 #include "tsat_ensemble.hpp"
 #include "tsat_dispersed.hpp"
 #include "tsat_gg.hpp"
+#include "tsat_pd.hpp"
 
 using namespace tsat;
 
@@ -37,6 +42,9 @@ using namespace tsat;
 hipError_t tsat_launch_gg_pack(const double* R, double gm, double* GT, int64_t rows, hipStream_t stream);
 hipError_t tsat_launch_ensemble_gg(const GgEnsArgs<double>& g, int waves, hipStream_t stream);
 double* tsat_ws_gravity(tsat_handle* h, size_t bytes);
+// roll-out of tsat_pd_ensemble (tsat_kernels_pd.hip); the handle's GPU (tsat_kernels.hip)
+hipError_t tsat_launch_pd(const PdArgs<double>& a, int waves, hipStream_t stream);
+int tsat_handle_device(const tsat_handle* h);
 
 template <typename real, int DIAGJ>
 __global__ __launch_bounds__(64) void tsat_ensemble_kernel(EnsArgs<real> a) {
@@ -327,9 +335,148 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   return 0;
 }
 
+// tsat_pd_ensemble: steps 2, 4 and 5 of run_ensemble around the kernels of tsat_kernels_pd.hip
+int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X, const double* U,
+           const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau, const double* dt,
+           const double* Jmat, const double* kd, const double* kp, int32_t feedforward, int32_t limit_mode, const double* x0_sim,
+           const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots, const double* plant, const double* sat_lo,
+           const double* sat_hi, tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* X_sim,
+           int32_t* n_clipped, const double* Rtab, double gm) {
+  g_err.clear();
+  if (!h) return efail(-1, "null handle or options");
+  const std::string why = check_pd(o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode,
+                                   x0_sim, x0_nom, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, Rtab, gm);
+  if (!why.empty()) return efail(-1, why);
+#define ENS_HIP(call)                                                                                   \
+  do {                                                                                                  \
+    hipError_t e_ = (call);                                                                             \
+    if (e_ != hipSuccess) return efail(-10, std::string(#call) + ": " + hipGetErrorString(e_));         \
+  } while (0)
+  ENS_HIP(hipSetDevice(tsat_handle_device(h)));
+  const int N = o->n_knots, n_tab = o->n_tab;
+  const size_t Tn = (size_t)T;
+  // ---- 2. upload: the plan only when the call tracks one --------------------------------------------------------------
+  const int nw = ensemble_waves(M), Mp = nw * WAVE;
+  const size_t nX = Tn * N * 7, nU = Tn * (size_t)(N - 1) * 3, nB = (size_t)n_btab * n_tab, nXU = Tn * N * XUW, nS = Tn * (size_t)M,
+               nXS = X_sim ? nS * N * 7 : 0;
+  std::vector<double> P(Tn * PSTRIDE), x0n(Tn * 7), zero(Tn * 6, 0.0), gain(Tn * PDGW), sat(Tn * SATW), model;
+  std::vector<int> bi(Tn);
+  for (size_t t = 0; t < Tn; ++t) {
+    bi[t] = btab_idx ? btab_idx[t] : (int)t;
+    for (int i = 0; i < 7; ++i) x0n[7 * t + i] = x0_nom ? x0_nom[7 * t + i] : (X ? X[t * N * 7 + i] : xf[7 * t + i]);
+    for (int c = 0; c < 3; ++c) {
+      gain[PDGW * t + c] = kd[3 * t + c];
+      gain[PDGW * t + 3 + c] = kp[3 * t + c];
+      sat[SATW * t + c] = sat_lo ? sat_lo[3 * t + c] : -HUGE_VAL;
+      sat[SATW * t + 3 + c] = sat_hi ? sat_hi[3 * t + c] : HUGE_VAL;
+    }
+  }
+  pack_tv_params<double>(T, x0n.data(), xf, tau0, dtau, dt, Jmat, zero.data(), zero.data(), zero.data(), P.data());
+  if (!plant) {   // every realisation flies the model's plant: (Jmat, G = I, m_res = 0); the pack reads the upper triangle of Jp
+    model.assign(nS * TSAT_PLANT_W, 0.0);
+    for (size_t t = 0; t < Tn; ++t)
+      for (int m = 0; m < M; ++m) {
+        double* pl = model.data() + (t * M + m) * TSAT_PLANT_W;
+        for (int i = 0; i < 9; ++i) pl[i] = Jmat[9 * t + i];
+        pl[9] = pl[13] = pl[17] = 1.0;
+      }
+    plant = model.data();
+  }
+  EnsScope s;
+  double *dP = nullptr, *dX = nullptr, *dU = nullptr, *dB = nullptr, *dBT = nullptr, *dXU = nullptr, *dX0 = nullptr, *dX0N = nullptr,
+         *dXS = nullptr, *dGain = nullptr, *dPlant = nullptr, *dPL = nullptr, *dSat = nullptr, *dR = nullptr, *dGT = nullptr;
+  int *dbi = nullptr, *dnk = nullptr, *dClip = nullptr;
+  long long* dnid = nullptr;
+  tsat_tvlqr_stats *dst = nullptr, *dsn = nullptr;
+  bool ok = s.alloc(&dP, P.size()) && s.alloc(&dB, nB * 3) && s.alloc(&dBT, nB * 4) && s.alloc(&dX0, nS * 7) && s.alloc(&dX0N, Tn * 7) &&
+            s.alloc(&dbi, Tn) && s.alloc(&dst, nS) && s.alloc(&dsn, Tn) && s.alloc(&dGain, gain.size()) &&
+            s.alloc(&dPlant, nS * TSAT_PLANT_W) && s.alloc(&dPL, Tn * PLW * (size_t)Mp) && s.alloc(&dSat, sat.size());
+  if (ok && X) ok = s.alloc(&dX, nX) && s.alloc(&dU, nU) && s.alloc(&dXU, nXU);
+  if (ok && n_knots) ok = s.alloc(&dnk, Tn);
+  if (ok && noise_id0) ok = s.alloc(&dnid, Tn);
+  if (ok && X_sim) ok = s.alloc(&dXS, nXS);
+  if (ok && n_clipped) ok = s.alloc(&dClip, nS);
+  if (ok && Rtab) ok = s.alloc(&dR, nB * 3) && (dGT = tsat_ws_gravity(h, nB * 4 * 8)) != nullptr;
+  if (!ok) return efail(-10, "device allocation failed in tsat_pd_ensemble");
+  ENS_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+  for (hipEvent_t& e : s.ev) ENS_HIP(hipEventCreate(&e));
+  ENS_HIP(hipMemcpy(dP, P.data(), P.size() * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dB, Btab, nB * 3 * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dX0, x0_sim, nS * 7 * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dX0N, x0n.data(), x0n.size() * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dbi, bi.data(), Tn * sizeof(int), hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dGain, gain.data(), gain.size() * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dPlant, plant, nS * TSAT_PLANT_W * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dSat, sat.data(), sat.size() * 8, hipMemcpyHostToDevice));
+  if (n_knots) ENS_HIP(hipMemcpy(dnk, n_knots, Tn * sizeof(int), hipMemcpyHostToDevice));
+  if (noise_id0) ENS_HIP(hipMemcpy(dnid, noise_id0, Tn * sizeof(long long), hipMemcpyHostToDevice));
+  if (X) {
+    ENS_HIP(hipMemcpy(dX, X, nX * 8, hipMemcpyHostToDevice));
+    if (feedforward) ENS_HIP(hipMemcpy(dU, U, nU * 8, hipMemcpyHostToDevice));
+    else ENS_HIP(hipMemset(dU, 0, nU * 8));                  // U is not read without feed-forward: the records carry zeros
+    const int64_t n_rec = T * (int64_t)N;
+    hipLaunchKernelGGL(tsat_ensemble_pack_xu_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s.stream, n_rec, N, dX, dU, dXU);
+  }
+  hipLaunchKernelGGL(tsat_ensemble_pack_bt_kernel, dim3((unsigned)((nB + 255) / 256)), dim3(256), 0, s.stream, (int64_t)nB, dB, dBT);
+  ENS_HIP(hipGetLastError());
+  if (n_knots && X_sim) ENS_HIP(hipMemsetAsync(dXS, 0, nXS * 8, s.stream));   // ragged: zero beyond a slew's own horizon
+  {
+    const int64_t n = T * (int64_t)(M + 1);
+    hipLaunchKernelGGL(tsat_dispersed_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, dPlant, dP, o->u_scale, dPL,
+                       T, M, Mp);
+    ENS_HIP(hipGetLastError());
+  }
+  if (Rtab) {
+    ENS_HIP(hipMemcpy(dR, Rtab, nB * 3 * 8, hipMemcpyHostToDevice));
+    ENS_HIP(tsat_launch_gg_pack(dR, gm, dGT, (int64_t)nB, s.stream));
+  }
+  // ---- 4. the roll-out ------------------------------------------------------------------------------------------------
+  ENS_HIP(hipEventRecord(s.ev[0], s.stream));
+  {
+    PdArgs<double> pa;
+    EnsArgs<double>& a = pa.d.e;
+    a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.min_steps = o->min_steps;
+    a.us = o->u_scale; a.w_tol = o->w_tol; a.ang_tol = o->angle_tol;
+    a.P = dP; a.BT = dBT; a.bidx = dbi; a.nk = dnk; a.XUR = dXU; a.KD = nullptr; a.X0 = dX0;
+    a.k0 = (unsigned)(o->noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o->noise_seed >> 32);
+    a.nid0 = dnid; a.sg = o->sigma_gyro; a.sa = o->sigma_att; a.fa = o->field_amp;
+    a.XS = dXS; a.stats = dst; a.stats_nom = dsn;
+    pa.d.PL = dPL; pa.d.Mp = Mp; pa.d.SAT = dSat; pa.d.nclip = dClip;
+    pa.GT = dGT; pa.GAIN = dGain; pa.X0N = dX0N; pa.feedforward = feedforward; pa.limit_mode = limit_mode;
+    ENS_HIP(tsat_launch_pd(pa, nw, s.stream));
+  }
+  ENS_HIP(hipEventRecord(s.ev[1], s.stream));
+  ENS_HIP(hipStreamSynchronize(s.stream));
+  // ---- 5. download ----------------------------------------------------------------------------------------------------
+  ENS_HIP(hipMemcpy(stats, dst, nS * sizeof(tsat_tvlqr_stats), hipMemcpyDeviceToHost));
+  if (stats_nominal) ENS_HIP(hipMemcpy(stats_nominal, dsn, Tn * sizeof(tsat_tvlqr_stats), hipMemcpyDeviceToHost));
+  if (X_sim) ENS_HIP(hipMemcpy(X_sim, dXS, nXS * 8, hipMemcpyDeviceToHost));
+  if (dClip) ENS_HIP(hipMemcpy(n_clipped, dClip, nS * sizeof(int32_t), hipMemcpyDeviceToHost));
+  ensemble_summary(T, M, stats, summary);
+  if (const char* v = std::getenv("TSAT_ENSEMBLE_TIMING")) {   // diagnostic (tools/pd_timing.py): HIP-event time of the roll-out
+    if (v[0] == '1') {
+      float e = 0;
+      (void)hipEventElapsedTime(&e, s.ev[0], s.ev[1]);
+      std::fprintf(stderr, "tsat_pd_ensemble: pd_kernel_ms %.4f\n", e);
+    }
+  }
+#undef ENS_HIP
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int tsat_pd_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                     const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                     const double* dtau, const double* dt, const double* Jmat, const double* kd, const double* kp, int32_t feedforward,
+                     int32_t limit_mode, const double* x0_sim, const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots,
+                     const double* plant, const double* sat_lo, const double* sat_hi, tsat_tvlqr_stats* stats, double* summary,
+                     tsat_tvlqr_stats* stats_nominal, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm) {
+  return run_pd(h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode, x0_sim, x0_nom,
+                noise_id0, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, X_sim, n_clipped, Rtab, gm);
+}
 
 const char* tsat_ensemble_last_error(void) { return g_err.c_str(); }
 

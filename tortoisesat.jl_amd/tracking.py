@@ -336,3 +336,81 @@ def attitude_ensemble_gg(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, no
     if rc != 0:
         raise RuntimeError(f"tsat_tvlqr_ensemble_gg failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
     return dict(out, n_clipped=ncl)
+
+
+def pd_gains(Jmat, wn, zeta):
+    """Per-axis gains of the projection PD law for a closed loop of natural frequency ``wn`` (rad/s) and damping ``zeta`` on the
+    principal moments J_ii of ``Jmat`` ((T, 9) column-major as ``SlewBatch.Jmat``, or (T, 3, 3)); ``wn`` and ``zeta`` scalars or (T,).
+    Returns (kd, kp), each (T, 3): kp = 2 J_ii wn^2 (the vector part of the error quaternion is half the angle), kd = 2 zeta wn J_ii."""
+    Jmat = np.asarray(Jmat, dtype=np.float64)
+    if Jmat.ndim == 2 and Jmat.shape[1] == 9:
+        Jmat = Jmat.reshape(-1, 3, 3)
+    if Jmat.ndim != 3 or Jmat.shape[1:] != (3, 3):
+        raise ValueError("Jmat must be (T, 9) or (T, 3, 3)")
+    Jd = np.stack([Jmat[:, 0, 0], Jmat[:, 1, 1], Jmat[:, 2, 2]], axis=1)
+    wn = np.broadcast_to(np.asarray(wn, dtype=np.float64), (Jd.shape[0],))[:, None]
+    zeta = np.broadcast_to(np.asarray(zeta, dtype=np.float64), (Jd.shape[0],))[:, None]
+    return np.ascontiguousarray(2.0 * zeta * wn * Jd), np.ascontiguousarray(2.0 * Jd * wn * wn)
+
+
+def attitude_ensemble_pd(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X=None, U=None, plant=None, Rtab=None, gm=0.0, sat=None,
+                         limit_mode=0, x0_nom=None, noise_id0=None, want_trajectories=False, sigma_scale=1.0, u_scale=1e-2,
+                         min_steps=10, w_tol=0.05, angle_tol=0.08727):
+    """The projection PD law on the plants of ``attitude_ensemble_gg`` (``tsat_pd_ensemble``): the baseline a tracked plan is
+    compared against — no plan, gains or Riccati pass needed. Per knot T_req = -(kd dw + kp s e), m = (b x T_req) / |b|^2 with dw
+    the rate error, e the vector part of conj(q_ref) (x) q, s the sign of its scalar part and b the body-frame field
+    (include/tortoise_hip.h; the reference's src/comparison/psiaki_dynamics.jl:1-26).
+    ``kd``, ``kp`` (T, 3) or (3,) in N m s / rad and N m (``pd_gains``). ``X`` (T, N, 7) is the trajectory to track, ``None``
+    regulates to ``batch.xf`` over ``batch.N`` knots (nothing of size N goes to the device); ``U`` (T, N-1, 3) adds the plan's
+    feed-forward (needs ``X``). ``plant`` (T, M, 21) or None for the model's plant; ``Rtab``, ``gm`` as ``attitude_ensemble_gg``
+    (``Rtab=None`` needs gm = 0). ``sat`` as ``attitude_ensemble_dispersed``; ``limit_mode`` 0 clips each component, 1 scales the
+    whole command back onto the box (needs lo < 0 < hi). ``x0_nom`` (T, 7) starts the noise-free MODEL plant (default X[:, 0];
+    when regulating without it ``nominal`` is None). Returns dict(stats (T, M), summary (T, 8), nominal (T,) or None, X_sim
+    (T, M, N, 7) or None, n_clipped (T, M))."""
+    lib = _abi.load()
+    T, N = batch.T, batch.N
+    c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    x0_sim = c(x0_sim)
+    if x0_sim.ndim != 3 or x0_sim.shape[0] != T or x0_sim.shape[2] != 7:
+        raise ValueError("x0_sim must be (T, M, 7)")
+    M = x0_sim.shape[1]
+    kd, kp = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in (kd, kp))
+    X, U, plant, x0_nom = c(X), c(U), c(plant), c(x0_nom)
+    if U is not None and X is None:
+        raise ValueError("the feed-forward U needs the trajectory X it belongs to")
+    if (X is not None and X.shape != (T, N, 7)) or (U is not None and U.shape != (T, N - 1, 3)):
+        raise ValueError("array shapes do not match the batch")
+    if plant is not None and plant.shape != (T, M, PLANT_W):
+        raise ValueError("plant must be (T, M, 21)")
+    if x0_nom is not None and x0_nom.shape != (T, 7):
+        raise ValueError("x0_nom must be (T, 7)")
+    if Rtab is not None:
+        Rtab = orbit_table(batch, Rtab)
+    o = _abi.TvlqrOptions()
+    lib.tsat_tvlqr_default_options(C.byref(o))
+    o.n_knots, o.n_tab, o.min_steps = N, batch.n_tab, int(min_steps)
+    o.u_scale, o.w_tol, o.angle_tol = float(u_scale), float(w_tol), float(angle_tol)
+    o.noise_mode, o.noise_seed = 1, int(noise_seed)
+    o.sigma_gyro, o.sigma_att = o.sigma_gyro * float(sigma_scale), o.sigma_att * float(sigma_scale)
+    id0 = None if noise_id0 is None else np.ascontiguousarray(noise_id0, dtype=np.int64)
+    if id0 is not None and id0.shape != (T,):
+        raise ValueError("noise_id0 must be (T,)")
+    nk = None if batch.n_knots is None else np.ascontiguousarray(batch.n_knots, dtype=np.int32)
+    lo = hi = None
+    if sat is not None:
+        lo, hi = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in sat)
+    st = np.zeros((T, M), dtype=_abi.TVLQR_STATS_DTYPE)
+    nom = np.zeros(T, dtype=_abi.TVLQR_STATS_DTYPE) if (X is not None or x0_nom is not None) else None
+    summary = np.zeros((T, 8))
+    Xs = np.empty((T, M, N, 7)) if want_trajectories else None
+    ncl = np.zeros((T, M), dtype=np.int32)
+    d = _abi.as_dp
+    rc = lib.tsat_pd_ensemble(solver._h, C.byref(o), T, batch.Btab.shape[0], M, d(X), d(U), d(batch.xf), d(batch.Btab),
+                              _abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat), d(kd), d(kp),
+                              0 if U is None else 1, int(limit_mode), d(x0_sim), d(x0_nom),
+                              None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), _abi.as_ip(nk), d(plant), d(lo), d(hi),
+                              st.ctypes.data_as(C.c_void_p), d(summary), None if nom is None else nom.ctypes.data_as(C.c_void_p), d(Xs),
+                              _abi.as_ip(ncl), d(Rtab), float(gm))
+    if rc != 0:
+        raise RuntimeError(f"tsat_pd_ensemble failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
+    return dict(stats=st, summary=summary, nominal=nom, X_sim=Xs, n_clipped=ncl)
