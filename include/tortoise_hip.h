@@ -446,6 +446,67 @@ int  tsat_pd_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, in
                          tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
                          double* X_sim, int32_t* n_clipped, const double* Rtab, double gm);
 
+/* The ensemble controllers fed MEASUREMENTS: every closed loop above commands from the realisation's TRUE state — a perfect
+ * attitude solution, a perfect gyro, a perfect magnetometer. The two calls below are tsat_tvlqr_ensemble_gg and tsat_pd_ensemble
+ * with the feedback reading a biased, noisy, optionally one-knot-old measurement instead. The reference's noise figures ARE
+ * sensor figures — a gyro figure of 0.38 deg and an attitude figure of 1 deg (src/simulator.jl:5,10), which it squares and injects
+ * into the dynamics —; read UN-SQUARED, sigma_gyro = 0.38 pi / 180 rad/s and sigma_att = pi / 180 rad are the levels
+ * examples/sensed_slew.py flies. No estimator or filter: the law sees the raw measurement.
+ *   sigma_gyro  rad/s             sigma_att  rad (rotation vector)             sigma_mag  units of Btab
+ *   latency     0: the command of knot k is computed from y_k; 1: from y_max(k-1, 0). The reference record (and U_k) stay knot k's.
+ * tsat_sensor_default_options fills the ideal sensor: all zero.
+ *   sensor  9 x M x T or NULL (zeros)   per realisation: gyro bias bw (3, rad/s), attitude-sensor bias ba (3, rotation vector,
+ *                                       rad, body frame), magnetometer bias bm (3, units of Btab)
+ * Knot k of realisation (t, m), true state x, generator id gid, key o->noise_seed. The draw layout documented at
+ * tsat_tvlqr_options is used at two stage indices the plant never uses: stage 4 — counters (gid lo, gid hi, k, 16 + j) — gives n_w
+ * (its gyro triple, at the sensor's sigma_gyro) and n_a (its attitude triple, at the sensor's sigma_att); stage 5 — counter
+ * (..., k, 20) — gives n_m (its gyro triple, at sigma_mag). The measurement y_k:
+ *   w_m = x[0:3] + bw + n_w
+ *   phi = ba + n_a;  th = |phi|;  dq = [cos(th/2); phi * (th == 0 ? 1/2 : sin(th/2)/th)]
+ *   q_m = x[3:7] (x) dq                                    not normalised: the TVLQR feedback uses x[3:7] raw
+ *   b_m = qrot(x[3:7] / |x[3:7]|, field row floor(fma(k, dtau, tau0)) clamped) + bm + n_m       the TRUE body field, as a
+ *                                                                                                magnetometer reads it
+ * TVLQR law:  dX = [w_m - xr[0:3]; vec(conj(xr[3:7]) (x) q_m)],  u_cmd = U_k - K_k dX
+ * PD law:     dw, e and the sign rule from (w_m, q_m), b = b_m, m = 0 where b_m . b_m == 0
+ * Everything after u_cmd is the parent's: the limit rule, G u_sat + m_res / u_scale held over four stages, the plant draws of
+ * stages 0..3 and their injection, the gravity-gradient term, the table clock, the statistic evaluated on the TRUE state, X_sim
+ * (true states), n_clipped, summary, ragged n_knots, zero fill. stats_nominal flies the noise-free model plant with the IDEAL
+ * sensor (no draws, zero biases) at the call's latency. With sensor NULL or zero, zero sigmas and latency 0 the measurement is the
+ * state (x + 0 + 0 z, x (x) (1,0,0,0) and b + 0 + 0 z are exact) and the calls repeat their parents.
+ * tsat_tvlqr_ensemble_sensed also allows plant == NULL (every realisation flies the model's plant) and Rtab == NULL with gm == 0
+ * (the kernel without the gravity rows), as tsat_pd_ensemble does.
+ * Rejected with -1 (text in tsat_ensemble_last_error; nothing is launched and no workspace grows): s NULL; a sigma non-finite or
+ * negative; latency not 0 or 1; a non-finite sensor entry (the text carries (t, m)); and everything the parent rejects. */
+struct tsat_sensor_options {
+  double  sigma_gyro;
+  double  sigma_att;
+  double  sigma_mag;
+  int32_t latency;
+  int32_t reserved;         /* 0 */
+};
+typedef struct tsat_sensor_options tsat_sensor_options;
+#define TSAT_SENSOR_W 9
+void tsat_sensor_default_options(tsat_sensor_options* s);
+int  tsat_tvlqr_ensemble_sensed(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                         const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* K_lqr, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor);
+int  tsat_pd_ensemble_sensed(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat,
+                         const double* kd, const double* kp, int32_t feedforward, int32_t limit_mode,
+                         const double* x0_sim, const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Receding-horizon re-solve on the RESIDENT batch (BASELINE.json configs[4]). NOT in the reference —
  * it tracks its plan with TVLQR (src/attitude_controller.jl:1-48); defined here as: n_steps times

@@ -70,6 +70,15 @@ class BtableOptions(C.Structure):
                 ("r_igrf_km", C.c_double), ("date", C.c_double)]
 
 
+class SensorOptions(C.Structure):
+    """``tsat_sensor_options`` — what the feedback of the sensed ensembles sees of the state (all zero: the ideal sensor)."""
+
+    _fields_ = [("sigma_gyro", C.c_double), ("sigma_att", C.c_double), ("sigma_mag", C.c_double), ("latency", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+assert C.sizeof(SensorOptions) == 32
+
 TVLQR_STATS_DTYPE = np.dtype([("slew_index", "<i4"), ("failed", "<i4"), ("slew_time", "<f8"), ("final_w_norm", "<f8"),
                               ("final_angle", "<f8")])
 assert TVLQR_STATS_DTYPE.itemsize == 32
@@ -140,6 +149,13 @@ PROTOTYPES = {
     "tsat_pd_ensemble": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp, _ip,
                                    _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp,
                                    C.c_void_p, _dp, C.c_void_p, _dp, _ip, _dp, C.c_double]),
+    "tsat_sensor_default_options": (None, [C.POINTER(SensorOptions)]),
+    "tsat_tvlqr_ensemble_sensed": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp,
+                                             _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp,
+                                             C.c_void_p, _dp, C.c_void_p, _dp, _dp, _ip, _dp, C.c_double, C.POINTER(SensorOptions), _dp]),
+    "tsat_pd_ensemble_sensed": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp, _ip,
+                                          _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp,
+                                          _dp, C.c_void_p, _dp, C.c_void_p, _dp, _ip, _dp, C.c_double, C.POINTER(SensorOptions), _dp]),
 }
 
 LIB_NAME = "libtortoise_hip.so"

@@ -86,10 +86,34 @@ struct ModelPlant {
   TSAT_DEV void store(size_t) const {}
 };
 
-// One closed loop per lane: realisation 64 wave + lane of slew traj on the plant `plant` (the choice is a template argument:
-// nothing in the loop asks which entry point it serves).
-template <typename real, typename Plant>
-TSAT_DEV void ensemble_rollout(const EnsArgs<real>& a, Plant& plant, int traj, int wave) {
+// What the LAW sees of the lane's state, as a plant type answers what the plant is. TrueState: the state itself (`state`) and
+// the stage-0 field row in the body frame of the true attitude (`field`, used by the PD law of tsat_pd.hpp) — every entry point
+// but the sensed ones (Sensed of tsat_sensed.hpp: biases, noise and a one-knot delay). `load` is called once per lane after the
+// plant's; gid, k and noisy name the realisation's generator id, the knot and whether the lane draws noise at all.
+struct TrueState {
+  TSAT_DEV void load(int, int) {}
+  template <typename real>
+  TSAT_DEV void state(long long, int, bool, const real x[7], real y[7]) {
+    for (int i = 0; i < 7; ++i) y[i] = x[i];
+  }
+  // B = qrot(x[3:7] / |x[3:7]|, b0) = b0 + 2 v x (v x b0 + s b0), as dyn_h rotates it
+  template <typename real>
+  TSAT_DEV void field(long long, int, bool, const real x[7], const real b0[3], real B[3]) {
+    const real rn = rsqrt_<real>(x[3] * x[3] + x[4] * x[4] + x[5] * x[5] + x[6] * x[6]);
+    const real q0 = x[3] * rn, q1 = x[4] * rn, q2 = x[5] * rn, q3 = x[6] * rn;
+    const real c0 = (q2 * b0[2] - q3 * b0[1]) + q0 * b0[0];
+    const real c1 = (q3 * b0[0] - q1 * b0[2]) + q0 * b0[1];
+    const real c2 = (q1 * b0[1] - q2 * b0[0]) + q0 * b0[2];
+    B[0] = b0[0] + 2 * (q2 * c2 - q3 * c1);
+    B[1] = b0[1] + 2 * (q3 * c0 - q1 * c2);
+    B[2] = b0[2] + 2 * (q1 * c1 - q2 * c0);
+  }
+};
+
+// One closed loop per lane: realisation 64 wave + lane of slew traj on the plant `plant`, the feedback reading `sensor` (the
+// choices are template arguments: nothing in the loop asks which entry point it serves).
+template <typename real, typename Plant, typename Sensor = TrueState>
+TSAT_DEV void ensemble_rollout(const EnsArgs<real>& a, Plant& plant, int traj, int wave, Sensor sensor = Sensor()) {
   constexpr int DIAGJ = Plant::DIAGJ;
   const int lane = TSAT_LANE();
   const int NS = a.N, n_tab = a.n_tab, M = a.M;
@@ -106,6 +130,7 @@ TSAT_DEV void ensemble_rollout(const EnsArgs<real>& a, Plant& plant, int traj, i
   const TSAT_CONSTMEM real* bt = (const TSAT_CONSTMEM real*)(a.BT + (size_t)a.bidx[traj] * n_tab * 4);
   const Traj<real> tr = ensemble_traj<real>(Pc, a.us, N, n_tab);
   plant.load(tr, traj, r);
+  sensor.load(traj, r);
   const Traj<real>& tp = plant.traj(tr);                       // what dyn_sim_h reads
   const long long gid = (a.nid0 ? a.nid0[traj] : (long long)traj * (long long)M) + (long long)r;
   TSAT_GLOBAL real* xs = (a.XS && live && noisy) ? (TSAT_GLOBAL real*)(a.XS + ((size_t)traj * M + r) * NS * 7) : nullptr;
@@ -130,13 +155,14 @@ TSAT_DEV void ensemble_rollout(const EnsArgs<real>& a, Plant& plant, int traj, i
       for (int i = 0; i < 7; ++i) xs[(size_t)k * 7 + i] = x[i];
     const TSAT_CONSTMEM real* xr = xu + (size_t)k * XUW;
     const TSAT_CONSTMEM real* kd = kdg + (size_t)k * KDW;
-    real dX[6];
-    for (int i = 0; i < 3; ++i) dX[i] = x[i] - xr[i];
+    real y[7], dX[6];                                          // y: what the feedback sees of x
+    sensor.state(gid, k, noisy, x, y);
+    for (int i = 0; i < 3; ++i) dX[i] = y[i] - xr[i];
     {  // vector part of q_ref^-1 (x) q_sim  (src/attitude_controller.jl:42)
       const real s1 = xr[3], a1 = -xr[4], a2 = -xr[5], a3 = -xr[6];
-      dX[3] = s1 * x[4] + x[3] * a1 + (a2 * x[6] - a3 * x[5]);
-      dX[4] = s1 * x[5] + x[3] * a2 + (a3 * x[4] - a1 * x[6]);
-      dX[5] = s1 * x[6] + x[3] * a3 + (a1 * x[5] - a2 * x[4]);
+      dX[3] = s1 * y[4] + y[3] * a1 + (a2 * y[6] - a3 * y[5]);
+      dX[4] = s1 * y[5] + y[3] * a2 + (a3 * y[4] - a1 * y[6]);
+      dX[5] = s1 * y[6] + y[3] * a3 + (a1 * y[5] - a2 * y[4]);
     }
     real uc[3], us[3];
     for (int c = 0; c < 3; ++c) {

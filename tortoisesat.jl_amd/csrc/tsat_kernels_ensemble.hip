@@ -23,6 +23,10 @@
 // tsat_pd_ensemble (tsat_pd.hpp) flies the projection PD law on the same plants (run_pd): no step 1 and no step 3 — there are no
 // gains —, the plan goes up only when the call tracks one (X == NULL regulates to xf and uploads nothing of size N), the plant
 // pack and the gravity-row pack are the ones above, and step 4 launches a kernel of tsat_kernels_pd.hip.
+//
+// tsat_tvlqr_ensemble_sensed and tsat_pd_ensemble_sensed (tsat_sensed.hpp) are run_ensemble and run_pd with a `Sensing`: the host
+// validates the sensor options and biases (check_sensor), a pack kernel lays the biases out per lane, and step 4 launches a kernel
+// of tsat_kernels_sensed.hip. The TVLQR one also takes the model's plant for a NULL plant and no gravity rows for a NULL Rtab.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -34,6 +38,7 @@
 #include "tsat_dispersed.hpp"
 #include "tsat_gg.hpp"
 #include "tsat_pd.hpp"
+#include "tsat_sensed.hpp"
 
 using namespace tsat;
 
@@ -45,6 +50,10 @@ double* tsat_ws_gravity(tsat_handle* h, size_t bytes);
 // roll-out of tsat_pd_ensemble (tsat_kernels_pd.hip); the handle's GPU (tsat_kernels.hip)
 hipError_t tsat_launch_pd(const PdArgs<double>& a, int waves, hipStream_t stream);
 int tsat_handle_device(const tsat_handle* h);
+// pack and roll-outs of the sensed calls (tsat_kernels_sensed.hip)
+hipError_t tsat_launch_sensed_pack(const double* sensor, double* SN, int64_t T, int M, int Mp, hipStream_t stream);
+hipError_t tsat_launch_sensed_tv(const SensedTvArgs<double>& a, int waves, hipStream_t stream);
+hipError_t tsat_launch_sensed_pd(const SensedPdArgs<double>& a, int waves, hipStream_t stream);
 
 template <typename real, int DIAGJ>
 __global__ __launch_bounds__(64) void tsat_ensemble_kernel(EnsArgs<real> a) {
@@ -135,6 +144,32 @@ struct Gravity {
   double gm;
 };
 
+// ... and the sensed calls to either law
+struct Sensing {
+  const tsat_sensor_options* s;
+  const double* sensor;
+};
+
+// every realisation flies the model's plant: (Jmat, G = I, m_res = 0); the pack reads the upper triangle of Jp
+std::vector<double> model_plants(const double* Jmat, size_t Tn, int M) {
+  std::vector<double> model(Tn * (size_t)M * TSAT_PLANT_W, 0.0);
+  for (size_t t = 0; t < Tn; ++t)
+    for (int m = 0; m < M; ++m) {
+      double* pl = model.data() + (t * M + m) * TSAT_PLANT_W;
+      for (int i = 0; i < 9; ++i) pl[i] = Jmat[9 * t + i];
+      pl[9] = pl[13] = pl[17] = 1.0;
+    }
+  return model;
+}
+
+// the launch block of the sensor from the options of both calls
+SensArgs<double> sens_args(const Sensing& sn, const tsat_tvlqr_options* o, const double* dSN, int Mp) {
+  SensArgs<double> a;
+  a.SN = dSN; a.Mp = Mp; a.sgy = sn.s->sigma_gyro; a.sat = sn.s->sigma_att; a.smg = sn.s->sigma_mag; a.latency = sn.s->latency;
+  a.k0 = (unsigned)(o->noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o->noise_seed >> 32);
+  return a;
+}
+
 std::string at_tm(int64_t t, int m) { return " at (t, m) = (" + std::to_string(t) + ", " + std::to_string(m) + ")"; }
 
 // the host only validates the plants: "" or the reason, with the offending (t, m)
@@ -150,13 +185,14 @@ std::string check_dispersion(const Dispersion& d, int64_t T, int M) {
   return "";
 }
 
-// all entry points: `disp` == nullptr is tsat_tvlqr_ensemble, `grav` != nullptr (with `disp`) tsat_tvlqr_ensemble_gg
+// all entry points: `disp` == nullptr is tsat_tvlqr_ensemble, `grav` != nullptr (with `disp`) tsat_tvlqr_ensemble_gg, `sens` != nullptr
+// (with both) tsat_tvlqr_ensemble_sensed
 int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
                  const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
                  const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
                  const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
                  tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr,
-                 double* X_sim, const Dispersion* disp, const Gravity* grav = nullptr) {
+                 double* X_sim, const Dispersion* disp, const Gravity* grav = nullptr, const Sensing* sens = nullptr) {
   g_err.clear();
   if (!h || !o) return efail(-1, "null handle or options");
   const std::string why = check_tv_options(*o);
@@ -178,12 +214,20 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
     if (n_knots && (n_knots[t] < 2 || n_knots[t] > N)) return efail(-1, "n_knots[t] must be in [2, N]");
     bi[(size_t)t] = (int)v;
   }
-  if (disp) {
-    const std::string bad = check_dispersion(*disp, T, M);
+  if (disp) {   // the sensed call takes the model's plant for a NULL plant
+    const std::string bad = (sens && !disp->plant) ? check_limits(disp->sat_lo, disp->sat_hi, T) : check_dispersion(*disp, T, M);
     if (!bad.empty()) return efail(-1, bad);
+  }
+  if (grav && sens && !grav->Rtab) {   // ... and the kernel without the gravity rows for a NULL Rtab
+    if (!(grav->gm == 0.0)) return efail(-1, "Rtab is NULL but gm != 0: the gravity-gradient term needs the orbit table");
+    grav = nullptr;
   }
   if (grav) {
     const std::string bad = check_gravity(grav->Rtab, grav->gm, n_btab * (int64_t)o->n_tab);
+    if (!bad.empty()) return efail(-1, bad);
+  }
+  if (sens) {
+    const std::string bad = check_sensor(sens->s, sens->sensor, T, M);
     if (!bad.empty()) return efail(-1, bad);
   }
   // ---- 1. the handle: the library's own checks on slew 0 cut to two knots; its GPU becomes the thread's current device ----
@@ -226,6 +270,9 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   // the gravity call: the raw orbit table is the call's, the packed rows are the handle's
   double *dR = nullptr, *dGT = nullptr;
   if (ok && grav) ok = s.alloc(&dR, nB * 3) && (dGT = tsat_ws_gravity(h, nB * 4 * 8)) != nullptr;
+  // the sensed call: raw biases (when given) and the per-lane records
+  double *dSens = nullptr, *dSN = nullptr;
+  if (ok && sens) ok = s.alloc(&dSN, Tn * SNW * (size_t)Mp) && (!sens->sensor || s.alloc(&dSens, nS * SNW));
   if (!ok) return efail(-10, std::string("device allocation failed in ") + name);
 #define ENS_HIP(call)                                                                                   \
   do {                                                                                                  \
@@ -258,7 +305,8 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
         sat[SATW * t + c] = disp->sat_lo ? disp->sat_lo[3 * t + c] : -HUGE_VAL;
         sat[SATW * t + 3 + c] = disp->sat_hi ? disp->sat_hi[3 * t + c] : HUGE_VAL;
       }
-    ENS_HIP(hipMemcpy(dPlant, disp->plant, nS * TSAT_PLANT_W * 8, hipMemcpyHostToDevice));
+    const std::vector<double> model = disp->plant ? std::vector<double>() : model_plants(Jmat, Tn, M);
+    ENS_HIP(hipMemcpy(dPlant, disp->plant ? disp->plant : model.data(), nS * TSAT_PLANT_W * 8, hipMemcpyHostToDevice));
     ENS_HIP(hipMemcpy(dSat, sat.data(), sat.size() * 8, hipMemcpyHostToDevice));
     ENS_HIP(hipEventRecord(s.ev[3], s.stream));
     const int64_t n = T * (int64_t)(M + 1);
@@ -269,6 +317,10 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   if (grav) {
     ENS_HIP(hipMemcpy(dR, grav->Rtab, nB * 3 * 8, hipMemcpyHostToDevice));
     ENS_HIP(tsat_launch_gg_pack(dR, grav->gm, dGT, (int64_t)nB, s.stream));
+  }
+  if (sens) {
+    if (sens->sensor) ENS_HIP(hipMemcpy(dSens, sens->sensor, nS * SNW * 8, hipMemcpyHostToDevice));
+    ENS_HIP(tsat_launch_sensed_pack(dSens, dSN, T, M, Mp, s.stream));
   }
   ENS_HIP(hipEventRecord(s.ev[0], s.stream));
   {
@@ -290,7 +342,12 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
     if (disp) {
       DispArgs<double> d;
       d.e = a; d.PL = dPL; d.Mp = Mp; d.SAT = dSat; d.nclip = dClip;
-      if (grav) {
+      if (sens) {
+        SensedTvArgs<double> sa;
+        sa.g.d = d; sa.g.GT = dGT;
+        sa.s = sens_args(*sens, o, dSN, Mp);
+        ENS_HIP(tsat_launch_sensed_tv(sa, nw, s.stream));
+      } else if (grav) {
         GgEnsArgs<double> g;
         g.d = d; g.GT = dGT;
         ENS_HIP(tsat_launch_ensemble_gg(g, nw, s.stream));
@@ -335,18 +392,23 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   return 0;
 }
 
-// tsat_pd_ensemble: steps 2, 4 and 5 of run_ensemble around the kernels of tsat_kernels_pd.hip
+// tsat_pd_ensemble: steps 2, 4 and 5 of run_ensemble around the kernels of tsat_kernels_pd.hip; `sens` != nullptr is
+// tsat_pd_ensemble_sensed
 int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X, const double* U,
            const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau, const double* dt,
            const double* Jmat, const double* kd, const double* kp, int32_t feedforward, int32_t limit_mode, const double* x0_sim,
            const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots, const double* plant, const double* sat_lo,
            const double* sat_hi, tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* X_sim,
-           int32_t* n_clipped, const double* Rtab, double gm) {
+           int32_t* n_clipped, const double* Rtab, double gm, const Sensing* sens = nullptr) {
   g_err.clear();
   if (!h) return efail(-1, "null handle or options");
   const std::string why = check_pd(o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode,
                                    x0_sim, x0_nom, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, Rtab, gm);
   if (!why.empty()) return efail(-1, why);
+  if (sens) {
+    const std::string bad = check_sensor(sens->s, sens->sensor, T, M);
+    if (!bad.empty()) return efail(-1, bad);
+  }
 #define ENS_HIP(call)                                                                                   \
   do {                                                                                                  \
     hipError_t e_ = (call);                                                                             \
@@ -372,14 +434,8 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
     }
   }
   pack_tv_params<double>(T, x0n.data(), xf, tau0, dtau, dt, Jmat, zero.data(), zero.data(), zero.data(), P.data());
-  if (!plant) {   // every realisation flies the model's plant: (Jmat, G = I, m_res = 0); the pack reads the upper triangle of Jp
-    model.assign(nS * TSAT_PLANT_W, 0.0);
-    for (size_t t = 0; t < Tn; ++t)
-      for (int m = 0; m < M; ++m) {
-        double* pl = model.data() + (t * M + m) * TSAT_PLANT_W;
-        for (int i = 0; i < 9; ++i) pl[i] = Jmat[9 * t + i];
-        pl[9] = pl[13] = pl[17] = 1.0;
-      }
+  if (!plant) {
+    model = model_plants(Jmat, Tn, M);
     plant = model.data();
   }
   EnsScope s;
@@ -397,6 +453,8 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
   if (ok && X_sim) ok = s.alloc(&dXS, nXS);
   if (ok && n_clipped) ok = s.alloc(&dClip, nS);
   if (ok && Rtab) ok = s.alloc(&dR, nB * 3) && (dGT = tsat_ws_gravity(h, nB * 4 * 8)) != nullptr;
+  double *dSens = nullptr, *dSN = nullptr;
+  if (ok && sens) ok = s.alloc(&dSN, Tn * SNW * (size_t)Mp) && (!sens->sensor || s.alloc(&dSens, nS * SNW));
   if (!ok) return efail(-10, "device allocation failed in tsat_pd_ensemble");
   ENS_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
   for (hipEvent_t& e : s.ev) ENS_HIP(hipEventCreate(&e));
@@ -430,6 +488,10 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
     ENS_HIP(hipMemcpy(dR, Rtab, nB * 3 * 8, hipMemcpyHostToDevice));
     ENS_HIP(tsat_launch_gg_pack(dR, gm, dGT, (int64_t)nB, s.stream));
   }
+  if (sens) {
+    if (sens->sensor) ENS_HIP(hipMemcpy(dSens, sens->sensor, nS * SNW * 8, hipMemcpyHostToDevice));
+    ENS_HIP(tsat_launch_sensed_pack(dSens, dSN, T, M, Mp, s.stream));
+  }
   // ---- 4. the roll-out ------------------------------------------------------------------------------------------------
   ENS_HIP(hipEventRecord(s.ev[0], s.stream));
   {
@@ -443,7 +505,14 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
     a.XS = dXS; a.stats = dst; a.stats_nom = dsn;
     pa.d.PL = dPL; pa.d.Mp = Mp; pa.d.SAT = dSat; pa.d.nclip = dClip;
     pa.GT = dGT; pa.GAIN = dGain; pa.X0N = dX0N; pa.feedforward = feedforward; pa.limit_mode = limit_mode;
-    ENS_HIP(tsat_launch_pd(pa, nw, s.stream));
+    if (sens) {
+      SensedPdArgs<double> sa;
+      sa.p = pa;
+      sa.s = sens_args(*sens, o, dSN, Mp);
+      ENS_HIP(tsat_launch_sensed_pd(sa, nw, s.stream));
+    } else {
+      ENS_HIP(tsat_launch_pd(pa, nw, s.stream));
+    }
   }
   ENS_HIP(hipEventRecord(s.ev[1], s.stream));
   ENS_HIP(hipStreamSynchronize(s.stream));
@@ -457,7 +526,7 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
     if (v[0] == '1') {
       float e = 0;
       (void)hipEventElapsedTime(&e, s.ev[0], s.ev[1]);
-      std::fprintf(stderr, "tsat_pd_ensemble: pd_kernel_ms %.4f\n", e);
+      std::fprintf(stderr, "%s: pd_kernel_ms %.4f\n", sens ? "tsat_pd_ensemble_sensed" : "tsat_pd_ensemble", e);
     }
   }
 #undef ENS_HIP
@@ -476,6 +545,24 @@ int tsat_pd_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int
                      tsat_tvlqr_stats* stats_nominal, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm) {
   return run_pd(h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode, x0_sim, x0_nom,
                 noise_id0, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, X_sim, n_clipped, Rtab, gm);
+}
+
+int tsat_pd_ensemble_sensed(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                            const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                            const double* dtau, const double* dt, const double* Jmat, const double* kd, const double* kp,
+                            int32_t feedforward, int32_t limit_mode, const double* x0_sim, const double* x0_nom, const int64_t* noise_id0,
+                            const int32_t* n_knots, const double* plant, const double* sat_lo, const double* sat_hi,
+                            tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* X_sim, int32_t* n_clipped,
+                            const double* Rtab, double gm, const tsat_sensor_options* sn, const double* sensor) {
+  const Sensing se{sn, sensor};
+  return run_pd(h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode, x0_sim, x0_nom,
+                noise_id0, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, X_sim, n_clipped, Rtab, gm, &se);
+}
+
+void tsat_sensor_default_options(tsat_sensor_options* s) {
+  if (!s) return;
+  s->sigma_gyro = 0.0; s->sigma_att = 0.0; s->sigma_mag = 0.0;
+  s->latency = 0; s->reserved = 0;
 }
 
 const char* tsat_ensemble_last_error(void) { return g_err.c_str(); }
@@ -513,6 +600,20 @@ int tsat_tvlqr_ensemble_gg(tsat_handle* h, const tsat_tvlqr_options* o, int64_t 
   const Gravity g{Rtab, gm};
   return run_ensemble("tsat_tvlqr_ensemble_gg", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, Qd, Qfd, Rd, x0_sim,
                       noise_id0, n_knots, stats, summary, stats_nominal, K_lqr, X_sim, &d, &g);
+}
+
+int tsat_tvlqr_ensemble_sensed(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                               const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                               const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
+                               const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                               const double* plant, const double* sat_lo, const double* sat_hi, tsat_tvlqr_stats* stats,
+                               double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr, double* X_sim, int32_t* n_clipped,
+                               const double* Rtab, double gm, const tsat_sensor_options* sn, const double* sensor) {
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  const Sensing se{sn, sensor};
+  return run_ensemble("tsat_tvlqr_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, Qd, Qfd, Rd,
+                      x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, K_lqr, X_sim, &d, &g, &se);
 }
 
 }  // extern "C"

@@ -18,6 +18,8 @@
 //   b = qrot(x[3:7] / |x[3:7]|, b0)         b0: the stage-0 field row the step has loaded anyway, no noise
 //   m = (b x Treq) / (b . b), 0 where b . b == 0        [A m^2]
 //   u_cmd = (feedforward ? U_k : 0) + m / u_scale
+// (what the law sees of x — the errors' state and the body-frame field — comes from the `Sensor` of the roll-out: TrueState of
+// tsat_ensemble.hpp, which holds the qrot lines above, for tsat_pd_ensemble; Sensed of tsat_sensed.hpp for tsat_pd_ensemble_sensed)
 // then the limit (0: the component clip of DispersedPlant::command; 1: u / beta when beta = max_c u_c / (u_c > 0 ? hi_c : lo_c)
 // exceeds 1) and the parent's G u_sat + m_res / u_scale held over the four stages.
 //
@@ -46,8 +48,8 @@ struct PdArgs {
   int feedforward, limit_mode;
 };
 
-template <typename real, typename Plant>
-TSAT_DEV void pd_rollout(const PdArgs<real>& pa, Plant& plant, int traj, int wave) {
+template <typename real, typename Plant, typename Sensor = TrueState>
+TSAT_DEV void pd_rollout(const PdArgs<real>& pa, Plant& plant, int traj, int wave, Sensor sensor = Sensor()) {
   constexpr int DIAGJ = Plant::DIAGJ;
   const EnsArgs<real>& a = pa.d.e;
   const int lane = TSAT_LANE();
@@ -65,6 +67,7 @@ TSAT_DEV void pd_rollout(const PdArgs<real>& pa, Plant& plant, int traj, int wav
   const TSAT_CONSTMEM real* bt = (const TSAT_CONSTMEM real*)(a.BT + (size_t)a.bidx[traj] * n_tab * 4);
   const Traj<real> tr = ensemble_traj<real>(Pc, a.us, N, n_tab);
   plant.load(tr, traj, r);
+  sensor.load(traj, r);
   const Traj<real>& tp = plant.traj(tr);                       // what dyn_sim_h reads
   const long long gid = (a.nid0 ? a.nid0[traj] : (long long)traj * (long long)M) + (long long)r;
   TSAT_GLOBAL real* xs = (a.XS && live && noisy) ? (TSAT_GLOBAL real*)(a.XS + ((size_t)traj * M + r) * NS * 7) : nullptr;
@@ -109,29 +112,23 @@ TSAT_DEV void pd_rollout(const PdArgs<real>& pa, Plant& plant, int traj, int wav
     const TSAT_CONSTMEM real* p1 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tr, k, 0.5)) * 4;
     const TSAT_CONSTMEM real* p2 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tr, k, 1.0)) * 4;
     const real b0[3] = {p0[0], p0[1], p0[2]}, b1[3] = {p1[0], p1[1], p1[2]}, b2[3] = {p2[0], p2[1], p2[2]};
-    {  // the law
-      real tq[3];
+    {  // the law, on what the sensor gives of x: y for the errors, B for the body-frame field
+      real tq[3], y[7], B[3];
+      sensor.state(gid, k, noisy, x, y);
       {
         // e = q_ref^-1 (x) q_sim: the vector part as ensemble_rollout forms it, and the scalar part for the sign rule
         const real s1 = xr[3], a1 = -xr[4], a2 = -xr[5], a3 = -xr[6];
-        const real e0 = s1 * x[3] - (a1 * x[4] + a2 * x[5] + a3 * x[6]);
-        const real e1 = s1 * x[4] + x[3] * a1 + (a2 * x[6] - a3 * x[5]);
-        const real e2 = s1 * x[5] + x[3] * a2 + (a3 * x[4] - a1 * x[6]);
-        const real e3 = s1 * x[6] + x[3] * a3 + (a1 * x[5] - a2 * x[4]);
+        const real e0 = s1 * y[3] - (a1 * y[4] + a2 * y[5] + a3 * y[6]);
+        const real e1 = s1 * y[4] + y[3] * a1 + (a2 * y[6] - a3 * y[5]);
+        const real e2 = s1 * y[5] + y[3] * a2 + (a3 * y[4] - a1 * y[6]);
+        const real e3 = s1 * y[6] + y[3] * a3 + (a1 * y[5] - a2 * y[4]);
         const bool neg = e0 < 0;                               // shortest rotation
-        tq[0] = -(kd[0] * (x[0] - xr[0]) + kp[0] * (neg ? -e1 : e1));
-        tq[1] = -(kd[1] * (x[1] - xr[1]) + kp[1] * (neg ? -e2 : e2));
-        tq[2] = -(kd[2] * (x[2] - xr[2]) + kp[2] * (neg ? -e3 : e3));
+        tq[0] = -(kd[0] * (y[0] - xr[0]) + kp[0] * (neg ? -e1 : e1));
+        tq[1] = -(kd[1] * (y[1] - xr[1]) + kp[1] * (neg ? -e2 : e2));
+        tq[2] = -(kd[2] * (y[2] - xr[2]) + kp[2] * (neg ? -e3 : e3));
       }
-      // b = qrot(q, b0) = b0 + 2 v x (v x b0 + s b0), as dyn_h rotates it
-      const real rn = rsqrt_<real>(x[3] * x[3] + x[4] * x[4] + x[5] * x[5] + x[6] * x[6]);
-      const real q0 = x[3] * rn, q1 = x[4] * rn, q2 = x[5] * rn, q3 = x[6] * rn;
-      const real c0 = (q2 * b0[2] - q3 * b0[1]) + q0 * b0[0];
-      const real c1 = (q3 * b0[0] - q1 * b0[2]) + q0 * b0[1];
-      const real c2 = (q1 * b0[1] - q2 * b0[0]) + q0 * b0[2];
-      const real B0 = b0[0] + 2 * (q2 * c2 - q3 * c1);
-      const real B1 = b0[1] + 2 * (q3 * c0 - q1 * c2);
-      const real B2 = b0[2] + 2 * (q1 * c1 - q2 * c0);
+      sensor.field(gid, k, noisy, x, b0, B);                   // TrueState: qrot(q, b0)
+      const real B0 = B[0], B1 = B[1], B2 = B[2];
       const real bb = B0 * B0 + B1 * B1 + B2 * B2;
       // the one reciprocal of the knot; a zero row (the last of a magnetic_simulation table) gives no dipole
       const real sc = (bb == 0) ? (real)0 : rcp_(bb) * ius;

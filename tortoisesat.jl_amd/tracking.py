@@ -367,6 +367,13 @@ def attitude_ensemble_pd(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X
     whole command back onto the box (needs lo < 0 < hi). ``x0_nom`` (T, 7) starts the noise-free MODEL plant (default X[:, 0];
     when regulating without it ``nominal`` is None). Returns dict(stats (T, M), summary (T, 8), nominal (T,) or None, X_sim
     (T, M, N, 7) or None, n_clipped (T, M))."""
+    return _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
+                    want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol)
+
+
+def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0, want_trajectories,
+             sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=None):
+    """``tsat_pd_ensemble``, or with ``sensing`` = (SensorOptions, sensor array or None) ``tsat_pd_ensemble_sensed``"""
     lib = _abi.load()
     T, N = batch.T, batch.N
     c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
@@ -405,12 +412,96 @@ def attitude_ensemble_pd(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X
     Xs = np.empty((T, M, N, 7)) if want_trajectories else None
     ncl = np.zeros((T, M), dtype=np.int32)
     d = _abi.as_dp
-    rc = lib.tsat_pd_ensemble(solver._h, C.byref(o), T, batch.Btab.shape[0], M, d(X), d(U), d(batch.xf), d(batch.Btab),
-                              _abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat), d(kd), d(kp),
-                              0 if U is None else 1, int(limit_mode), d(x0_sim), d(x0_nom),
-                              None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), _abi.as_ip(nk), d(plant), d(lo), d(hi),
-                              st.ctypes.data_as(C.c_void_p), d(summary), None if nom is None else nom.ctypes.data_as(C.c_void_p), d(Xs),
-                              _abi.as_ip(ncl), d(Rtab), float(gm))
+    args = (solver._h, C.byref(o), T, batch.Btab.shape[0], M, d(X), d(U), d(batch.xf), d(batch.Btab),
+            _abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat), d(kd), d(kp),
+            0 if U is None else 1, int(limit_mode), d(x0_sim), d(x0_nom),
+            None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), _abi.as_ip(nk), d(plant), d(lo), d(hi),
+            st.ctypes.data_as(C.c_void_p), d(summary), None if nom is None else nom.ctypes.data_as(C.c_void_p), d(Xs),
+            _abi.as_ip(ncl), d(Rtab), float(gm))
+    if sensing is None:
+        name, rc = "tsat_pd_ensemble", lib.tsat_pd_ensemble(*args)
+    else:
+        name, rc = "tsat_pd_ensemble_sensed", lib.tsat_pd_ensemble_sensed(*args, C.byref(sensing[0]), d(sensing[1]))
     if rc != 0:
-        raise RuntimeError(f"tsat_pd_ensemble failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
+        raise RuntimeError(f"{name} failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
     return dict(stats=st, summary=summary, nominal=nom, X_sim=Xs, n_clipped=ncl)
+
+
+SENSOR_W = 9
+#: the reference's gyro and attitude figures read UN-SQUARED (src/simulator.jl:5,10): 0.38 deg (rad/s) and 1 deg (rad)
+SENSOR_SIGMA_GYRO = 0.38 * np.pi / 180.0
+SENSOR_SIGMA_ATT = 1.0 * np.pi / 180.0
+
+
+def disperse_sensor(T, M, rng, gyro_bias=0.0, att_bias_deg=0.0, mag_bias=0.0):
+    """Sensor biases of M realisations per slew for the sensed ensembles, (T, M, 9) = [bw (3, rad/s), ba (3, rotation vector, rad,
+    body frame), bm (3, units of the field table)]: normal per axis with sigma ``gyro_bias``, ``att_bias_deg`` (degrees) and
+    ``mag_bias``. All-zero levels return exactly zeros. Every realisation consumes the same 9 normals per slew, realisation after
+    realisation, as ``disperse_plant``: the first M' realisations of a larger ensemble are the ensemble of size M'."""
+    if min(gyro_bias, att_bias_deg, mag_bias) < 0.0:
+        raise ValueError("bias levels must not be negative")
+    out = np.zeros((int(T), int(M), SENSOR_W))
+    lev = np.repeat([float(gyro_bias), float(np.deg2rad(att_bias_deg)), float(mag_bias)], 3)
+    for m in range(int(M)):
+        out[:, m, :] = lev * rng.standard_normal((int(T), SENSOR_W))
+    return out
+
+
+def _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency):
+    """(SensorOptions, biases (T, M, 9) or None) of a sensed call"""
+    so = _abi.SensorOptions()
+    _abi.load().tsat_sensor_default_options(C.byref(so))
+    so.sigma_gyro, so.sigma_att, so.sigma_mag, so.latency = float(sigma_gyro), float(sigma_att), float(sigma_mag), int(latency)
+    if sensor is not None:
+        sensor = np.ascontiguousarray(sensor, dtype=np.float64)
+        if sensor.shape != (T, M, SENSOR_W):
+            raise ValueError("sensor must be (T, M, 9)")
+    return so, sensor
+
+
+def attitude_ensemble_sensed(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant=None, Rtab=None, gm=0.0, sat=None,
+                             sensor=None, sigma_gyro=0.0, sigma_att=0.0, sigma_mag=0.0, latency=0, noise_id0=None, sigma_scale=1.0,
+                             want_K=False, want_trajectories=False, linearize_dt_sq=True, u_scale=1e-2, min_steps=10, w_tol=0.05,
+                             angle_tol=0.08727):
+    """``attitude_ensemble_gg`` with the TVLQR feedback reading a MEASUREMENT of the state instead of the state
+    (``tsat_tvlqr_ensemble_sensed``): w_m = w + bw + n_w and q_m = q (x) dq(ba + n_a) per knot, with the biases of ``sensor``
+    ((T, M, 9), ``disperse_sensor``; None: zeros), white noise of ``sigma_gyro`` (rad/s) and ``sigma_att`` (rad) drawn in the kernel
+    from the realisation's generator id, and ``latency`` 0 or 1 knots between measurement and command (include/tortoise_hip.h).
+    ``sigma_mag`` is accepted for symmetry with ``attitude_ensemble_pd_sensed``: this law reads no magnetometer. ``plant`` None
+    flies the model's plant, ``Rtab`` None (needs gm = 0) no gravity-gradient term. The plant, the statistic and ``X_sim`` are the
+    TRUE states; ``nominal`` flies the ideal sensor at the same latency. Returns the dict of ``attitude_ensemble_gg``."""
+    lib, head, tail, out = _ensemble_call(solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, noise_id0, sigma_scale, want_K,
+                                          want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol)
+    T, M = out["stats"].shape
+    c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    plant = c(plant)
+    if plant is not None and plant.shape != (T, M, PLANT_W):
+        raise ValueError("plant must be (T, M, 21)")
+    if Rtab is not None:
+        Rtab = orbit_table(batch, Rtab)
+    lo = hi = None
+    if sat is not None:
+        lo, hi = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in sat)
+    so, sensor = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
+    ncl = np.zeros((T, M), dtype=np.int32)
+    d = _abi.as_dp
+    rc = lib.tsat_tvlqr_ensemble_sensed(*head, d(plant), d(lo), d(hi), *tail, _abi.as_ip(ncl), d(Rtab), float(gm), C.byref(so), d(sensor))
+    if rc != 0:
+        raise RuntimeError(f"tsat_tvlqr_ensemble_sensed failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
+    return dict(out, n_clipped=ncl)
+
+
+def attitude_ensemble_pd_sensed(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X=None, U=None, plant=None, Rtab=None, gm=0.0,
+                                sat=None, limit_mode=0, x0_nom=None, sensor=None, sigma_gyro=0.0, sigma_att=0.0, sigma_mag=0.0, latency=0,
+                                noise_id0=None, want_trajectories=False, sigma_scale=1.0, u_scale=1e-2, min_steps=10, w_tol=0.05,
+                                angle_tol=0.08727):
+    """``attitude_ensemble_pd`` with the law reading MEASUREMENTS (``tsat_pd_ensemble_sensed``): rate and attitude errors from
+    (w_m, q_m) as ``attitude_ensemble_sensed``, and the body-frame field from a magnetometer, b_m = (true body field) + bm + n_m
+    with noise of ``sigma_mag`` (units of the field table). ``sensor``, ``sigma_*`` and ``latency`` as there; everything else and
+    the returned dict as ``attitude_ensemble_pd``."""
+    x0 = np.asarray(x0_sim)
+    if x0.ndim != 3:
+        raise ValueError("x0_sim must be (T, M, 7)")
+    sensing = _sensing(batch.T, x0.shape[1], sensor, sigma_gyro, sigma_att, sigma_mag, latency)
+    return _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
+                    want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing)
