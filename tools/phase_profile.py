@@ -34,9 +34,11 @@ solver.set_endgame(0)     # one kernel: the stamps of a wavefront cover its traj
 if len(sys.argv) > 7:     # keep rule of the one-trajectory builds' line search (tsat_set_store_policy): few, hold
     solver.set_store_policy(int(sys.argv[6]), int(sys.argv[7]))
     print(f"store policy: few = {sys.argv[6]}, hold = {sys.argv[7]}")
-solver.upload(b, o.max_linesearch); solver.trace(1)
+one_traj = not (variant >= 3 or (variant == 0 and T >= 2048))
+solver.upload(b, o.max_linesearch); solver.trace(2 if one_traj else 1)
 ms = solver.run(o); ms = solver.run(o)
-tr = solver.trace_download()[:, 0, :]
+tr_all = solver.trace_download()
+tr = tr_all[:, 0, :]
 nfw = solver.download(want_K=False)["stats"]["n_forward"].astype(float)
 if variant >= 3 or (variant == 0 and T >= 3072):   # the packed builds stamp one row per wavefront (its first trajectory): sums over
     tr = tr[::int(os.environ.get("TSAT_PK_G", "4"))]   # its PK_G trajectories
@@ -69,5 +71,13 @@ if not (variant >= 3 or (variant == 0 and T >= 2048)):
         print(f"    {t:4d}  {tot[t]/1e6:8.1f}  {int(it[t]):10d}  {int(nfw[t]):6d}  {int(nfw[t] - 1 - it[t]):8d}  {int(npass[t]):11d} ({cpass[t]/1e6:5.2f}, {100*cpass[t]/tot[t]:4.1f})"
               f"  {tr[t, 0]/1e6:10.1f}  {tr[t, 1]/1e6:8.1f}  {tr[t, 2]/1e6:8.1f}  {tr[t, 3]/1e6:8.1f}")
     print(f"  percentiles of a wave's Mcycles: p50 {np.percentile(tot, 50)/1e6:.1f}, p90 {np.percentile(tot, 90)/1e6:.1f}, p99 {np.percentile(tot, 99)/1e6:.1f}, max {tot.max()/1e6:.1f}")
+if one_traj:
+    # row 1 of a one-trajectory build: shader cycles and ticks of the 100 MHz counter over the whole solve of the wavefront — the
+    # clock it ran at (the chip lowers it under load), as opposed to the GHz-equivalent below, which divides by the KERNEL's time
+    cyc, ticks = tr_all[:, 1, 0], tr_all[:, 1, 1]
+    ghz = cyc / np.maximum(ticks, 1) * 0.1
+    sl = int(np.argmax(tot))
+    print(f"  in-kernel clock: median over wavefronts {np.median(ghz):.3f} GHz (min {ghz.min():.3f}, max {ghz.max():.3f}); slowest wavefront "
+          f"{ghz[sl]:.3f} GHz ({cyc[sl]/1e6:.1f} Mcycles in {ticks[sl]*1e-5:.2f} ms)")
 print(f"  sum of stamped phases {tot.mean()/1e6:.1f} Mcycles/wave = {tot.mean()/ (ms*1e-3)/1e9:.2f} GHz-equivalent of the kernel time")
 solver.close()

@@ -37,6 +37,7 @@ namespace tsat_emu { int lane(); void sync(); void* lds(); double* xch(); }
 #define TSAT_ATOMIC_ADD(ptr, v) __atomic_fetch_add((ptr), (v), __ATOMIC_RELAXED)
 #define TSAT_ATOMIC_LOAD(ptr) __atomic_load_n((ptr), __ATOMIC_RELAXED)
 #define TSAT_UNIFORM_INT(x) (x)
+#define TSAT_LANES_BELOW(n) (true)   // the emulator's lanes meet in barriers inside a step: all of them take every step
 #else
 #define TSAT_DEV __device__ __forceinline__
 // Each sweep is its own (non-inlined) function: the register allocator then works on one hot loop at a time
@@ -84,6 +85,11 @@ namespace tsat_emu { int lane(); void sync(); void* lds(); double* xch(); }
 #define TSAT_ATOMIC_LOAD(ptr) __hip_atomic_load((ptr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 // an int that is the same in every lane, said so to the compiler (lane 0's copy in an SGPR): a loop or branch on it is scalar
 #define TSAT_UNIFORM_INT(x) __builtin_amdgcn_readfirstlane((int)(x))
+// Guard of a sequential loop whose results are read from the first n lanes only (n a multiple of 16, a whole DPP row): the other
+// lanes sit the loop out. A masked lane does not shorten an instruction, but it lowers the load of the chip, which lowers its
+// clock under load. Measured worth having in the Riccati loop, not in the forward sweep (profiles/lanes/README.md). Never fewer
+// than 16 lanes: 8 or fewer active lanes issue fp64 2.4x slower (profiles/r01/lane_mask_ubench.txt).
+#define TSAT_LANES_BELOW(n) (TSAT_LANE() < (n))
 #endif
 
 // Every build contracts a*b + c ONLY where the source writes it in one expression (the language's own rule, decided by the front end
@@ -437,8 +443,10 @@ template <typename real> TSAT_DEV real dot3_(real a0, real b0, real a1, real b1,
 // the trace buffer's row 0 of each trajectory; the production build compiles all of it away.
 #if defined(TSAT_PROFILE) && !defined(TSAT_EMU)
 TSAT_DEV unsigned long long tick_() { return __builtin_amdgcn_s_memtime(); }
+TSAT_DEV unsigned long long wall_() { return wall_clock64(); }      // the 100 MHz counter: with tick_(), the clock a wavefront ran at
 #else
 TSAT_DEV unsigned long long tick_() { return 0ull; }
+TSAT_DEV unsigned long long wall_() { return 0ull; }
 #endif
 
 // a[i] for a register-resident array and a run-time i (select chain: keeps `a` out of scratch memory)
@@ -1537,8 +1545,8 @@ TSAT_PHASE BwdOut<real> riccati_chunk(TSAT_GLOBAL real* KDg, int k0, int nk, rea
 // between the steps of a knot: a value another lane holds is read as the DPP operand `row_newbcast:n` of the FMA that consumes
 // it (v_fmac_f64_dpp: src0 = lane n of the reader's row; issue cost and latency of a plain v_fma_f64,
 // profiles/r04/valu_f64_ubench.txt), against ~90 cycles for an LDS write -> read exchange, of which riccati_chunk pays four per
-// knot and the packed builds' former column recursion three. The one-trajectory builds run the same instructions with the
-// four rows holding the same trajectory; the packed builds run four trajectories at once (tsat_packed.hpp).
+// knot and the packed builds' former column recursion three. The one-trajectory builds run the same instructions on
+// row 0 alone (riccati_rows: the other rows sit the loop out); the packed builds run four trajectories at once (tsat_packed.hpp).
 //   step 1  W[r]  = sum_m S~[r][m] F[m][j]                r <= NH; row NH starts from l_j = [lx; lu]_j: W[NH] = Qx_j | Qu_b
 //   step 2  Q[i]  = lxx(i,j) | luu + sum_m F[m][i] W[m]   i < NH + 3: Qxx(:, j), Qux(:, j) on a state lane, Quu(:, b) on a control lane
 //   step 3  Quu, Qu to every lane (v_mov_b64_dpp); regularise, Sylvester test, adjugate inverse, K(:, j), d (every lane)
@@ -1710,31 +1718,44 @@ TSAT_PHASE BwdOut<real> riccati_rows(TSAT_GLOBAL real* KDg, int k0_, int nk_, re
   const double km = (lane < NH) ? 1.0 : 0.0, dm = (lane == 7) ? 1.0 : 0.0;
   int slot[3];
   for (int c = 0; c < 3; ++c) slot[c] = (lane < 7) ? (c * 7 + lane) : (21 + c);
-  bool pd_ok = true;
-  // One knot: the recursion step on the record read a knot ago, then its K,d record to HBM. Returns the Sylvester test.
-  auto knot = [&](const RowIn<NH>& in, int l) {
+  // The Sylvester test is accumulated over the chunk and looked at once, after it (backward_sweep stops between chunks): no
+  // scalar read-back and branch per knot. A failed sweep leaves in HBM what it always has — the failing knot's K,d record and none
+  // behind it: a knot stores while every knot before it has passed. What the knots after a failure compute (possibly NaN, which
+  // fails every later test as well) is thrown away by the restart. The four rows hold the same trajectory: the flag is the same in
+  // every lane. The flag lives in a register as a number, together with the lane's part in the store (lanes 0 .. 7): one compare
+  // and one select per knot, where a bool carried round the loop becomes a lane mask merged by scalar instructions.
+  int live = (lane < 8) ? 1 : -1;    // 0 once a knot has failed; until then > 0 on the lanes with a part in the K,d record
+  TSAT_GLOBAL real* kd = KDg + (size_t)(k0 + nk - 1) * KDW;      // the K,d record of the knot in hand, stepped down with it
+  // One knot: the recursion step on the record read a knot ago, then its K,d record to HBM.
+  auto knot = [&](const RowIn<NH>& in) {
     double Kc[3], d[3];
     const bool pd = riccati_row_step<NH, R>(st, in, ro, rho, Kc, d, dV1, dV2);
-    if (lane < 8) {
-      TSAT_GLOBAL real* kd = KDg + (size_t)(k0 + l) * KDW;
+    if (live > 0)
       for (int c = 0; c < 3; ++c) kd[slot[c]] = (real)fma_(Kc[c], km, d[c] * dm);
-    }
-    return TSAT_UNIFORM_INT(pd) != 0;      // wave-uniform: the four rows hold the same trajectory
+    kd -= KDW;
+    live = pd ? live : 0;
   };
   // The record of knot l - 1 is read while knot l is worked on (one wavefront per SIMD has nobody to hide an LDS latency behind);
-  // two knots per turn, two register sets A / B taking turns (a single set would have to be copied every knot).
-  auto rec = [&](int l) { return rec_base() + ((l > 0) ? l : 0) * R::RECS; };
-  RowIn<NH> A = row_load<jac_t, NH, R>(rec(nk - 1), ro);
-  for (int l = nk - 1; l >= 0; l -= 2) {
-    const RowIn<NH> B = row_load<jac_t, NH, R>(rec(l - 1), ro);
-    TSAT_SCHED_FENCE();
-    if (!knot(A, l)) { pd_ok = false; break; }
-    if (l - 1 >= 0) {
-      A = row_load<jac_t, NH, R>(rec(l - 2), ro);
+  // two knots per turn, two register sets A / B taking turns (a single set would have to be copied every knot). The read pointer
+  // steps down a record per knot; the read-ahead of the chunk's last knot takes the record's worth of LDS below L_REC (never used).
+  static_assert(L_REC * sizeof(cfg_real) >= R::RECS * sizeof(jac_t), "the read-ahead below the first record stays inside LDS");
+  // Only row 0 is read (K,d from lanes < 8, S~ from lanes < NH): the three other rows would repeat it, and sit the loop out.
+  if (TSAT_LANES_BELOW(16)) {
+    const jac_t* rp = rec_base() + (nk - 1) * R::RECS;
+    RowIn<NH> A = row_load<jac_t, NH, R>(rp, ro);
+    for (int l = nk - 1; l >= 0; l -= 2) {
+      const RowIn<NH> B = row_load<jac_t, NH, R>(rp - R::RECS, ro);
       TSAT_SCHED_FENCE();
-      if (!knot(B, l - 1)) { pd_ok = false; break; }
+      knot(A);
+      if (l - 1 >= 0) {
+        A = row_load<jac_t, NH, R>(rp - 2 * R::RECS, ro);
+        TSAT_SCHED_FENCE();
+        knot(B);
+      }
+      rp -= 2 * R::RECS;
     }
   }
+  const bool pd_ok = TSAT_UNIFORM_INT(live) != 0;      // lane 0's: non-zero while the sweep is sound (the emulator's lanes all ran the loop and agree)
   TSAT_SYNC_LDS();
   if (lane < NH)
     for (int r = 0; r <= NH; ++r) S64[r * 9 + lane] = st.Sc[r];
@@ -1979,6 +2000,7 @@ TSAT_DEV int solve_trajectory(const KArgs<real>& a, int traj, const Resume<real>
   unsigned long long pc_fwd = 0, pc_par = 0, pc_cost = 0;
   int n_cost = 0;                   // candidate_costs passes of the line searches (diagnostic build)
   bool start_ok = true;
+  const unsigned long long t_s0 = tick_(), w_s0 = wall_();      // diagnostic build: the solve's span on both counters
 
   if (rs) {
     // carry on: the nominal trajectory, gains' inputs and multipliers are in HBM; counters and terminal multipliers come along
@@ -2193,10 +2215,14 @@ TSAT_DEV int solve_trajectory(const KArgs<real>& a, int traj, const Resume<real>
       trace[3] = (double)pc_par; trace[4] = (double)inner_iters; trace[5] = (double)n_backward;
 #ifndef TSAT_PACKED      // (the packed builds stamp columns 6 and 7 themselves)
       trace[6] = (double)n_cost; trace[7] = (double)pc_cost;      // cost passes of the line searches, and the cycles in them
+      if (a.trace_rows > 1) {         // row 1: shader cycles and 100 MHz ticks from the start of the solve to here, and the two wall stamps
+        const unsigned long long w_s1 = wall_();
+        trace[8] = (double)(tick_() - t_s0); trace[9] = (double)(w_s1 - w_s0); trace[10] = (double)w_s0; trace[11] = (double)w_s1;
+      }
 #endif
     }
 #else
-    (void)pc_fwd; (void)pc_par; (void)pc_cost; (void)n_cost;
+    (void)pc_fwd; (void)pc_par; (void)pc_cost; (void)n_cost; (void)t_s0; (void)w_s0;
 #endif
   }
   return 0;
