@@ -64,6 +64,14 @@ if not (variant >= 3 or (variant == 0 and T >= 2048)):
     npass, cpass = tr[:, 6], tr[:, 7]
     print(f"  cost passes: {npass.mean():.1f} per wave, {cpass.sum() / max(npass.sum(), 1) / 1e3:.1f} kcycles each, "
           f"{100 * cpass.sum() / tot.sum():.2f} % of the stamped cycles (inside `parallel passes`)")
+    if tr_all.shape[1] > 1:
+        # row 1, columns 4 and 5: of those cycles, the stage-cost steps (record loads included) and the knot-order sums that
+        # are not hidden behind them; what is left is a pass's prologue and epilogue (constants, max reductions, terminal cost)
+        # and the caller's accept test
+        csteps, csums = tr_all[:, 1, 4], tr_all[:, 1, 5]
+        nps = max(npass.sum(), 1)
+        print(f"    of a pass: stage-cost steps {csteps.sum() / nps / 1e3:.1f} kcycles, knot-order sums {csums.sum() / nps / 1e3:.1f}, "
+              f"prologue + epilogue {(cpass.sum() - csteps.sum() - csums.sum()) / nps / 1e3:.1f}")
     print(f"  executed forward sweeps: {nfw.mean():.2f} per wave, repeated {np.mean(nfw - 1 - it):.3f} (max {int(np.max(nfw - 1 - it))})")
     print("  the ten slowest waves:")
     print("    traj   Mcycles  iterations  sweeps  repeated  cost passes (Mcycles, %)     forward  jacobian   riccati  parallel")

@@ -299,15 +299,17 @@ constexpr int FB_XU = FB_KD + ((CK * KDW + GLDS - 1) / GLDS) * GLDS;   // CK x 1
 constexpr int FB_BA = FB_XU + ((CK * XUW + GLDS - 1) / GLDS) * GLDS;   // 3 CK stage rows: (b0, b1) [double] or the whole row (b0, b1, b2, pad) [float]
 constexpr int FB_BB = FB_BA + ((CK * 3 * RPU + GLDS - 1) / GLDS) * GLDS; // 3 CK stage rows, (b2, pad) [double only]
 constexpr int FB_SIZE = FB_BB + (BROW_UNITS == 2 ? ((CK * 3 * RPU + GLDS - 1) / GLDS) * GLDS : 0);
-// candidate_costs: per-knot costs of CG candidates x KB knots (+2: the CG summing lanes read different banks)
+// candidate_costs: per-knot costs of CG candidates x KB knots (+2: the CG summing lanes read different banks), then the
+// candidates' terminal states (7, +1)
 constexpr int CG = 2, KB = 4 * WAVE, KBS = KB + 2;
+constexpr int CC_XN = CG * KBS, CC_SIZE = CC_XN + CG * 8;
 #if defined(TSAT_DENSE) || (defined(TSAT_F32) && TSAT_OCC >= 3)
 constexpr int FWD_NBUF = 1;   // 20 KB budget: one buffer; the second wavefront on the SIMD covers the copy latency
 #else
 constexpr int FWD_NBUF = 2;   // the next chunk is copied while this one is rolled out
 #endif
 constexpr int L_FWD = L_UNION;
-constexpr int L_FWD_END = L_FWD + (FWD_NBUF * FB_SIZE > CG * KBS ? FWD_NBUF * FB_SIZE : CG * KBS);
+constexpr int L_FWD_END = L_FWD + (FWD_NBUF * FB_SIZE > CC_SIZE ? FWD_NBUF * FB_SIZE : CC_SIZE);
 constexpr int L_BWD_RECV = (BwdCfg<0>::CHB * BwdCfg<0>::RECS > BwdCfg<1>::CHB * BwdCfg<1>::RECS
                                ? BwdCfg<0>::CHB * BwdCfg<0>::RECS : BwdCfg<1>::CHB * BwdCfg<1>::RECS);     // record values of a chunk
 constexpr int L_BWD_SOLVE = (L_BWD_RECV * (int)sizeof(jac_t) + (int)sizeof(cfg_real) - 1) / (int)sizeof(cfg_real);   // ... in reals
@@ -326,6 +328,7 @@ constexpr int LDS_REALS = (TSAT_PK_LDS_BYTES - ((sizeof(cfg_real) == 8) ? 0 : 64
 #else
 constexpr int LDS_REALS = (L_FWD_END > L_BWD_END ? L_FWD_END : L_BWD_END);
 #endif
+static_assert(L_FWD + CC_SIZE <= L_FWD_END && L_FWD + CC_SIZE <= LDS_REALS, "the cost blocks of candidate_costs fit this build's LDS block");
 
 // The wavefront's LDS block: a STATIC module-level __shared__ array. Declared at namespace scope so that every phase
 // function addresses it as LDS (address space 3) at a link-time constant address — a generic pointer argument would
@@ -458,6 +461,23 @@ TSAT_DEV real sel7(const real a[7], int i) {
 }
 
 template <typename real> TSAT_DEV real inf_() { return (real)__builtin_huge_val(); }
+
+// a value that is the same in every lane, moved to scalar registers (lane 0's copy): an operand of the vector instructions that
+// use it, and no vector register held across a loop
+template <typename real>
+TSAT_DEV real uniform_(real v) {
+#ifdef TSAT_EMU
+  return v;
+#else
+  if constexpr (sizeof(real) == 8) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return __builtin_bit_cast(real, ((unsigned long long)hi << 32) | lo);
+  } else {
+    return __builtin_bit_cast(real, (unsigned)__builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, v)));
+  }
+#endif
+}
 
 // Store of a branch-free lane-role step: lanes without a role in the step aim at the sink word L_SINK (never read). On the
 // GPU that is one ds_write for the whole wave — lanes hitting the same address in one instruction are well defined — while
@@ -1166,55 +1186,78 @@ TSAT_FWD void forward_sweep(TPtrs<real> p, int N, int n_tab, int closed, int n_c
 // packed builds run inside their sequential sweeps: stage_cost_gated on the stored record) and leaves it in LDS, KB knots at a
 // time; lane c then adds candidate c's costs IN KNOT ORDER, so J is, bit for bit, the sum a sequential roll-out accumulates. A
 // roll-out is valid when no |x_i|, |u_i| exceeded max_state and J is a number (a non-finite roll-out leaves amax = inf or J = NaN).
-// The records come from HBM: a step's loads (64 knots: multipliers + the candidates' records) are issued one step ahead of
-// their use, two register sets taking turns.
-template <typename real> struct CostIn { real lam[6], r[CG][XUW]; };
+//  * The records come from HBM: a step's loads (64 knots: multipliers + the candidates' records, REC_STORES loads a record) are
+//    issued one step ahead of their use — a candidate's next record into the registers its stage cost has just read, the
+//    multipliers into two sets that take turns. How many candidates take part is a template argument: nothing in the loop is
+//    predicated per element, and a lane past the last knot works on knot N - 1 once more (kx) — the maximum does not notice,
+//    record N - 1 carries u = 0, and its stage cost lands in a slot nobody adds.
+//  * Candidate c's terminal state goes to lane c through LDS from the lane that holds knot N - 1 in the last step, not through HBM.
+// one stored (x,u) record as REC_STORES loads: the mirror image of store_record5
 template <typename real>
-TSAT_PHASE FwdOut<real> candidate_costs(TPtrs<real> p, int N, int c0, int nc, real mu, int term_mask, real max_state) {
+TSAT_DEV void load_record5(const TSAT_GLOBAL real* cr, real r[XUW]) {
+  static_assert(XUW == 2 * REC_STORES, "a record is REC_STORES pairs");
+#ifdef TSAT_EMU
+  for (int i = 0; i < XUW; ++i) r[i] = cr[i];
+#else
+  typedef real v2 __attribute__((ext_vector_type(2)));
+  typedef const TSAT_GLOBAL v2* gv2;
+  for (int i = 0; i < REC_STORES; ++i) {
+    const v2 v = ((gv2)cr)[i];
+    r[2 * i] = v.x; r[2 * i + 1] = v.y;
+  }
+#endif
+}
+template <typename real, int NC>
+TSAT_PHASE FwdOut<real> candidate_costs_n(TPtrs<real> p, int N_, int c0, real mu, int term_mask, real max_state) {
+  static_assert(1 <= NC && NC <= CG, "a pass takes up to CG candidates");
+  const int N = TSAT_UNIFORM_INT(N_);          // (arguments arrive in vector registers: the loop control is scalar)
   real* lds = lds_base<real>();
-  const Traj<real> tr = load_traj<real>(N, 1, p.bt);
+  Traj<real> tr = load_traj<real>(N, 1, p.bt);
   const int lane = TSAT_LANE();
+  // what a stage cost reads of the constants sits in scalar registers, not in vector registers held across the loop
   HalfWeights<real> hw;
-  for (int i = 0; i < 7; ++i) hw.hQd[i] = (real)0.5 * tr.Qd[i];
-  for (int i = 0; i < 3; ++i) hw.hRd[i] = (real)0.5 * tr.Rd[i];
-  hw.hmu = (real)0.5 * mu;
-  real* L = lds + L_FWD;                       // [CG][KBS]
-  real am[CG];
-  for (int c = 0; c < CG; ++c) am[c] = 0;
+  for (int i = 0; i < 7; ++i) { hw.hQd[i] = uniform_((real)0.5 * tr.Qd[i]); tr.xf[i] = uniform_(tr.xf[i]); }
+  for (int i = 0; i < 3; ++i) { hw.hRd[i] = uniform_((real)0.5 * tr.Rd[i]); tr.ulo[i] = uniform_(tr.ulo[i]); tr.uhi[i] = uniform_(tr.uhi[i]); }
+  hw.hmu = uniform_((real)0.5 * mu);
+  real* L = lds + L_FWD;                       // [CG][KBS] costs, [CG][8] terminal states
+  real am[NC];
+  for (int c = 0; c < NC; ++c) am[c] = 0;
   acc_t J = 0;
-  const int cme = (lane < nc) ? lane : 0;
-  const TSAT_GLOBAL real* Cc[CG];
-  for (int c = 0; c < CG; ++c) Cc[c] = slab_ptr<real>(p, N, cand_slab(p.cur, c0 + (c < nc ? c : 0)));
+  unsigned long long pc_sum = 0;
+  const int cme = (lane < NC) ? lane : 0;
+  const TSAT_GLOBAL real* Cc[NC];
+  for (int c = 0; c < NC; ++c) Cc[c] = slab_ptr<real>(p, N, cand_slab(p.cur, c0 + c));
   const int S = (N + WAVE - 1) / WAVE;         // steps of 64 knots
   constexpr int SPB = KB / WAVE;               // steps per summed block
-  auto load = [&](int st) {
-    CostIn<real> in;
-    const int k = st * WAVE + lane, kx = (k < N) ? k : N - 1, kl = (k < N - 1) ? k : 0;
-    for (int e = 0; e < 6; ++e) in.lam[e] = p.LAM[(size_t)kl * LMW + e];
-    for (int c = 0; c < CG; ++c)
-      for (int e = 0; e < XUW; ++e) in.r[c][e] = (c < nc) ? Cc[c][(size_t)kx * XUW + e] : (real)0;
-    return in;
+  auto load_lam = [&](real* lam, int st) {
+    const int k = st * WAVE + lane, kl = (k < N - 1) ? k : 0;
+    for (int e = 0; e < 6; ++e) lam[e] = p.LAM[(size_t)kl * LMW + e];
   };
-  auto step = [&](const CostIn<real>& in, int st) {
-    const int k = st * WAVE + lane;
+  auto load_rec = [&](real* r, int c, int st) {
+    const int k = st * WAVE + lane, kx = (k < N) ? k : N - 1;
+    load_record5<real>(Cc[c] + (size_t)kx * XUW, r);
+  };
+  // one step: the stage costs of 64 knots of every candidate from the records in `r`; as soon as a candidate's record has been
+  // used, the same registers take its record of step `nx`
+  auto step = [&](const real* lam, real (*r)[XUW], int st, int nx) {
+    const int b = st / SPB, q = st % SPB;
     real gate[6];
-    for (int e = 0; e < 6; ++e) gate[e] = (in.lam[e] > 0) ? -inf_<real>() : (real)0;
-    for (int c = 0; c < CG; ++c) {
-      if (c >= nc) break;
+    for (int e = 0; e < 6; ++e) gate[e] = (lam[e] > 0) ? -inf_<real>() : (real)0;
+    real* Lw = L + q * WAVE + lane;
+    for (int c = 0; c < NC; ++c) {
       real a = am[c];
-      if (k < N)
-        for (int e = 0; e < 7; ++e) a = fmaxabs_(a, in.r[c][e]);
-      if (k < N - 1) {
-        for (int e = 7; e < 10; ++e) a = fmaxabs_(a, in.r[c][e]);
-        L[c * KBS + (st % SPB) * WAVE + lane] = stage_cost_gated(tr, hw, in.r[c], in.r[c] + 7, in.lam, gate);
-      }
+      for (int e = 0; e < XUW; ++e) a = fmaxabs_(a, r[c][e]);
       am[c] = a;
+      Lw[c * KBS] = stage_cost_gated(tr, hw, r[c], r[c] + 7, lam, gate);
+      if (st == S - 1 && st * WAVE + lane == N - 1)
+        for (int i = 0; i < 7; ++i) L[CC_XN + c * 8 + i] = r[c][i];
+      load_rec(r[c], c, nx);
     }
-    if ((st % SPB) == SPB - 1 || st == S - 1) {          // a block is complete: candidate `lane` adds its costs in knot order
+    if (q == SPB - 1 || st == S - 1) {                   // a block is complete: candidate `lane` adds its costs in knot order
+      const unsigned long long t_a = tick_();
       TSAT_SYNC_LDS();
-      if (lane < nc) {
-        const int k0 = (st / SPB) * KB;
-        const int n = (N - 1 - k0 < KB) ? (N - 1 - k0) : KB;
+      if (lane < NC) {
+        const int n = (N - 1 - b * KB < KB) ? (N - 1 - b * KB) : KB;
         const real* Lc = L + cme * KBS;
         int kk = 0;
         for (; kk + 16 <= n; kk += 16) {                 // the reads of a batch are issued together, the adds stay one chain
@@ -1225,31 +1268,44 @@ TSAT_PHASE FwdOut<real> candidate_costs(TPtrs<real> p, int N, int c0, int nc, re
         for (; kk < n; ++kk) J += (acc_t)Lc[kk];
       }
       TSAT_SYNC_LDS();
+      pc_sum += tick_() - t_a;
     }
   };
-  CostIn<real> A = load(0);
+  const unsigned long long t_l0 = tick_();
+  real lamA[6], lamB[6], r[NC][XUW];
+  load_lam(lamA, 0);
+  for (int c = 0; c < NC; ++c) load_rec(r[c], c, 0);
   for (int st = 0; st < S; st += 2) {
-    const CostIn<real> B = load((st + 1 < S) ? st + 1 : st);
-    step(A, st);
+    load_lam(lamB, (st + 1 < S) ? st + 1 : st);
+    step(lamA, r, st, (st + 1 < S) ? st + 1 : st);
     if (st + 1 < S) {
-      A = load((st + 2 < S) ? st + 2 : st + 1);
-      step(B, st + 1);
+      load_lam(lamA, (st + 2 < S) ? st + 2 : st + 1);
+      step(lamB, r, st + 1, (st + 2 < S) ? st + 2 : st + 1);
     }
   }
+#if defined(TSAT_PROFILE) && !defined(TSAT_EMU)
+  if (lane == 0) { lds[L_PC + 0] += (real)((tick_() - t_l0) - pc_sum); lds[L_PC + 3] += (real)pc_sum; }
+#else
+  (void)t_l0; (void)pc_sum;
+#endif
   real amax = 0;
-  for (int c = 0; c < CG; ++c) {
-    if (c >= nc) break;
+  for (int c = 0; c < NC; ++c) {
     const real m = wave_max(am[c], lds + L_RED);
     amax = (lane == c) ? m : amax;
   }
   real nu[7], xN[7];
-  const TSAT_GLOBAL real* cN = slab_ptr<real>(p, N, cand_slab(p.cur, c0 + cme)) + (size_t)(N - 1) * XUW;
-  for (int i = 0; i < 7; ++i) { nu[i] = lds[L_NU + i]; xN[i] = cN[i]; }
+  for (int i = 0; i < 7; ++i) { nu[i] = lds[L_NU + i]; xN[i] = L[CC_XN + cme * 8 + i]; }
   J += (acc_t)term_cost(tr, xN, nu, mu, term_mask, true);
   FwdOut<real> out;
   out.J = J;
-  out.ok = (lane < nc && (amax <= max_state) && (J == J)) ? 1 : 0;
+  out.ok = (lane < NC && (amax <= max_state) && (J == J)) ? 1 : 0;
   return out;
+}
+template <typename real>
+TSAT_DEV FwdOut<real> candidate_costs(TPtrs<real> p, int N, int c0, int nc, real mu, int term_mask, real max_state) {
+  static_assert(CG == 2, "one instance per group width");
+  if (TSAT_UNIFORM_INT(nc) >= 2) return candidate_costs_n<real, 2>(p, N, c0, mu, term_mask, max_state);
+  return candidate_costs_n<real, 1>(p, N, c0, mu, term_mask, max_state);
 }
 
 
@@ -2025,6 +2081,9 @@ TSAT_DEV int solve_trajectory(const KArgs<real>& a, int traj, const Resume<real>
     n_forward++;
     TSAT_SYNC();
     const FwdOut<real> f0 = candidate_costs<real>(p, N, 0, 1, mu, tmask, max_state);
+#if defined(TSAT_PROFILE) && !defined(TSAT_EMU)
+    if (lane == 0) lds[L_PC + 0] = lds[L_PC + 3] = 0;       // the stamps of the cost passes are those of the line searches
+#endif
     const acc_t J0 = wave_bcast(f0.J, 0, red64());
     const int ok0 = wave_first<real>(!f0.ok, lds + L_RED) > 0;  // lane 0 ok?
     TSAT_SYNC();
@@ -2218,6 +2277,9 @@ TSAT_DEV int solve_trajectory(const KArgs<real>& a, int traj, const Resume<real>
       if (a.trace_rows > 1) {         // row 1: shader cycles and 100 MHz ticks from the start of the solve to here, and the two wall stamps
         const unsigned long long w_s1 = wall_();
         trace[8] = (double)(tick_() - t_s0); trace[9] = (double)(w_s1 - w_s0); trace[10] = (double)w_s0; trace[11] = (double)w_s1;
+        // of the cost passes' cycles (column 7 of row 0): their stage-cost steps and their knot-order sums; the rest is the
+        // prologue and epilogue of a pass (constants, max reductions, terminal cost)
+        trace[12] = (double)lds[L_PC + 0]; trace[13] = (double)lds[L_PC + 3];
       }
 #endif
     }
