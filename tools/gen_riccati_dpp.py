@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Generates tortoisesat.jl_amd/csrc/tsat_riccati_dpp.inc: the four inline-asm blocks of one knot of the row-oriented Riccati
-recursion (riccati_row_step, tsat_device.hpp) for NH = 6 (error coordinates) and NH = 7 (full state).
+recursion (riccati_row_step, tsat_device.hpp) for NH = 6 (error coordinates) and NH = 7 (full state), and the feedback block of
+one knot of the closed-loop forward sweep (forward_sweep) for the same two.
 
 A block is a run of v_fmac_f64_dpp / v_mov_b64_dpp with `row_newbcast:n` — src0 is lane n of the reader's 16-lane row, for free
 in the FMA itself (profiles/r04/valu_f64_ubench.txt) — written out by hand because (a) hipcc does not fold a 64-bit
@@ -14,8 +15,8 @@ block starts with the wait states a DPP read of a just-written VGPR needs (2; th
 DPP = " row_newbcast:%d row_mask:0xf bank_mask:0xf"
 
 
-def block(name, nh, lines, outs, inouts, ins):
-    """one macro: TSAT_RB<name>_<nh>(operands...) -> asm volatile(...)"""
+def block(name, nh, lines, outs, inouts, ins, prefix="TSAT_RB"):
+    """one macro: <prefix><name>_<nh>() -> asm volatile(...)"""
     ops = [o for o, _ in outs] + [o for o, _ in inouts] + [o for o, _ in ins]
     txt = "".join('    "%s\\n"\\\n' % l for l in lines)
     cons = []
@@ -23,7 +24,7 @@ def block(name, nh, lines, outs, inouts, ins):
     io = ", ".join('[%s] "+v"(%s)' % (o, e) for o, e in inouts)
     out_s = ", ".join(s for s in (cons[0], io) if s)
     in_s = ", ".join('[%s] "v"(%s)' % (o, e) for o, e in ins)
-    return "#define TSAT_RB%s_%d() asm volatile(\\\n%s    : %s\\\n    : %s)\n" % (name, nh, txt, out_s, in_s)
+    return "#define %s%s_%d() asm volatile(\\\n%s    : %s\\\n    : %s)\n" % (prefix, name, nh, txt, out_s, in_s)
 
 
 def gen(nh):
@@ -71,8 +72,30 @@ def gen(nh):
     return "".join(out)
 
 
+def gen_fwd_gain(nh):
+    """TSAT_FG_<nh>: the feedback of one knot of the closed-loop forward sweep (forward_sweep, tsat_device.hpp),
+    u_c += sum_j K[c][j] dx_j + alpha d_c. The knot's K, d record (24 doubles: K 3 x 7 row-major, then d) sits two doubles a lane in
+    the first twelve lanes of every row — value i in lane i / 2, low or high double — and every term names the lane that holds its
+    multiplicand. Per accumulator the terms run j ascending, alpha d_c last: the order (and so the bits) of the plain loop. The
+    three accumulators take turns, so that one is touched again only three instructions later."""
+    kd = lambda i: (("%[kl]" if i % 2 == 0 else "%[kh]"), i // 2)
+    L = ["s_nop 1"]
+    for j in range(nh):
+        for c in range(3):
+            reg, lane = kd(c * 7 + j)
+            L.append(("v_fmac_f64_dpp %%[u%d], %s, %%[x%d]" % (c, reg, j)) + DPP % lane)
+    for c in range(3):
+        reg, lane = kd(21 + c)
+        L.append(("v_fmac_f64_dpp %%[u%d], %s, %%[al]" % (c, reg)) + DPP % lane)
+    return block("", nh, L, [], [("u%d" % c, "u[%d]" % c) for c in range(3)],
+                 [("kl", "kin.kd[0]"), ("kh", "kin.kd[1]")] + [("x%d" % j, "dx[%d]" % j) for j in range(nh)] + [("al", "alpha")], prefix="TSAT_FG")
+
+
 if __name__ == "__main__":
     print("// GENERATED by tools/gen_riccati_dpp.py — do not edit. Inline-asm blocks of riccati_row_step (tsat_device.hpp).")
     print("// Operands are the local names of that function: st.Sc, f, W, Q, h00..h22, qu, Kc, Tc.")
     for nh in (6, 7):
         print(gen(nh))
+    print("// Feedback of one knot of the closed-loop forward sweep. Operands are the local names of forward_sweep's knot: u, kin.kd, dx, alpha.")
+    for nh in (6, 7):
+        print(gen_fwd_gain(nh))

@@ -1060,15 +1060,50 @@ TSAT_DEV void fwd_chunk_issue(real* fb, const TSAT_GLOBAL real* KDg, const TSAT_
 template <typename real> struct FwdOut { acc_t J; int ok; };
 template <typename real> struct BwdOut { acc_t dV1, dV2; int pd_ok; };
 
-// what the roll-out of one knot reads from the staged chunk: nominal (x,u) record, gains K (3 x 7 row-major) and d, three field rows
-template <typename real> struct KnotIn { real xu[XUW], kd[KDW], b0[3], b1[3], b2[3]; };
+// The generated inline-asm blocks: the Riccati rows further down, and the feedback of a forward knot right here.
+#ifndef TSAT_EMU
+#include "tsat_riccati_dpp.inc"
+#endif
+// The gains of a forward knot through DPP (the wide fp64 build). The record K (3 x 7 row-major), d is the same for every lane and
+// each of its values is used once, as the multiplicand of one FMA: instead of eleven wave-uniform LDS reads a knot — each an issue
+// slot of the lone wavefront, as dear as an FMA (profiles/fwd_gains/premise.txt) — lane l reads the 16-byte unit min(l & 15, 11)
+// of the record with ONE ds_read_b128, and v_fmac_f64_dpp row_newbcast:n takes value i from lane i / 2 of the reader's row, at
+// the price of a plain FMA. Lanes 12 - 15 repeat unit 11 (nobody names them): no lane reads past the record.
+// Only where the sweep is inlined into the kernel (the wide unit): measured there (profiles/fwd_gains/). The dense and packed
+// units, whose sweep is a function of its own, keep the broadcast reads, and their code is what it was.
+#if !defined(TSAT_EMU) && !defined(TSAT_F32) && !defined(TSAT_DENSE)
+#define TSAT_FWD_GAIN_DPP 1
+constexpr int KDL = 2;     // doubles of the record a lane holds
+#else
+constexpr int KDL = KDW;   // emulator, float, dense and packed units: the whole record in every lane
+#endif
+// what the roll-out of one knot reads from the staged chunk: nominal (x,u) record, gains K and d, three field rows
+template <typename real> struct KnotIn { real xu[XUW], kd[KDL], b0[3], b1[3], b2[3]; };
+// where this lane's share of knot 0's gain record lies in the chunk buffer `fb` (formed once per chunk; fwd_knot_load steps it)
 template <typename real>
-TSAT_DEV KnotIn<real> fwd_knot_load(const real* fb, int kk) {
+TSAT_DEV const real* fwd_kd_lane(const real* fb) {
+#ifdef TSAT_FWD_GAIN_DPP
+  const int unit = TSAT_LANE() & 15;
+  return fb + FB_KD + 2 * (unit < KDW / 2 - 1 ? unit : KDW / 2 - 1);
+#else
+  return fb + FB_KD;
+#endif
+}
+template <typename real>
+TSAT_DEV KnotIn<real> fwd_knot_load(const real* fb, const real* kdl, int kk) {
   KnotIn<real> in;
   const real* xu = fb + FB_XU + kk * XUW;
-  const real* kd = fb + FB_KD + kk * KDW;
+  const real* kd = kdl + kk * KDW;
   for (int i = 0; i < XUW; ++i) in.xu[i] = xu[i];
+#ifdef TSAT_FWD_GAIN_DPP
+  static_assert(KDW % 2 == 0 && (FB_KD * sizeof(real)) % 16 == 0 && (L_FWD * sizeof(real)) % 16 == 0 && (FB_SIZE * sizeof(real)) % 16 == 0,
+                "a gain record is whole, aligned 16-byte units");
+  typedef real v2 __attribute__((ext_vector_type(2)));
+  const v2 v = *reinterpret_cast<const v2*>(kd);
+  in.kd[0] = v.x; in.kd[1] = v.y;
+#else
   for (int i = 0; i < KDW; ++i) in.kd[i] = kd[i];
+#endif
   fwd_brows<real>(fb, kk, in.b0, in.b1, in.b2);
   return in;
 }
@@ -1103,6 +1138,7 @@ TSAT_FWD void forward_sweep(TPtrs<real> p, int N, int n_tab, int closed, int n_c
     real* fb = lds + L_FWD + cur * FB_SIZE;
     real* fbn = lds + L_FWD + ((FWD_NBUF == 2) ? (1 - cur) : 0) * FB_SIZE;
     if (FWD_NBUF == 2 && nkn > 0) fwd_chunk_issue<real>(fbn, KDg, XUg, tr, kn, nkn, closed);
+    const real* kdl = fwd_kd_lane<real>(fb);
     // The staged records are read one knot AHEAD: knot kk + 1's nominal record, gains and field rows are requested from LDS
     // before knot kk is rolled out and have long arrived when its turn comes. Left to the compiler the reads sit right in front
     // of their first use (register pressure), nine exposed LDS latencies per knot on the critical path of the launch.
@@ -1110,7 +1146,6 @@ TSAT_FWD void forward_sweep(TPtrs<real> p, int N, int n_tab, int closed, int n_c
       const real* xu = kin.xu;
       real u[3] = {xu[7], xu[8], xu[9]};
       if (closed) {
-        const real* kd = kin.kd;
         real dx[7];
         if (ES) {
           // quaternion_error(new, nominal) = [dw; MRP(q_nom^-1 (x) q_new)]  (src/quaternion_toolbox.jl:58-75)
@@ -1126,11 +1161,18 @@ TSAT_FWD void forward_sweep(TPtrs<real> p, int N, int n_tab, int closed, int n_c
         } else {
           for (int i = 0; i < 7; ++i) dx[i] = x[i] - xu[i];
         }
+        // u_c = ubar_c + sum_j K[c][j] dx_j + alpha d_c: per c the terms in this order, every one of them an FMA
+#ifdef TSAT_FWD_GAIN_DPP
+        static_assert(sizeof(real) == 8, "the DPP block is fp64");
+        if constexpr (BwdCfg<ES>::NH == 6) { TSAT_FG_6(); } else { TSAT_FG_7(); }
+#else
+        const real* kd = kin.kd;
         for (int c = 0; c < 3; ++c) {
           real v = u[c];
           for (int j = 0; j < BwdCfg<ES>::NH; ++j) v += kd[c * 7 + j] * dx[j];
           u[c] = v + alpha * kd[21 + c];
         }
+#endif
       }
       if (lane < n_cand) {
         TSAT_GLOBAL real* cr = Cg + (size_t)(k0 + kk) * XUW;
@@ -1147,19 +1189,19 @@ TSAT_FWD void forward_sweep(TPtrs<real> p, int N, int n_tab, int closed, int n_c
     // the dense double build (256 registers in all, no AGPRs) cannot hold two read-ahead sets of 43 doubles without spilling
     // into this loop; its second wavefront per SIMD covers part of the LDS latency instead
     for (int kk = 0; kk < nk; ++kk) {
-      const KnotIn<real> A = fwd_knot_load<real>(fb, kk);
+      const KnotIn<real> A = fwd_knot_load<real>(fb, kdl, kk);
       knot(A, kk);
     }
 #else
-    KnotIn<real> A = fwd_knot_load<real>(fb, 0);
+    KnotIn<real> A = fwd_knot_load<real>(fb, kdl, 0);
     for (int kk = 0; kk < nk; kk += 2) {
       TSAT_WAIT_LDS();               // A has arrived (requested a whole knot ago); only then the next batch is put in flight
-      const KnotIn<real> B = fwd_knot_load<real>(fb, (kk + 1 < nk) ? kk + 1 : kk);
+      const KnotIn<real> B = fwd_knot_load<real>(fb, kdl, (kk + 1 < nk) ? kk + 1 : kk);
       TSAT_SCHED_FENCE();
       knot(A, kk);
       if (kk + 1 < nk) {
         TSAT_WAIT_LDS();
-        A = fwd_knot_load<real>(fb, (kk + 2 < nk) ? kk + 2 : kk + 1);
+        A = fwd_knot_load<real>(fb, kdl, (kk + 2 < nk) ? kk + 2 : kk + 1);
         TSAT_SCHED_FENCE();
         knot(B, kk + 1);
       }
@@ -1612,9 +1654,7 @@ TSAT_PHASE BwdOut<real> riccati_chunk(TSAT_GLOBAL real* KDg, int k0, int nk, rea
 // of lane r's column, the same DPP read with the roles of register and lane exchanged — so the cost-to-go the recursion works
 // with is symmetric to the last bit. The arithmetic is double whatever the storage type of the records.
 // --------------------------------------------------------------------------------------------------
-#ifndef TSAT_EMU
-#include "tsat_riccati_dpp.inc"
-#endif
+// (the generated blocks, tsat_riccati_dpp.inc, are included ahead of the forward sweep, which uses one of them too)
 template <int NH> struct RowState { double Sc[NH + 1]; };
 #ifdef TSAT_EMU
 // emulator: the DPP reads of a knot become three exchanges through scratch blocks — every lane publishes the registers the
