@@ -25,6 +25,7 @@ namespace tsat_emu { int lane(); void sync(); void* lds(); double* xch(); }
 #define TSAT_DEV inline
 #define TSAT_PHASE inline
 #define TSAT_FWD inline
+#define TSAT_JAC inline
 #define TSAT_GLOBAL
 #define TSAT_CONSTMEM
 #define TSAT_LANE() (tsat_emu::lane())
@@ -52,6 +53,15 @@ namespace tsat_emu { int lane(); void sync(); void* lds(); double* xch(); }
 #define TSAT_FWD __device__ __noinline__
 #else
 #define TSAT_FWD __device__ __forceinline__
+#endif
+// The Jacobian lanes of a backward chunk use every register there is. As a function of their own they save and restore the
+// caller's on every call, once per chunk: in the wide build (512 registers, one wavefront per SIMD) they are inlined into
+// backward_sweep, which pays that round trip once per sweep and keeps it out of the chunk loop (profiles/bwd_chunk/README.md).
+// The 256-register builds, which have no AGPRs to park the sweep's own state in, keep the call and the code they had.
+#if defined(TSAT_DENSE) || defined(TSAT_F32)
+#define TSAT_JAC __device__ __noinline__
+#else
+#define TSAT_JAC __device__ __forceinline__
 #endif
 // HBM pointers that cross a (non-inlined) function boundary must carry their address space, otherwise every
 // access through them is a flat_* instruction (both memory pipes, both wait counters) instead of global_*.
@@ -1432,7 +1442,7 @@ TSAT_DEV jac_t* rec_base() { return reinterpret_cast<jac_t*>(lds_base<cfg_real>(
 // Jacobian lanes of one backward chunk: lane l linearises knot k0 + l and leaves its record in LDS
 // --------------------------------------------------------------------------------------------------
 template <typename real, int INTEG, int DIAGJ, int ES>
-TSAT_PHASE void jacobian_chunk(TPtrs<real> p, int N, int n_tab, int k0, int nk, real mu) {
+TSAT_JAC void jacobian_chunk(TPtrs<real> p, int N, int n_tab, int k0, int nk, real mu) {
   const int lane = TSAT_LANE();
   if (lane < nk) {
     const Traj<real> tr = load_traj<real>(N, n_tab, p.bt);
@@ -1795,7 +1805,7 @@ TSAT_DEV bool riccati_row_step(RowState<NH>& st, const RowIn<NH>& in, const RowR
 }
 
 // The recursion over one chunk whose records are in LDS at L_REC (one-trajectory builds; last knot first). S~ comes from and
-// goes back to L_ST (row stride 9) between chunks: jacobian_chunk, a function of its own, runs in between.
+// goes back to L_ST (row stride 9) between chunks: the Jacobian lanes of the next chunk (jacobian_chunk) run in between.
 template <typename real, int NH, typename R>
 TSAT_PHASE BwdOut<real> riccati_rows(TSAT_GLOBAL real* KDg, int k0_, int nk_, real rho_, acc_t dV1, acc_t dV2) {
   // (arguments of a non-inlined function arrive in VGPRs: the chunk bounds are said to be wave-uniform, the loop below is scalar)
