@@ -605,6 +605,40 @@ int  tsat_mpc_run_held_gg(tsat_handle* h, const tsat_options* o, const tsat_tvlq
                        const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
                        int32_t* n_clipped, float* solve_ms, const double* Rtab, double gm);
 
+/* tsat_mpc_run_held / tsat_mpc_run_held_gg FED MEASUREMENTS: the two places at which the held loop reads the plant's state — the
+ * x0 the solve of a block starts from, and the state the held steps' U_j + K_j dx is evaluated on — read the sensor of the sensed
+ * ensembles (tsat_sensor_options above) instead. The true state and the state the solver is given become two different things.
+ * Everything not named here is the parent's, operation for operation: blocks, the j = 0 rule, the clip, the dispersed RK4 plant
+ * step with the draws of stages 0..3, the table clock, the shift, n_clipped, tsat_mpc_tally, and the statistic, which is evaluated
+ * on the TRUE state. s: control step RELATIVE TO THE CALL, kappa = step0 + s the generator's knot, x_s the true state:
+ *   m_s = (w_m, q_m) of x_s      the raw measurement of the sensed ensembles, word for word (w_m = x[0:3] + bw + n_w,
+ *                                q_m = x[3:7] (x) dq(ba + n_a), the th == 0 select); n_w, n_a from stage index 4 — counters 16, 17 —
+ *                                of (generator id, kappa) at s->sigma_gyro / s->sigma_att, key po->noise_seed, drawn only when
+ *                                po->noise_mode == 1 (biases apply either way)
+ *   y_s = m_s (latency 0), m_max(s-1, 0) (latency 1): the first step of a call sees its own measurement
+ *   block at s_b: the solve starts from x0 := y_{s_b} (warm start and tau0 as the parent); step j = 0 applies U_0; step j > 0 with
+ *                 feedback applies U_j + K_j dx, dx the solver's own state difference between y_s and X_j; without, U_j
+ *   the plant advances the TRUE state: X_hist holds true states, Y_hist[s] = y_s, what that step's command or solve used
+ * The loop has no law that reads the field: sigma_mag and bm (sensor rows 6..8) are validated and nothing reads them; no stage-5
+ * block is generated.
+ *   Rtab, gm   as tsat_mpc_run_held_gg; Rtab NULL is allowed iff gm == 0: the kernel without the gravity rows
+ *   sensor     9 x T or NULL (zeros): bw, ba, bm of each trajectory (TSAT_SENSOR_W)
+ *   Y_hist     7 x n_steps x T out, may be NULL
+ * While the call runs the resident x0 carries measurements; the true state lives in a workspace of the handle. The last block
+ * writes the TRUE x_{n_steps} back (host copies refreshed), so afterwards the resident batch is in the state tsat_mpc_run_held
+ * leaves: tsat_tvlqr_resident, tsat_batch_run and a continuation keep their meaning. A continuation (step0 = the steps made, no
+ * upload) equals one longer run when the first call's n_steps is a multiple of R AND latency = 0: latency 1 RESTARTS ITS MEMORY
+ * with every call (the first step of the second call sees its own measurement, where the longer run sees the step before).
+ * With sensor NULL or zero, zero sigmas and latency 0 the call repeats tsat_mpc_run_held (Rtab NULL) or tsat_mpc_run_held_gg:
+ * x + 0 + 0 z and x (x) (1,0,0,0) are exact, as argued for the ensembles.
+ * Rejected with -1 (text in tsat_last_error; nothing is launched and no workspace grows): everything the sensed ensembles reject of
+ * s and sensor (M = 1: the text of a non-finite entry carries (t, 0)); Rtab NULL with gm != 0; and everything the parents reject. */
+int  tsat_mpc_run_held_sensed(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                       int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo, const double* sat_hi,
+                       const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
+                       int32_t* n_clipped, float* solve_ms, const double* Rtab, double gm,
+                       const tsat_sensor_options* s, const double* sensor, double* Y_hist);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Sweep exchange across GPUs. The reference's Monte-Carlo is a serial loop whose iterations share nothing but the result
  * lists they append to (src/monte_carlo.jl:52-66, 199-235; src/paper_images/heatmap.jl:114-243). Here each rank — one

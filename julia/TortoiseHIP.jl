@@ -620,10 +620,11 @@ function write_results(dir, n, A, sim_states, sim_control_inputs, B_ECI_total, t
 end
 
 # Entry points of include/tortoise_hip.h deliberately left without a binding here (read by tests/test_julia_shim.py): the sensed
-# ensembles. They take a `tsat_sensor_options*` (three Float64 — sigma_gyro, sigma_att, sigma_mag —, then Int32 latency and Int32
-# reserved: 32 bytes), a struct the static cross-check of this shim against the header has no mapping for, so a `ccall` with a
-# `Ref` to its mirror could not be held to the header; they stay unbound until it can. The Python layer binds them
-# (tracking.attitude_ensemble_sensed, tracking.attitude_ensemble_pd_sensed).
-const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsat_pd_ensemble_sensed]
+# ensembles and the held re-planning loop fed measurements. They take a `tsat_sensor_options*` (three Float64 — sigma_gyro,
+# sigma_att, sigma_mag —, then Int32 latency and Int32 reserved: 32 bytes), a struct the static cross-check of this shim against
+# the header has no mapping for, so a `ccall` with a `Ref` to its mirror could not be held to the header; they stay unbound until
+# it can. The Python layer binds them (tracking.attitude_ensemble_sensed, tracking.attitude_ensemble_pd_sensed,
+# mpc.receding_horizon_held_sensed).
+const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsat_pd_ensemble_sensed, :tsat_mpc_run_held_sensed]
 
 end # module

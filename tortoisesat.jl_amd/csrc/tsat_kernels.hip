@@ -17,6 +17,7 @@
 #include "tsat_host_pack.hpp"
 #include "tsat_mpc_held.hpp"
 #include "tsat_gg.hpp"
+#include "tsat_mpc_sensed.hpp"
 
 using namespace tsat;
 
@@ -46,6 +47,10 @@ hipError_t tsat_launch_mpc_held_shift(const MpcArgs<double>& m, int r, hipStream
 // the pack of the orbit table and the hold under gravity-gradient torque of tsat_mpc_run_held_gg (tsat_kernels_gg.hip)
 hipError_t tsat_launch_gg_pack(const double* R, double gm, double* GT, int64_t rows, hipStream_t stream);
 hipError_t tsat_launch_mpc_held_gg(const MpcHeldGgArgs<double>& a, int error_state, hipStream_t stream);
+// the pack (bias records, first measurement) and the hold commanding from measurements of tsat_mpc_run_held_sensed
+// (tsat_kernels_mpc_sensed.hip)
+hipError_t tsat_launch_mpc_sensed_pack(const MpcSensedArgs<double>& a, const double* sensor, hipStream_t stream);
+hipError_t tsat_launch_mpc_sensed(const MpcSensedArgs<double>& a, int error_state, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -140,6 +145,8 @@ struct tsat_handle {
          WS_AG_CHK, WS_MPC_TALLY, WS_ENDGAME,
          WS_MPCD_PLANT, WS_MPCD_PL, WS_MPCD_SAT, WS_MPCD_NID, WS_MPCD_REC, WS_MPCD_ST, WS_MPCD_CLIP,   // tsat_mpc_run_dispersed
          WS_GG_GT,             // packed gravity rows of tsat_tvlqr_ensemble_gg / tsat_mpc_run_held_gg
+         WS_MPCS_XT, WS_MPCS_SN, WS_MPCS_IN, WS_MPCS_Y,   // tsat_mpc_run_held_sensed: true state + last measurement [14][T], biases
+                               // [9][T], the uploaded sensor array, Y_hist
          WS_COUNT };
   void* ws[WS_COUNT] = {};
   size_t ws_bytes[WS_COUNT] = {};
@@ -624,12 +631,18 @@ int tsat_mpc_tally(tsat_handle* h, int64_t* tally) {
 namespace {
 // the loop of tsat_mpc_run_dispersed (replan_every = 0: a solve and the one-wavefront-per-trajectory step kernel per control step)
 // and of tsat_mpc_run_held (replan_every >= 1: a solve, the lane-per-trajectory hold and the plan shift per block); with
-// `gravity` the hold is the one of tsat_mpc_run_held_gg (Rtab [n_btab][n_tab][3] of the resident batch, gm)
+// `gravity` the hold is the one of tsat_mpc_run_held_gg (Rtab [n_btab][n_tab][3] of the resident batch, gm); with `sc` the hold of
+// tsat_mpc_run_held_sensed, which reads measurements (tsat_mpc_sensed.hpp) — through the gravity rows when `gravity`
+struct SensedCall {
+  const tsat_sensor_options* s;
+  const double* sensor;      // 9 x T or null
+  double* Y_hist;            // 7 x n_steps x T or null
+};
 int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps,
                    int64_t step0, int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo,
                    const double* sat_hi, const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last,
                    tsat_tvlqr_stats* stats, int32_t* n_clipped, float* solve_ms, bool gravity = false, const double* Rtab = nullptr,
-                   double gm = 0.0) {
+                   double gm = 0.0, const SensedCall* sc = nullptr) {
   if (!h || !o || !po) return -1;
   const bool held = replan_every != 0;
   if (!h->uploaded) return fail(h, -1, "tsat_batch_upload has not been called");
@@ -642,6 +655,10 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   if (gravity) {
     const std::string badg = check_gravity(Rtab, gm, (int64_t)n_rows);
     if (!badg.empty()) return fail(h, -1, badg);
+  }
+  if (sc) {
+    const std::string bads = check_mpc_sensed(sc->s, sc->sensor, h->T, Rtab, gm);
+    if (!bads.empty()) return fail(h, -1, bads);
   }
   if (!X_hist || !U_hist) return fail(h, -1, "null array");
   TSAT_HIP(h, hipSetDevice(h->dev));
@@ -666,6 +683,14 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   MpcDispRec* dRec = (MpcDispRec*)ws_get(h, tsat_handle::WS_MPCD_REC, T * sizeof(MpcDispRec));
   tsat_tvlqr_stats* dSt = (tsat_tvlqr_stats*)ws_get(h, tsat_handle::WS_MPCD_ST, T * sizeof(tsat_tvlqr_stats));
   int* dClip = (int*)ws_get(h, tsat_handle::WS_MPCD_CLIP, T * sizeof(int));
+  double *dXT = nullptr, *dSN = nullptr, *dSIn = nullptr, *dY = nullptr;
+  if (sc) {
+    dXT = (double*)ws_get(h, tsat_handle::WS_MPCS_XT, T * MSX_W * 8);
+    dSN = (double*)ws_get(h, tsat_handle::WS_MPCS_SN, T * SNW * 8);
+    dSIn = sc->sensor ? (double*)ws_get(h, tsat_handle::WS_MPCS_IN, T * SNW * 8) : nullptr;
+    dY = (double*)ws_get(h, tsat_handle::WS_MPCS_Y, nU / 3 * 7 * 8);
+    if (!dXT || !dSN || (sc->sensor && !dSIn) || !dY) return fail(h, -10, std::string("device allocation failed in ") + name);
+  }
   // the gravity call: the packed rows are the handle's, the raw orbit table lives until the pack has run
   double* dGT = gravity ? tsat_ws_gravity(h, n_rows * 4 * 8) : nullptr;
   struct Raw {
@@ -686,6 +711,7 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   if (plant) TSAT_HIP(h, hipMemcpy(dPlant, plant, T * TSAT_PLANT_W * 8, hipMemcpyHostToDevice));
   if (noise_id) TSAT_HIP(h, hipMemcpy(dNid, noise_id, T * sizeof(long long), hipMemcpyHostToDevice));
   if (gravity) TSAT_HIP(h, hipMemcpy(dR.p, Rtab, n_rows * 3 * 8, hipMemcpyHostToDevice));
+  if (dSIn) TSAT_HIP(h, hipMemcpy(dSIn, sc->sensor, T * SNW * 8, hipMemcpyHostToDevice));
   TSAT_HIP(h, hipMemsetAsync(dTally, 0, T * 4 * sizeof(long long), h->stream));
   h->mpc_tally_T = (int64_t)T;
   const KArgs<double> a = solve_args(h, o);
@@ -705,16 +731,30 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   md.noisy = po->noise_mode; md.step0 = (long long)step0; md.rec = dRec;
   mh.KD = h->KD; mh.feedback = feedback;
   MpcHeldGgArgs<double> mg = {};
+  MpcSensedArgs<double> ms = {};
+  if (sc) {
+    ms.GT = gravity ? dGT : nullptr; ms.XT = dXT; ms.HY = dY;
+    ms.s.SN = dSN; ms.s.Mp = (int)T; ms.s.sgy = sc->s->sigma_gyro; ms.s.sat = sc->s->sigma_att; ms.s.smg = sc->s->sigma_mag;
+    ms.s.latency = sc->s->latency; ms.s.k0 = e.k0; ms.s.k1 = e.k1;
+  }
   int rc = 0;
   if (hipEventRecord(h->ev0, h->stream) != hipSuccess) rc = -10;
   if (held) {   // the pack, then solve, hold and shift per block queued back to back; the stream orders them
     if (tsat_launch_mpc_held_pack(mh, dPlant, h->stream) != hipSuccess) rc = -10;
     if (!rc && gravity && tsat_launch_gg_pack(dR.p, gm, dGT, (int64_t)n_rows, h->stream) != hipSuccess) rc = -10;
+    if (sc) {   // biases, the true state to its own record, the first measurement into the record the solve reads
+      ms.h = mh;
+      if (!rc && tsat_launch_mpc_sensed_pack(ms, dSIn, h->stream) != hipSuccess) rc = -10;
+    }
     for (int s = 0; s < n_steps && !rc; s += replan_every) {
       if (launch_solve(h, o, a) != hipSuccess) rc = -10;
       m.step = s;
       mh.r = std::min<int>(replan_every, n_steps - s);
-      if (gravity) {   // the hold through the gravity rows, then the held loop's own plan shift
+      if (sc) {        // the hold on measurements (with or without the gravity rows), then the held loop's own plan shift
+        ms.h = mh;
+        if (!rc && tsat_launch_mpc_sensed(ms, o->error_state, h->stream) != hipSuccess) rc = -10;
+        if (!rc && tsat_launch_mpc_held_shift(m, mh.r, h->stream) != hipSuccess) rc = -10;
+      } else if (gravity) {   // the hold through the gravity rows, then the held loop's own plan shift
         mg.h = mh; mg.GT = dGT;
         if (!rc && tsat_launch_mpc_held_gg(mg, o->error_state, h->stream) != hipSuccess) rc = -10;
         if (!rc && tsat_launch_mpc_held_shift(m, mh.r, h->stream) != hipSuccess) rc = -10;
@@ -733,6 +773,7 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   if (rc) return rc;
   if (stats) TSAT_HIP(h, hipMemcpy(stats, dSt, T * sizeof(tsat_tvlqr_stats), hipMemcpyDeviceToHost));
   if (n_clipped) TSAT_HIP(h, hipMemcpy(n_clipped, dClip, T * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (sc && sc->Y_hist) TSAT_HIP(h, hipMemcpy(sc->Y_hist, dY, nU / 3 * 7 * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 }  // namespace
@@ -761,6 +802,17 @@ int tsat_mpc_run_held_gg(tsat_handle* h, const tsat_options* o, const tsat_tvlqr
   if (replan_every < 1) return fail(h, -1, check_mpc_held(replan_every, feedback, 2));
   return mpc_plant_loop(h, "tsat_mpc_run_held_gg", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id,
                         X_hist, U_hist, stats_last, stats, n_clipped, solve_ms, true, Rtab, gm);
+}
+
+int tsat_mpc_run_held_sensed(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                             int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo, const double* sat_hi,
+                             const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
+                             int32_t* n_clipped, float* solve_ms, const double* Rtab, double gm, const tsat_sensor_options* s,
+                             const double* sensor, double* Y_hist) {
+  if (replan_every < 1) return fail(h, -1, check_mpc_held(replan_every, feedback, 2));
+  const SensedCall sc = {s, sensor, Y_hist};
+  return mpc_plant_loop(h, "tsat_mpc_run_held_sensed", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id,
+                        X_hist, U_hist, stats_last, stats, n_clipped, solve_ms, Rtab != nullptr, Rtab, gm, &sc);
 }
 
 int tsat_batch_export_device(tsat_handle* h, void* X_dev, void* U_dev, void* K_dev, void* stats_dev) {

@@ -52,9 +52,10 @@ def _noise_options(lib, noise_opts):
 
 
 def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
-                gravity=None):
-    """``tsat_mpc_run_dispersed`` (``replan_every`` None), ``tsat_mpc_run_held`` or — with ``gravity`` = (Rtab, gm) —
-    ``tsat_mpc_run_held_gg`` on ``prob``: marshalling of all three"""
+                gravity=None, sensed=None):
+    """``tsat_mpc_run_dispersed`` (``replan_every`` None), ``tsat_mpc_run_held``, — with ``gravity`` = (Rtab, gm) —
+    ``tsat_mpc_run_held_gg`` or — with ``sensed`` = (SensorOptions, sensor (T, 9) or None) and ``gravity`` (Rtab may be None) —
+    ``tsat_mpc_run_held_sensed`` on ``prob``: marshalling of all four"""
     lib = _abi.load()
     b = prob.arrays
     o = solver.opts.to_abi(b.N, b.n_tab, prob.integrator, prob.terminal_mask, error_state=prob.error_state)
@@ -85,6 +86,20 @@ def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise
     head = (solver._h, C.byref(o), C.byref(po), int(n_steps), int(step0))
     tail = (d(plant), d(lo), d(hi), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int64)), d(Xh), d(Uh),
             st.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p), _abi.as_ip(ncl), C.byref(ms))
+    if sensed is not None:
+        so, sensor = sensed
+        Rtab = None
+        if gravity[0] is not None:
+            from .tracking import orbit_table
+            Rtab = orbit_table(b, gravity[0])
+        if sensor is not None:
+            sensor = c(sensor)
+            if sensor.shape != (T, 9):
+                raise ValueError("sensor must be (T, 9)")
+        Yh = np.empty((T, n_steps, 7))
+        solver._check(lib.tsat_mpc_run_held_sensed(*head, int(replan_every), int(feedback), *tail, d(Rtab), float(gravity[1]), C.byref(so),
+                                                   d(sensor), d(Yh)), "tsat_mpc_run_held_sensed")
+        return dict(X_hist=Xh, U_hist=Uh, stats=st, tracking_stats=ts, n_clipped=ncl, ms=float(ms.value), Y_hist=Yh)
     if gravity is not None:
         from .tracking import orbit_table
         Rtab = orbit_table(b, gravity[0])
@@ -137,15 +152,44 @@ def receding_horizon_held_gg(prob, solver, n_steps, replan_every, Rtab, gm=3.986
     return r
 
 
+def receding_horizon_held_sensed(prob, solver, n_steps, replan_every, sensor_opts=None, sensor=None, latency=0, Rtab=None, gm=0.0,
+                                 feedback=True, plant=None, sat=None, noise_opts=None, noise_id=None, step0=0, max_outer=1, max_inner=3,
+                                 upload=True):
+    """``receding_horizon_held`` (``Rtab`` None, ``gm`` 0) or ``receding_horizon_held_gg`` FED MEASUREMENTS
+    (``tsat_mpc_run_held_sensed``): every block's solve starts from, and the held steps' gains act on, a measurement of the true
+    state — gyro and attitude noise of ``sensor_opts`` (None = the ideal sensor, a dict of ``sigma_gyro`` / ``sigma_att`` /
+    ``sigma_mag``, or a ready ``_abi.SensorOptions``, whose latency then counts), biases ``sensor`` ((T, 9): one realisation of
+    ``tracking.disperse_sensor`` per trajectory; None = zeros), ``latency`` 0 or 1 control steps. The plant flies and the statistic
+    judges the true state. The sensor draws are made when ``noise_opts`` switches the generated noise on, under its seed. The
+    magnetometer figures are accepted and unused: the loop has no law that reads the field. A continuation equals one longer run
+    only with ``latency=0`` (and whole blocks): latency 1 restarts its memory with every call. Returns the dict of
+    ``receding_horizon_held`` plus ``Y_hist`` (T, n_steps, 7), the measurement each step's command or solve used."""
+    if isinstance(sensor_opts, _abi.SensorOptions):
+        so = _abi.SensorOptions.from_buffer_copy(sensor_opts)
+    else:
+        kw = dict(sensor_opts or {})
+        unknown = set(kw) - {"sigma_gyro", "sigma_att", "sigma_mag"}
+        if unknown:
+            raise ValueError(f"unknown tsat_sensor_options field(s) {sorted(unknown)}")
+        so = _abi.SensorOptions(sigma_gyro=kw.get("sigma_gyro", 0.0), sigma_att=kw.get("sigma_att", 0.0), sigma_mag=kw.get("sigma_mag", 0.0),
+                                latency=int(latency), reserved=0)
+    r = _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
+                    gravity=(Rtab, gm), sensed=(so, sensor))
+    r["n_solves"] = -(-int(n_steps) // int(replan_every))
+    return r
+
+
 _PER_SLEW = ("x0", "xf", "btab_idx", "tau0", "dtau", "dt", "Jmat", "Qd", "Qfd", "Rd", "ulo", "uhi", "U0")
 
 
-def tile_realisations(batch, M, plant=None, noise_id0=None, sat=None):
+def tile_realisations(batch, M, plant=None, noise_id0=None, sat=None, sensor=None):
     """M realisations per slew laid out as one batch of T M trajectories, slew-major (t M + m): the per-slew arrays repeated, the
     field tables shared through ``btab_idx``. ``plant`` (T, M, 21) straight from ``tracking.disperse_plant``; generator ids
     ``noise_id0[t] + m`` (default t M + m). Realisation (t, m) of ``receding_horizon_dispersed(BatchProblem.from_arrays(tiled),
     solver, n, **kw)`` then flies the plant and draws the noise of realisation (t, m) of ``tracking.attitude_ensemble_dispersed``.
-    Returns (tiled batch, kw) with kw = dict(plant (T M, 21) or None, noise_id (T M,), sat)."""
+    ``sensor`` (T, M, 9) straight from ``tracking.disperse_sensor``: the biases of ``receding_horizon_held_sensed``, realisation
+    (t, m) those of realisation (t, m) of ``tracking.attitude_ensemble_sensed``.
+    Returns (tiled batch, kw) with kw = dict(plant (T M, 21) or None, noise_id (T M,), sat) and, when given, sensor (T M, 9)."""
     T, M = batch.T, int(M)
     if batch.Btab is None:
         raise ValueError("the tiled batch shares host field tables through btab_idx: batch.Btab must be an array")
@@ -165,4 +209,10 @@ def tile_realisations(batch, M, plant=None, noise_id0=None, sat=None):
     ids = np.ascontiguousarray((id0[:, None] + np.arange(M, dtype=np.int64)[None, :]).reshape(T * M))
     if sat is not None:
         sat = tuple(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))[idx]) for v in sat)
-    return tiled, dict(plant=plant, noise_id=ids, sat=sat)
+    kw = dict(plant=plant, noise_id=ids, sat=sat)
+    if sensor is not None:
+        sensor = np.asarray(sensor, dtype=np.float64)
+        if sensor.shape != (T, M, 9):
+            raise ValueError("sensor must be (T, M, 9)")
+        kw["sensor"] = np.ascontiguousarray(sensor.reshape(T * M, 9))
+    return tiled, kw
