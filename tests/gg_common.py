@@ -224,7 +224,7 @@ class EmuGg:
 
     def __init__(self, abi):
         d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "-f", "gg.mk", "libtsat_emu_gg.so"], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", d, "libtsat_emu_gg.so"], stdout=subprocess.DEVNULL)
         self.lib = C.CDLL(os.path.join(d, "libtsat_emu_gg.so"))
         self.abi = abi
 

@@ -25,7 +25,7 @@ class EmuLineSearch(Emu):
     def __init__(self, abi, dense=False):
         d = os.path.join(ROOT, "tests", "emu")
         name = "libtsat_emu_line_search_dense.so" if dense else "libtsat_emu_line_search.so"
-        subprocess.check_call(["make", "-C", d, "-f", "line_search.mk", name], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", d, name], stdout=subprocess.DEVNULL)
         self.lib = C.CDLL(os.path.join(d, name))
         self.lib.emu_solve_batch = self.lib.emu_ls_solve_batch      # Emu.solve: same arguments, this driver's launch
         self.abi = abi

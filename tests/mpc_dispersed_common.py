@@ -148,7 +148,7 @@ class EmuMpcDispersed:
 
     def __init__(self, abi):
         d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "-f", "mpc_dispersed.mk", "libtsat_emu_mpc_dispersed.so"], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", d, "libtsat_emu_mpc_dispersed.so"], stdout=subprocess.DEVNULL)
         self.lib = C.CDLL(os.path.join(d, "libtsat_emu_mpc_dispersed.so"))
         self.abi = abi
 

@@ -117,7 +117,7 @@ class EmuMpcHeld:
 
     def __init__(self, abi):
         d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "-f", "mpc_held.mk", "libtsat_emu_mpc_held.so"], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", d, "libtsat_emu_mpc_held.so"], stdout=subprocess.DEVNULL)
         self.lib = C.CDLL(os.path.join(d, "libtsat_emu_mpc_held.so"))
         self.abi = abi
 

@@ -168,7 +168,7 @@ class EmuMpcSensed:
 
     def __init__(self, abi):
         d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "-f", "mpc_sensed.mk", "libtsat_emu_mpc_sensed.so"], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", d, "libtsat_emu_mpc_sensed.so"], stdout=subprocess.DEVNULL)
         self.lib = C.CDLL(os.path.join(d, "libtsat_emu_mpc_sensed.so"))
         self.abi = abi
 

@@ -294,7 +294,7 @@ class EmuPd:
 
     def __init__(self, abi):
         d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "-f", "pd.mk", "libtsat_emu_pd.so"], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", d, "libtsat_emu_pd.so"], stdout=subprocess.DEVNULL)
         self.lib = C.CDLL(os.path.join(d, "libtsat_emu_pd.so"))
         self.abi = abi
 

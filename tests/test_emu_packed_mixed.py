@@ -1,6 +1,6 @@
 """CPU tier: the packed and fp32 builds of the solve kernel on the lane emulator (tests/emu, the very source hipcc compiles).
 
-packed (tsat_packed.hpp, -DTSAT_PACKED): PK_G trajectories per wavefront — bit-identical to the one-trajectory builds, whatever
+packed (tsat_packed.hpp, TSAT_BUILD 3 .. 7 of the table of builds in tsat_device.hpp): PK_G trajectories per wavefront — bit-identical to the one-trajectory builds, whatever
 the group is made of (partial last group, ragged horizons, trajectories that finish early, fail or diverge next to healthy ones).
 mixed precision (-DTSAT_JAC32, options.precision = 32): float linearisation (Jacobian lanes and knot records), everything else
 double — against the fp64 oracle at the bar of SURVEY.md §8(d) for fp32 (1e-3 + status agreement); in fact far inside it, with
@@ -9,7 +9,26 @@ the oracle's iteration counts.
 import numpy as np
 import pytest
 
-from conftest import assert_same_solution, oracle_options
+from conftest import Emu, assert_same_solution, oracle_options
+
+
+# the mixed-precision builds that no conftest fixture binds: one more library of tests/emu/Makefile each
+@pytest.fixture(scope="module")
+def emu_packed8_mixed(pkg):
+    """eight trajectories per wavefront at two wavefronts per SIMD, float linearisation (tsat_kernels_packed8_mixed.hip)"""
+    return Emu(pkg._abi, "libtsat_emu_packed8_mixed.so")
+
+
+@pytest.fixture(scope="module")
+def emu_packed4w_mixed(pkg):
+    """four per wavefront at one wavefront per SIMD, float linearisation (tsat_kernels_packed4w_mixed.hip): what precision = 32 takes from 2048 trajectories on"""
+    return Emu(pkg._abi, "libtsat_emu_packed4w_mixed.so")
+
+
+@pytest.fixture(scope="module")
+def emu_packed8w_mixed(pkg):
+    """eight per wavefront at one wavefront per SIMD, float linearisation (tsat_kernels_packed8w_mixed.hip): ... from 4097 to 8192"""
+    return Emu(pkg._abi, "libtsat_emu_packed8w_mixed.so")
 
 
 def _same_bits(a, b):
@@ -115,7 +134,8 @@ def test_packed_build_mixed_fates_in_one_group(pkg, ol, emu, emu_packed):
 
 @pytest.mark.parametrize("which,T,N,at", [("emu_packed", 11, 33, 6), ("emu_packed", 7, 20, 100), ("emu_packed8", 19, 21, 9),
                                           ("emu_packed_mixed", 10, 30, 5), ("emu_packed4w", 9, 21, 4), ("emu_packed8w", 19, 21, 9), ("emu_packed16w", 37, 21, 12),
-                                          ("emu_packed16w_mixed", 21, 30, 6)])
+                                          ("emu_packed16w_mixed", 21, 30, 6), ("emu_packed8_mixed", 19, 21, 9), ("emu_packed4w_mixed", 9, 21, 4),
+                                          ("emu_packed8w_mixed", 19, 21, 9)])
 def test_packed_endgame_is_the_same_solve(pkg, ol, request, monkeypatch, which, T, N, at):
     """tsat_set_endgame: once `at` trajectories are left, the wavefronts park theirs and a second launch finishes each on a
     wavefront of its own (tsat_resume_kernel_packed). Which ones get parked depends on how the waves were scheduled — here: on
@@ -158,7 +178,9 @@ def test_mixed_build_against_the_fp64_oracle(pkg, ol, emu_mixed):
         np.testing.assert_allclose(got["stats"]["cost"], ref["stats"]["cost"], rtol=1e-6)
 
 
-@pytest.mark.parametrize("which,T,N,es", [("emu_packed_mixed", 5, 37, 1), ("emu_packed_mixed", 4, 26, 0), ("emu_packed16w_mixed", 5, 37, 1), ("emu_packed16w_mixed", 18, 26, 0)])
+@pytest.mark.parametrize("which,T,N,es", [("emu_packed_mixed", 5, 37, 1), ("emu_packed_mixed", 4, 26, 0), ("emu_packed16w_mixed", 5, 37, 1), ("emu_packed16w_mixed", 18, 26, 0),
+                                          ("emu_packed8_mixed", 11, 37, 1), ("emu_packed4w_mixed", 5, 37, 1), ("emu_packed4w_mixed", 6, 26, 0),
+                                          ("emu_packed8w_mixed", 11, 37, 1), ("emu_packed8w_mixed", 18, 26, 0)])
 def test_mixed_packed_build_is_the_mixed_solve(pkg, ol, request, emu_mixed, which, T, N, es):
     """precision = 32 on large batches takes the packed mixed builds: bit-identical to the one-trajectory mixed build (sixteen per
     wavefront at one wavefront per SIMD: all sixteen knots of a pass in the record ring, nothing through the workspace)"""

@@ -9,8 +9,10 @@
 //                   through LDS in CK-knot chunks by coalesced 16-byte loads and read back as broadcasts.
 //   Jacobians      (parallel in k):   lane l linearises knot k0+l (analytic forward-mode through the RK stages)
 //                   and leaves [A|B] + cost gradients in LDS for the Riccati step; nothing is stored to HBM.
-//   Riccati sweep  (sequential in k): the 64 lanes are the elements of the 8x10 / 7x7 / 3x7 blocks; operands are
-//                   broadcast through LDS; 4 dependent stages per knot.
+//   Riccati sweep  (sequential in k): row-oriented — lane j of a 16-lane DPP row owns column j of [A|B] and of the
+//                   cost-to-go [S; s'], in registers; a value another lane holds is the `row_newbcast` operand of
+//                   the FMA that consumes it, so nothing goes through LDS inside a knot (riccati_row_step). One
+//                   trajectory runs on row 0; the packed builds run four side by side (tsat_packed.hpp).
 //   AL/cost/copy   (parallel in k):   lane-strided over knots + butterfly reductions.
 //
 // The file is plain C++ over a tiny lane abstraction so that tests/emu can run it on the CPU with 64 host
@@ -18,6 +20,140 @@
 #pragma once
 #include <stdint.h>
 #include "../../include/tortoise_hip.h"
+
+// --------------------------------------------------------------------------------------------------
+// The builds of the solve kernel — the ONE place that says what a build is. A build is a set of compile-time numbers (LDS size,
+// register budget and wavefronts per SIMD are per-kernel compile-time facts, so every build is a translation unit of its own);
+// two keys select them:
+//   TSAT_BUILD   the build id of the C ABI (tsat_set_kernel_variant, tsat_selected_build); undefined: 1
+//   TSAT_JAC32   defined: the mixed-precision build of the layout (options.precision = 32: float linearisation, jac_t below)
+// A unit (tsat_kernels_<name>.hip), an emulator library (tests/emu) and a sanitizer driver (tests/sanitize) of a build define
+// those two and nothing else about it. Results are bit-identical across the builds of a precision.
+//   TSAT_DENSE         the LDS budget of two wavefronts per SIMD (20 KB, 256 registers) in the one-trajectory carve-up below
+//   TSAT_PACKED        several trajectories per wavefront (tsat_packed.hpp)
+//   TSAT_PK_G          ... how many
+//   TSAT_PK_CK, _NBUF  knots per forward chunk and trajectory; 2 buffers: the next chunk is copied while this one is rolled out
+//   TSAT_PK_STORE      line-search candidates per trajectory whose roll-outs a sweep keeps in HBM at most
+//   TSAT_PK_WAVES      wavefronts per SIMD the kernels are compiled for
+//   TSAT_PK_LDS_BYTES  the wavefront's LDS block
+//   TSAT_PK_RING       knots of every trajectory resident in the LDS record ring during the Riccati recursion (of a pass's sixteen)
+//   TSAT_BUILD_TAIL    end of the build's symbol names: tsat_launch_solve_<layout>[_mixed]<tail>
+// --------------------------------------------------------------------------------------------------
+// X(id, layout, tail): the builds with a unit of their own (the wide build's kernels live in tsat_kernels.hip)
+#define TSAT_SOLVE_BUILDS(X) X(2, dense, ) X(3, packed, ) X(4, packed, 8) X(5, packed, 8w) X(6, packed, 16w) X(7, packed, 4w)
+// A command line that still spells a build by its numbers (-DTSAT_DENSE [-DTSAT_PACKED -DTSAT_PK_G=8 -DTSAT_PK_WAVES=1 ...], as the
+// test Makefiles did before the table) means the row with that layout, group size and wavefronts per SIMD; the numbers it repeats
+// must be the row's: the compiler reports a macro redefined to another value.
+#ifndef TSAT_BUILD
+#if !defined(TSAT_DENSE)
+#define TSAT_BUILD 1
+#elif !defined(TSAT_PACKED)
+#define TSAT_BUILD 2
+#elif TSAT_PK_WAVES == 1
+#define TSAT_BUILD (TSAT_PK_G == 16 ? 6 : TSAT_PK_G == 8 ? 5 : 7)
+#else
+#define TSAT_BUILD (TSAT_PK_G == 8 ? 4 : 3)
+#endif
+#endif
+#if TSAT_BUILD == 1
+// wide: one trajectory per wavefront, ONE wavefront per SIMD (512 registers, <= 40.6 KB of LDS). Up to 1024 trajectories — the
+// 256 CUs x 4 SIMDs of the GPU — it is 11 % faster than the dense build. No unit compiles it with TSAT_JAC32.
+#define TSAT_BUILD_TAIL
+#elif TSAT_BUILD == 2
+// dense: the same mapping with 25-knot Jacobian chunks (19 992 B of LDS) and at most 256 registers, so that TWO wavefronts fit a
+// SIMD. One wave per SIMD uses 45 % of the fp64 issue rate, two use 65 % (profiles/r01/lane_mask_ubench.txt): for batches that do
+// not fit the GPU at one wave per SIMD (> 1024 trajectories) this build is 16-28 % faster (profiles/r01/large_batch.txt).
+// Mixed: float records, 59-knot passes in the 20 KB that hold 29 double ones; serves batches below 2048 trajectories and, inside
+// the packed mixed builds, the last live trajectory of a wavefront.
+#define TSAT_DENSE 1
+#define TSAT_BUILD_TAIL
+#elif TSAT_BUILD >= 3 && TSAT_BUILD <= 7
+#define TSAT_DENSE 1
+#define TSAT_PACKED 1
+#define TSAT_PK_CK 4
+#if TSAT_BUILD == 3
+// packed: four trajectories per wavefront at two wavefronts per SIMD (the dense build's budget), double-buffered four-knot forward
+// chunks. Four knots of every trajectory stay in the record ring; mixed: eight, so half as many records travel through the
+// wavefront's workspace, at half the size. No longer chosen automatically.
+#define TSAT_PK_G 4
+#define TSAT_PK_NBUF 2
+#define TSAT_BUILD_TAIL
+#elif TSAT_BUILD == 4
+// packed8: EIGHT trajectories per wavefront at two per SIMD. With eight trajectories the LDS holds ONE four-knot forward chunk: the
+// copy of the next one waits for it (measured: 4 % faster than two double-buffered two-knot chunks, whose wait comes twice as often).
+#define TSAT_PK_G 8
+#define TSAT_PK_NBUF 1
+#define TSAT_BUILD_TAIL 8
+#elif TSAT_BUILD == 5
+// packed8w: eight trajectories per wavefront at ONE wavefront per SIMD (40 KB of LDS and the whole register file): twelve of a pass's
+// sixteen knot records stay in the LDS ring and four go through the HBM workspace (two wavefronts per SIMD: four stay, twelve go),
+// the forward chunks are double-buffered. For batches of 4097 .. 8192 trajectories, which are one round of the machine's 1024
+// SIMDs this way. Mixed: with float records ALL sixteen knots of a pass stay in the ring — nothing goes through the workspace.
+#define TSAT_PK_G 8
+#define TSAT_PK_NBUF 2
+#define TSAT_BUILD_TAIL 8w
+#elif TSAT_BUILD == 6
+// packed16w: SIXTEEN trajectories per wavefront (four line-search candidates each) at one wavefront per SIMD: 16384 trajectories
+// are one round of the machine's 1024 SIMDs, larger batches go through in rounds that start as wavefronts finish. One
+// single-buffered four-knot forward chunk (31 KB for sixteen trajectories).
+#define TSAT_PK_G 16
+#define TSAT_PK_NBUF 1
+#define TSAT_BUILD_TAIL 16w
+#else
+// packed4w: four trajectories per wavefront at one wavefront per SIMD: sixteen line-search candidates per trajectory, one backward
+// pass per wavefront, double-buffered forward chunks. For 2048 .. 4096 trajectories — one round of the machine's 1024 SIMDs — e.g.
+// the receding-horizon loop of BASELINE.json configs[4], whose short solves (200 knots, 1 x 3 budget) gain most: 3.95 -> 2.84 ms
+// per control step.
+#define TSAT_PK_G 4
+#define TSAT_PK_NBUF 2
+#define TSAT_BUILD_TAIL 4w
+#endif
+// sixteen trajectories have four candidate lanes each; the others keep six roll-outs: on the Monte-Carlo workloads the accepted
+// step is alpha = 2^-j with j <= 5 in 99.8 % of the iterations (tsat_launch_solve_packed)
+#if TSAT_PK_G == 16
+#define TSAT_PK_STORE 4
+#else
+#define TSAT_PK_STORE 6
+#endif
+// two wavefronts per SIMD: 20 KB hold 4 double records per trajectory or 8 float ones; one per SIMD: 40 KB hold 12 or all 16
+#if TSAT_BUILD <= 4
+#define TSAT_PK_WAVES 2
+#define TSAT_PK_LDS_BYTES 20480
+#ifdef TSAT_JAC32
+#define TSAT_PK_RING 8
+#else
+#define TSAT_PK_RING 4
+#endif
+#else
+#define TSAT_PK_WAVES 1
+#define TSAT_PK_LDS_BYTES 40960
+#ifdef TSAT_JAC32
+#define TSAT_PK_RING 16
+#else
+#define TSAT_PK_RING 12
+#endif
+#endif
+#else
+#error "TSAT_BUILD: 1 wide, 2 dense, 3 packed, 4 packed8, 5 packed8w, 6 packed16w, 7 packed4w"
+#endif
+// symbol of this build: TSAT_BUILD_NAME(tsat_launch_solve_packed) is tsat_launch_solve_packed_mixed8w in the mixed packed8w unit
+#ifdef TSAT_JAC32
+#define TSAT_BUILD_MIXED _mixed
+#else
+#define TSAT_BUILD_MIXED
+#endif
+#define TSAT_CAT3_(a, b, c) a##b##c
+#define TSAT_CAT3(a, b, c) TSAT_CAT3_(a, b, c)
+#define TSAT_BUILD_NAME(base) TSAT_CAT3(base, TSAT_BUILD_MIXED, TSAT_BUILD_TAIL)
+// the [2][3][2] table of a kernel template's variants — integrator (RK3, RK4) x inertia class (full, diagonal, isotropic) x
+// error-state mode — indexed [rk4][inertia_class][error_state]
+#define TSAT_VARIANT_TABLE(kern)                                         \
+  {{{kern<double, 3, 0, 0>, kern<double, 3, 0, 1>},                      \
+    {kern<double, 3, 1, 0>, kern<double, 3, 1, 1>},                      \
+    {kern<double, 3, 2, 0>, kern<double, 3, 2, 1>}},                     \
+   {{kern<double, 4, 0, 0>, kern<double, 4, 0, 1>},                      \
+    {kern<double, 4, 1, 0>, kern<double, 4, 1, 1>},                      \
+    {kern<double, 4, 2, 0>, kern<double, 4, 2, 1>}}}
 
 #ifdef TSAT_EMU
 #include <cmath>
@@ -58,7 +194,7 @@ namespace tsat_emu { int lane(); void sync(); void* lds(); double* xch(); }
 // caller's on every call, once per chunk: in the wide build (512 registers, one wavefront per SIMD) they are inlined into
 // backward_sweep, which pays that round trip once per sweep and keeps it out of the chunk loop (profiles/bwd_chunk/README.md).
 // The 256-register builds, which have no AGPRs to park the sweep's own state in, keep the call and the code they had.
-#if defined(TSAT_DENSE) || defined(TSAT_F32)
+#if defined(TSAT_DENSE)
 #define TSAT_JAC __device__ __noinline__
 #else
 #define TSAT_JAC __device__ __forceinline__
@@ -117,15 +253,9 @@ namespace tsat_emu { int lane(); void sync(); void* lds(); double* xch(); }
 
 namespace tsat {
 
-// Storage / arithmetic type of the translation unit's solve kernel: double (tsat_kernels.hip, tsat_kernels_dense.hip) or
-// float (tsat_kernels_f32.hip, -DTSAT_F32: options.precision = 32). The LDS carve-up below is counted in elements of this
-// type, so the fp32 build needs half the LDS per wavefront. Whatever the storage type, costs, expected reductions and the
-// line-search test are carried in double (acc_t): J ~ 1e4 has to resolve dJ ~ 1e-4.
-#ifdef TSAT_F32
-typedef float cfg_real;
-#else
+// Storage / arithmetic type of every solve kernel; the LDS carve-up below is counted in elements of it. Costs, expected
+// reductions and the line-search test are carried in acc_t: J ~ 1e4 has to resolve dJ ~ 1e-4.
 typedef double cfg_real;
-#endif
 typedef double acc_t;
 constexpr int RPU = 16 / (int)sizeof(cfg_real);   // reals per 16-byte copy unit: 2 (double) or 4 (float)
 // Storage / arithmetic type of the LINEARISATION: the Jacobian lanes and the knot records they leave for the Riccati recursion.
@@ -141,18 +271,8 @@ typedef cfg_real jac_t;
 #endif
 constexpr int RPUJ = 16 / (int)sizeof(jac_t);     // record values per 16-byte copy unit
 
-// The fp32 build comes in three LDS budgets, TSAT_OCC = wavefronts per SIMD it is laid out for (the compiler derives the
-// register budget from the LDS-limited occupancy): 2 -> <= 20 480 B, 3 -> <= 13 653 B, 4 -> <= 10 240 B per wavefront.
-#if defined(TSAT_F32) && !defined(TSAT_OCC)
-#define TSAT_OCC 2
-#endif
-
 constexpr int WAVE = 64;
-#if defined(TSAT_F32) && TSAT_OCC == 4
-constexpr int CK = 16;    // knots per forward-sweep LDS chunk
-#else
-constexpr int CK = 32;
-#endif
+constexpr int CK = 32;    // knots per forward-sweep LDS chunk
 constexpr int PSTRIDE = 64;
 // Line-search candidates whose rollouts are kept in HBM: the candidate slabs a batch reserves per trajectory (tsat_batch_reserve).
 // Batches small enough for a one-trajectory build (fewer than 2048 trajectories) reserve one slab for EVERY candidate, so that no
@@ -198,10 +318,7 @@ template <int ES> struct BwdCfg {
   static constexpr int NH = ES ? 6 : 7;        // dimension of the state difference the gains act on
   static constexpr int RECS = PkRec<ES>::RECS; // reals per knot record
   // knots per backward chunk = Jacobian lanes per pass: as many as the LDS budget of the build holds, 64 at most
-#if defined(TSAT_F32)
-  // fp32 build: 4-byte records plus the 512-byte double reduction scratch inside the budget of TSAT_OCC waves per SIMD
-  static constexpr int CHB = (TSAT_OCC == 2) ? (ES ? 63 : 54) : (TSAT_OCC == 3) ? (ES ? 39 : 34) : (ES ? 27 : 23);
-#elif defined(TSAT_JAC32) && defined(TSAT_DENSE)
+#if defined(TSAT_JAC32) && defined(TSAT_DENSE)
   // mixed-precision builds at two wavefronts per SIMD: float records, twice the knots of the double build in the same 20 KB
   static constexpr int CHB = ES ? 59 : 50;
 #elif defined(TSAT_JAC32)
@@ -313,7 +430,7 @@ constexpr int FB_SIZE = FB_BB + (BROW_UNITS == 2 ? ((CK * 3 * RPU + GLDS - 1) / 
 // candidates' terminal states (7, +1)
 constexpr int CG = 2, KB = 4 * WAVE, KBS = KB + 2;
 constexpr int CC_XN = CG * KBS, CC_SIZE = CC_XN + CG * 8;
-#if defined(TSAT_DENSE) || (defined(TSAT_F32) && TSAT_OCC >= 3)
+#if defined(TSAT_DENSE)
 constexpr int FWD_NBUF = 1;   // 20 KB budget: one buffer; the second wavefront on the SIMD covers the copy latency
 #else
 constexpr int FWD_NBUF = 2;   // the next chunk is copied while this one is rolled out
@@ -323,17 +440,13 @@ constexpr int L_FWD_END = L_FWD + (FWD_NBUF * FB_SIZE > CC_SIZE ? FWD_NBUF * FB_
 constexpr int L_BWD_RECV = (BwdCfg<0>::CHB * BwdCfg<0>::RECS > BwdCfg<1>::CHB * BwdCfg<1>::RECS
                                ? BwdCfg<0>::CHB * BwdCfg<0>::RECS : BwdCfg<1>::CHB * BwdCfg<1>::RECS);     // record values of a chunk
 constexpr int L_BWD_SOLVE = (L_BWD_RECV * (int)sizeof(jac_t) + (int)sizeof(cfg_real) - 1) / (int)sizeof(cfg_real);   // ... in reals
-#if !defined(TSAT_DENSE) && !defined(TSAT_F32)
+#if !defined(TSAT_DENSE)
 constexpr int L_BWD_END = L_REC + (L_BWD_SOLVE > TV_CHB * TvRec::RECS ? L_BWD_SOLVE : TV_CHB * TvRec::RECS);   // + the tracking kernel
 #else
 constexpr int L_BWD_END = L_REC + L_BWD_SOLVE;
 #endif
 #if defined(TSAT_PACKED)
-// packed builds (tsat_packed.hpp): their own carve-up behind L_UNION, sized to the 20 480 B of two wavefronts per SIMD or to
-// TSAT_PK_LDS_BYTES (40 960 B: the one-wavefront-per-SIMD units, tsat_kernels_packed4w / 8w / 16w.hip)
-#ifndef TSAT_PK_LDS_BYTES
-#define TSAT_PK_LDS_BYTES 20480
-#endif
+// packed builds (tsat_packed.hpp): their own carve-up behind L_UNION, sized to the build's TSAT_PK_LDS_BYTES (the table above)
 constexpr int LDS_REALS = (TSAT_PK_LDS_BYTES - ((sizeof(cfg_real) == 8) ? 0 : 64 * 8)) / (int)sizeof(cfg_real);
 #else
 constexpr int LDS_REALS = (L_FWD_END > L_BWD_END ? L_FWD_END : L_BWD_END);
@@ -1081,11 +1194,11 @@ template <typename real> struct BwdOut { acc_t dV1, dV2; int pd_ok; };
 // the price of a plain FMA. Lanes 12 - 15 repeat unit 11 (nobody names them): no lane reads past the record.
 // Only where the sweep is inlined into the kernel (the wide unit): measured there (profiles/fwd_gains/). The dense and packed
 // units, whose sweep is a function of its own, keep the broadcast reads, and their code is what it was.
-#if !defined(TSAT_EMU) && !defined(TSAT_F32) && !defined(TSAT_DENSE)
+#if !defined(TSAT_EMU) && !defined(TSAT_DENSE)
 #define TSAT_FWD_GAIN_DPP 1
 constexpr int KDL = 2;     // doubles of the record a lane holds
 #else
-constexpr int KDL = KDW;   // emulator, float, dense and packed units: the whole record in every lane
+constexpr int KDL = KDW;   // emulator, dense and packed units: the whole record in every lane
 #endif
 // what the roll-out of one knot reads from the staged chunk: nominal (x,u) record, gains K and d, three field rows
 template <typename real> struct KnotIn { real xu[XUW], kd[KDL], b0[3], b1[3], b2[3]; };
@@ -1195,7 +1308,7 @@ TSAT_FWD void forward_sweep(TPtrs<real> p, int N, int n_tab, int closed, int n_c
     };
     // two knots per turn, two register sets A / B: while one is rolled out the other is on its way from LDS (a single set would
     // have to be copied, forty register moves per knot)
-#if defined(TSAT_DENSE) && !defined(TSAT_F32)
+#if defined(TSAT_DENSE)
     // the dense double build (256 registers in all, no AGPRs) cannot hold two read-ahead sets of 43 doubles without spilling
     // into this loop; its second wavefront per SIMD covers part of the LDS latency instead
     for (int kk = 0; kk < nk; ++kk) {

@@ -226,7 +226,7 @@ TSAT_DEV void ensemble_wave(const EnsArgs<real>& a, int traj, int wave) {
 // gains of one slew, exactly as tvlqr_trajectory computes them before its roll-out: terminal S = Qf_lqr, then chunks of
 // Jacobian lanes (tv_jacobian_chunk) + the element-oriented Riccati recursion (riccati_chunk<real, 6, TvRec>), written to KD
 // in the solver's sign. One wavefront per slew; uses the wave's LDS block of tsat_device.hpp (wide layout).
-#if !defined(TSAT_DENSE) && !defined(TSAT_F32)
+#if !defined(TSAT_DENSE)
 template <typename real, int DIAGJ>
 TSAT_DEV void ensemble_gains(const real* Pg, const real* BTg, const int* bidx, const int* nkg, const real* XUR, real* KDg,
                              int NS, int n_tab, real u_scale, int lin_sq, int traj) {

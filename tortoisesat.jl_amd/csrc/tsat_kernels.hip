@@ -21,22 +21,14 @@
 
 using namespace tsat;
 
-// the dense build of the solve kernel lives in its own translation unit (tsat_kernels_dense.hip)
-hipError_t tsat_launch_solve_dense(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-// the packed build — 8 trajectories per wavefront share the forward sweeps (tsat_kernels_packed.hip, tsat_packed.hpp)
-hipError_t tsat_launch_solve_packed(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-hipError_t tsat_launch_solve_packed8(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-hipError_t tsat_launch_solve_packed8w(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-hipError_t tsat_launch_solve_packed16w(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-hipError_t tsat_launch_solve_packed4w(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-// the mixed-precision builds (options.precision = 32: float linearisation, everything else double; -DTSAT_JAC32 in tsat_device.hpp)
-// of the dense, packed and packed8 layouts, on the very arrays of the fp64 builds (tsat_kernels_*_mixed.hip)
-hipError_t tsat_launch_solve_dense_mixed(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-hipError_t tsat_launch_solve_packed_mixed(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-hipError_t tsat_launch_solve_packed_mixed8(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-hipError_t tsat_launch_solve_packed_mixed8w(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-hipError_t tsat_launch_solve_packed_mixed16w(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
-hipError_t tsat_launch_solve_packed_mixed4w(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
+// every build of the solve kernel but the wide one lives in a translation unit of its own (tsat_kernels_dense.hip,
+// tsat_kernels_packed*.hip, ..._mixed.hip: options.precision = 32); the list of builds is TSAT_SOLVE_BUILDS (tsat_device.hpp)
+using solve_launch_t = hipError_t (*)(const KArgs<double>& a, int rk4, int inertia_class, int error_state, hipStream_t stream);
+#define TSAT_SOLVE_PROTO(id, layout, tail)                                                                                   \
+  hipError_t tsat_launch_solve_##layout##tail(const KArgs<double>&, int, int, int, hipStream_t);                             \
+  hipError_t tsat_launch_solve_##layout##_mixed##tail(const KArgs<double>&, int, int, int, hipStream_t);
+TSAT_SOLVE_BUILDS(TSAT_SOLVE_PROTO)
+#undef TSAT_SOLVE_PROTO
 
 // the plant step of tsat_mpc_run_dispersed (tsat_kernels_mpc_dispersed.hip); step 0 also packs the call's plant records
 hipError_t tsat_launch_mpc_dispersed(const MpcDispArgs<double>& a, const double* plant, hipStream_t stream);
@@ -400,13 +392,7 @@ using solve_kern_t = void (*)(KArgs<double>);
 // kernel variant: integrator x inertia class (full / diagonal / isotropic) x error-state mode. LDS is a static
 // module-level array (tsat_device.hpp): nothing dynamic to request at launch.
 solve_kern_t solve_variant(const tsat_handle* h, const tsat_options* o) {
-  static const solve_kern_t variants[2][3][2] = {
-      {{tsat_solve_kernel<double, 3, 0, 0>, tsat_solve_kernel<double, 3, 0, 1>},
-       {tsat_solve_kernel<double, 3, 1, 0>, tsat_solve_kernel<double, 3, 1, 1>},
-       {tsat_solve_kernel<double, 3, 2, 0>, tsat_solve_kernel<double, 3, 2, 1>}},
-      {{tsat_solve_kernel<double, 4, 0, 0>, tsat_solve_kernel<double, 4, 0, 1>},
-       {tsat_solve_kernel<double, 4, 1, 0>, tsat_solve_kernel<double, 4, 1, 1>},
-       {tsat_solve_kernel<double, 4, 2, 0>, tsat_solve_kernel<double, 4, 2, 1>}}};
+  static const solve_kern_t variants[2][3][2] = TSAT_VARIANT_TABLE(tsat_solve_kernel);
   return variants[o->integrator == 4 ? 1 : 0][h->inertia_class][o->error_state ? 1 : 0];
 }
 
@@ -436,22 +422,19 @@ int selected_build(const tsat_handle* h, int precision, int64_t budget) {
   if (precision == 32) return 2;
   return (h->variant == 2 || (h->variant != 1 && h->T > TSAT_WIDE_MAX_T)) ? 2 : 1;
 }
-hipError_t launch_solve(const tsat_handle* h, const tsat_options* o, const KArgs<double>& a) {
-  const int build = selected_build(h, o->precision, (int64_t)o->max_outer * o->max_inner), rk4 = o->integrator == 4;
-  if (o->precision == 32) {
-    if (build == 7) return tsat_launch_solve_packed_mixed4w(a, rk4, h->inertia_class, o->error_state, h->stream);
-    if (build == 6) return tsat_launch_solve_packed_mixed16w(a, rk4, h->inertia_class, o->error_state, h->stream);
-    if (build == 5) return tsat_launch_solve_packed_mixed8w(a, rk4, h->inertia_class, o->error_state, h->stream);
-    if (build == 4) return tsat_launch_solve_packed_mixed8(a, rk4, h->inertia_class, o->error_state, h->stream);
-    if (build == 3) return tsat_launch_solve_packed_mixed(a, rk4, h->inertia_class, o->error_state, h->stream);
-    return tsat_launch_solve_dense_mixed(a, rk4, h->inertia_class, o->error_state, h->stream);
+// at[mixed precision][build id]; null: the wide build, launched from this unit (selected_build never gives it at precision 32)
+struct SolveLaunchers {
+  solve_launch_t at[2][8] = {};
+  constexpr SolveLaunchers() {
+#define TSAT_SOLVE_ENTRY(id, layout, tail) at[0][id] = tsat_launch_solve_##layout##tail; at[1][id] = tsat_launch_solve_##layout##_mixed##tail;
+    TSAT_SOLVE_BUILDS(TSAT_SOLVE_ENTRY)
+#undef TSAT_SOLVE_ENTRY
   }
-  if (build == 7) return tsat_launch_solve_packed4w(a, rk4, h->inertia_class, o->error_state, h->stream);
-  if (build == 6) return tsat_launch_solve_packed16w(a, rk4, h->inertia_class, o->error_state, h->stream);
-  if (build == 5) return tsat_launch_solve_packed8w(a, rk4, h->inertia_class, o->error_state, h->stream);
-  if (build == 4) return tsat_launch_solve_packed8(a, rk4, h->inertia_class, o->error_state, h->stream);
-  if (build == 3) return tsat_launch_solve_packed(a, rk4, h->inertia_class, o->error_state, h->stream);
-  if (build == 2) return tsat_launch_solve_dense(a, rk4, h->inertia_class, o->error_state, h->stream);
+};
+hipError_t launch_solve(const tsat_handle* h, const tsat_options* o, const KArgs<double>& a) {
+  static constexpr SolveLaunchers launchers;
+  const int build = selected_build(h, o->precision, (int64_t)o->max_outer * o->max_inner), rk4 = o->integrator == 4;
+  if (const solve_launch_t launch = launchers.at[o->precision == 32][build]) return launch(a, rk4, h->inertia_class, o->error_state, h->stream);
   hipLaunchKernelGGL(solve_variant(h, o), dim3((unsigned)h->T), dim3(64), 0, h->stream, a);
   return hipGetLastError();
 }

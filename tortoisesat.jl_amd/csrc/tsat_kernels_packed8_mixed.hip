@@ -1,7 +1,4 @@
-// tsat_kernels_packed8_mixed.hip — the mixed-precision packed build with EIGHT trajectories per wavefront (see
-// tsat_kernels_packed_mixed.hip, tsat_kernels_packed8.hip)
-#define TSAT_PK_G 8
-#define TSAT_PK_CK 4
-#define TSAT_PK_NBUF 1
-#define TSAT_PK_NAME(base) base##_mixed8
-#include "tsat_kernels_packed_mixed.hip"
+// tsat_kernels_packed8_mixed.hip — the unit of one build of the solve kernel: packed8, mixed precision (the table of builds at the head of tsat_device.hpp)
+#define TSAT_BUILD 4
+#define TSAT_JAC32 1
+#include "tsat_kernels_packed.hip"

@@ -1,11 +1,4 @@
-// tsat_kernels_packed8w_mixed.hip — the mixed-precision build (float linearisation, tsat_kernels_packed_mixed.hip) of
-// tsat_kernels_packed8w.hip: with float records ALL sixteen knots of a pass stay in the LDS ring — nothing goes through the workspace
+// tsat_kernels_packed8w_mixed.hip — the unit of one build of the solve kernel: packed8w, mixed precision (the table of builds at the head of tsat_device.hpp)
+#define TSAT_BUILD 5
 #define TSAT_JAC32 1
-#define TSAT_PK_G 8
-#define TSAT_PK_CK 4
-#define TSAT_PK_NBUF 2
-#define TSAT_PK_WAVES 1
-#define TSAT_PK_LDS_BYTES 40960
-#define TSAT_PK_RING 16
-#define TSAT_PK_NAME(base) base##_mixed8w
 #include "tsat_kernels_packed.hip"

@@ -14,7 +14,7 @@
 // per-trajectory state machine that is advanced between two forward sweeps. The arithmetic of a trajectory is, operation
 // for operation, that of solve_trajectory: results are bit-identical to the other builds (tests: emulator and GPU).
 // Compiled for two wavefronts per SIMD (20 KB of LDS, 256 registers: tsat_kernels_packed.hip, ...packed8.hip) and for ONE (40 KB,
-// 512 registers: ...packed4w / 8w / 16w.hip, TSAT_PK_WAVES = 1), which is what the automatic choice takes (tsat_kernels.hip).
+// 512 registers: ...packed4w / 8w / 16w.hip, TSAT_PK_WAVES = 1: the table of builds in tsat_device.hpp), which is what the automatic choice takes (tsat_kernels.hip).
 //
 // Replaces, like solve_trajectory, TrajectoryOptimization.solve!(prob, solver) (src/TortoiseSat.jl:199; loop body of
 // src/monte_carlo.jl:118-235) for a batch.
@@ -23,20 +23,8 @@
 
 namespace tsat {
 
-#ifndef TSAT_PK_G
-#define TSAT_PK_G 4
-#endif
-#ifndef TSAT_PK_CK
-#define TSAT_PK_CK 4
-#endif
-#ifndef TSAT_PK_NBUF
-#define TSAT_PK_NBUF 2
-#endif
-#ifndef TSAT_PK_STORE
-#define TSAT_PK_STORE 6
-#endif
-#ifndef TSAT_PK_WAVES
-#define TSAT_PK_WAVES 2
+#ifndef TSAT_PACKED
+#error "tsat_packed.hpp is for the packed builds (TSAT_BUILD 3 .. 7: the table at the head of tsat_device.hpp sets every TSAT_PK_*)"
 #endif
 // One wavefront per SIMD (the `w` builds): nobody hides this wavefront's waits, so the Riccati lanes read the record of knot l - 1
 // from the ring while they work on knot l (riccati_rows does the same in the one-trajectory builds) and pad their copy stream so
@@ -85,9 +73,6 @@ static_assert(L_FWD + PK_NBUF * PK_FB <= LDS_REALS, "packed forward buffers fit 
 //                    is the `row_newbcast` source of the FMA that consumes it — no exchange through LDS inside a knot), four
 //                    trajectories side by side: the results are bit-identical to the one-trajectory builds.
 constexpr int PK_JCH = 16;                        // knots per trajectory and Jacobian pass (= lanes per trajectory)
-#ifndef TSAT_PK_RING
-#define TSAT_PK_RING ((sizeof(jac_t) == 8) ? 4 : 8)
-#endif
 constexpr int PK_RING = TSAT_PK_RING;      // knots of every trajectory resident in LDS during the recursion (20 KB: 4 double records, 8 float ones; 40 KB: 12 / 16)
 constexpr int PK_CPB = 16;                        // bytes per lane of a ring copy instruction (riccati_group)
 constexpr int PK_BC = 16;                         // lanes per trajectory in a backward pass
