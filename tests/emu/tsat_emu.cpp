@@ -169,6 +169,15 @@ static void run_block(const KArgs<R>& a, int traj) {
   });
 }
 
+// the emulated solve for an options block and an inertia class (inertia_class): the variant selection of tsat_batch_upload
+using blk_t = void (*)(const KArgs<R>&, int);
+static blk_t solve_block(const tsat_options& o, int cls) {
+  static const blk_t variants[2][3][2] = {
+      {{run_block<3, 0, 0>, run_block<3, 0, 1>}, {run_block<3, 1, 0>, run_block<3, 1, 1>}, {run_block<3, 2, 0>, run_block<3, 2, 1>}},
+      {{run_block<4, 0, 0>, run_block<4, 0, 1>}, {run_block<4, 1, 0>, run_block<4, 1, 1>}, {run_block<4, 2, 0>, run_block<4, 2, 1>}}};
+  return variants[o.integrator == 4 ? 1 : 0][cls][o.error_state ? 1 : 0];
+}
+
 #ifdef TSAT_PACKED
 template <int INTEG, int DIAGJ, int ES>
 static void resume_block(const KArgs<R>& a, int w) {      // tsat_resume_kernel_packed
@@ -209,11 +218,7 @@ extern "C" int emu_solve_batch(const tsat_options* o, int64_t T, int64_t n_btab,
   std::vector<R> JW((size_t)((T + 3) / 4) * TSAT_JW_REALS_PER_4, (R)0);     // packed builds: Jacobian records in flight
   a.JW = JW.data();
   const int cls = inertia_class(T, Jmat);   // same variant selection as tsat_batch_upload
-  using blk_t = void (*)(const KArgs<R>&, int);
-  static const blk_t variants[2][3][2] = {
-      {{run_block<3, 0, 0>, run_block<3, 0, 1>}, {run_block<3, 1, 0>, run_block<3, 1, 1>}, {run_block<3, 2, 0>, run_block<3, 2, 1>}},
-      {{run_block<4, 0, 0>, run_block<4, 0, 1>}, {run_block<4, 1, 0>, run_block<4, 1, 1>}, {run_block<4, 2, 0>, run_block<4, 2, 1>}}};
-  const blk_t blk = variants[o->integrator == 4 ? 1 : 0][cls][o->error_state ? 1 : 0];
+  const blk_t blk = solve_block(*o, cls);
 #ifdef TSAT_PACKED
   // endgame of the launch as tsat_launch_solve_packed queues it (TSAT_EMU_SUSPEND_AT=n: park at n live trajectories)
   const char* sa = std::getenv("TSAT_EMU_SUSPEND_AT");
@@ -274,11 +279,7 @@ extern "C" int emu_mpc_batch(const tsat_options* o, int64_t T, int64_t n_btab, c
   m.P = P.data(); m.BT = BT.data(); m.bidx = bidx.data(); m.nk = n_knots; m.XU = XU.data(); m.U0 = U0w.data();
   m.HX = X_hist; m.HU = U_hist; m.stats = nullptr; m.tally = nullptr;
   const int cls = inertia_class(T, Jmat);
-  using blk_t = void (*)(const KArgs<double>&, int);
-  static const blk_t variants[2][3][2] = {
-      {{run_block<3, 0, 0>, run_block<3, 0, 1>}, {run_block<3, 1, 0>, run_block<3, 1, 1>}, {run_block<3, 2, 0>, run_block<3, 2, 1>}},
-      {{run_block<4, 0, 0>, run_block<4, 0, 1>}, {run_block<4, 1, 0>, run_block<4, 1, 1>}, {run_block<4, 2, 0>, run_block<4, 2, 1>}}};
-  const blk_t blk = variants[o->integrator == 4 ? 1 : 0][cls][o->error_state ? 1 : 0];
+  const blk_t blk = solve_block(*o, cls);
   for (int s = 0; s < n_steps; ++s) {
     tsat_emu::for_each_wave((int)T, [&](int t) { blk(a, t); });
     m.step = s;

@@ -18,7 +18,7 @@ static int run_emu_ensemble(const tsat_tvlqr_options* o, int64_t T, int64_t n_bt
   const int N = o->n_knots, n_tab = o->n_tab;
   const int nw = ensemble_waves(M), Mp = nw * WAVE;
   std::vector<double> P((size_t)T * PSTRIDE), BT((size_t)n_btab * n_tab * 4), XUR((size_t)T * N * XUW),
-      KD((size_t)T * (N - 1) * KDW, 0.0), x0n((size_t)T * 7), PL(plant ? (size_t)T * PLW * Mp : 0, 0.0), SAT(plant ? (size_t)T * SATW : 0);
+      KD((size_t)T * (N - 1) * KDW, 0.0), x0n((size_t)T * 7), PL(plant ? (size_t)T * PLW * Mp : 0, 0.0), SAT;
   std::vector<int> bidx(T);
   for (int64_t t = 0; t < T; ++t)
     for (int i = 0; i < 7; ++i) x0n[7 * t + i] = X[(size_t)t * N * 7 + i];
@@ -30,22 +30,17 @@ static int run_emu_ensemble(const tsat_tvlqr_options* o, int64_t T, int64_t n_bt
     for (int j = 0; j < 6; ++j)
       for (int c = 0; c < 3; ++c) KD[ek * KDW + c * 7 + j] = -K_lqr[ek * 18 + j * 3 + c];
   if (plant) {
-    for (int64_t t = 0; t < T; ++t)
-      for (int c = 0; c < 3; ++c) {
-        SAT[SATW * t + c] = sat_lo ? sat_lo[3 * t + c] : -HUGE_VAL;
-        SAT[SATW * t + 3 + c] = sat_hi ? sat_hi[3 * t + c] : HUGE_VAL;
-      }
+    SAT = pack_limits(sat_lo, sat_hi, T);
     for (int64_t e = 0; e < T * (int64_t)(M + 1); ++e) dispersed_pack<double>(plant, P.data(), o->u_scale, PL.data(), T, M, Mp, e);
   }
   if (X_sim) std::memset(X_sim, 0, sizeof(double) * (size_t)T * M * N * 7);
   std::vector<tsat_tvlqr_stats> nom((size_t)T);
   DispArgs<double> d;
   EnsArgs<double>& a = d.e;
-  a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.min_steps = o->min_steps;
-  a.us = o->u_scale; a.w_tol = o->w_tol; a.ang_tol = o->angle_tol;
+  a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.us = o->u_scale;
+  fill_ens_options(*o, a);
   a.P = P.data(); a.BT = BT.data(); a.bidx = bidx.data(); a.nk = n_knots; a.XUR = XUR.data(); a.KD = KD.data(); a.X0 = x0_sim;
-  a.k0 = (unsigned)(o->noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o->noise_seed >> 32);
-  a.nid0 = (const long long*)noise_id0; a.sg = o->sigma_gyro; a.sa = o->sigma_att; a.fa = o->field_amp;
+  a.nid0 = (const long long*)noise_id0;
   a.XS = X_sim; a.stats = stats; a.stats_nom = nom.data();
   d.PL = PL.data(); d.Mp = Mp; d.SAT = SAT.data(); d.nclip = n_clipped;
   const int cls = inertia_class(T, Jmat);

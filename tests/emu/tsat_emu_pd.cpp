@@ -22,7 +22,8 @@ extern "C" int emu_pd_ensemble(const tsat_tvlqr_options* o, int64_t T, int64_t n
   const int nw = ensemble_waves(M), Mp = nw * WAVE;
   const size_t Tn = (size_t)T, nS = Tn * (size_t)M;
   std::vector<double> P(Tn * PSTRIDE), BT((size_t)n_btab * n_tab * 4), XUR, x0n(Tn * 7), zero(Tn * 6, 0.0), gain(Tn * PDGW),
-      SAT(Tn * SATW), PL(Tn * PLW * Mp, 0.0), model, GT;
+      PL(Tn * PLW * Mp, 0.0), model, GT;
+  const std::vector<double> SAT = pack_limits(sat_lo, sat_hi, T);
   std::vector<int> bidx(Tn);
   for (size_t t = 0; t < Tn; ++t) {
     bidx[t] = btab_idx ? btab_idx[t] : (int)t;
@@ -30,8 +31,6 @@ extern "C" int emu_pd_ensemble(const tsat_tvlqr_options* o, int64_t T, int64_t n
     for (int c = 0; c < 3; ++c) {
       gain[PDGW * t + c] = kd[3 * t + c];
       gain[PDGW * t + 3 + c] = kp[3 * t + c];
-      SAT[SATW * t + c] = sat_lo ? sat_lo[3 * t + c] : -HUGE_VAL;
-      SAT[SATW * t + 3 + c] = sat_hi ? sat_hi[3 * t + c] : HUGE_VAL;
     }
   }
   pack_tv_params<double>(T, x0n.data(), xf, tau0, dtau, dt, Jmat, zero.data(), zero.data(), zero.data(), P.data());
@@ -61,11 +60,10 @@ extern "C" int emu_pd_ensemble(const tsat_tvlqr_options* o, int64_t T, int64_t n
   std::vector<tsat_tvlqr_stats> nom(Tn);
   PdArgs<double> pa;
   EnsArgs<double>& a = pa.d.e;
-  a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.min_steps = o->min_steps;
-  a.us = o->u_scale; a.w_tol = o->w_tol; a.ang_tol = o->angle_tol;
+  a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.us = o->u_scale;
+  fill_ens_options(*o, a);
   a.P = P.data(); a.BT = BT.data(); a.bidx = bidx.data(); a.nk = n_knots; a.XUR = X ? XUR.data() : nullptr; a.KD = nullptr; a.X0 = x0_sim;
-  a.k0 = (unsigned)(o->noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o->noise_seed >> 32);
-  a.nid0 = (const long long*)noise_id0; a.sg = o->sigma_gyro; a.sa = o->sigma_att; a.fa = o->field_amp;
+  a.nid0 = (const long long*)noise_id0;
   a.XS = X_sim; a.stats = stats; a.stats_nom = nom.data();
   pa.d.PL = PL.data(); pa.d.Mp = Mp; pa.d.SAT = SAT.data(); pa.d.nclip = n_clipped;
   pa.GT = Rtab ? GT.data() : nullptr; pa.GAIN = gain.data(); pa.X0N = x0n.data(); pa.feedforward = feedforward; pa.limit_mode = limit_mode;

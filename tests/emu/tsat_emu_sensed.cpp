@@ -17,12 +17,7 @@ struct Common {
             const double* sat_lo, const double* sat_hi, const double* Rtab, double gm, const double* sensor) {
     const int Mp = ensemble_waves(M) * WAVE;
     const size_t Tn = (size_t)T, nS = Tn * (size_t)M;
-    SAT.resize(Tn * SATW);
-    for (size_t t = 0; t < Tn; ++t)
-      for (int c = 0; c < 3; ++c) {
-        SAT[SATW * t + c] = sat_lo ? sat_lo[3 * t + c] : -HUGE_VAL;
-        SAT[SATW * t + 3 + c] = sat_hi ? sat_hi[3 * t + c] : HUGE_VAL;
-      }
+    SAT = pack_limits(sat_lo, sat_hi, T);
     if (!plant) {
       model.assign(nS * TSAT_PLANT_W, 0.0);
       for (size_t e = 0; e < nS; ++e) {
@@ -54,11 +49,10 @@ SensArgs<double> sens_args(const tsat_sensor_options* s, const tsat_tvlqr_option
 void ens_args(EnsArgs<double>& a, const tsat_tvlqr_options* o, int64_t T, int32_t M, const double* P, const double* BT, const int* bidx,
               const int32_t* n_knots, const double* XUR, const double* KD, const double* x0_sim, const int64_t* noise_id0, double* X_sim,
               tsat_tvlqr_stats* stats, tsat_tvlqr_stats* nom) {
-  a.T = (int)T; a.N = o->n_knots; a.n_tab = o->n_tab; a.M = M; a.min_steps = o->min_steps;
-  a.us = o->u_scale; a.w_tol = o->w_tol; a.ang_tol = o->angle_tol;
+  a.T = (int)T; a.N = o->n_knots; a.n_tab = o->n_tab; a.M = M; a.us = o->u_scale;
+  fill_ens_options(*o, a);
   a.P = P; a.BT = BT; a.bidx = bidx; a.nk = n_knots; a.XUR = XUR; a.KD = KD; a.X0 = x0_sim;
-  a.k0 = (unsigned)(o->noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o->noise_seed >> 32);
-  a.nid0 = (const long long*)noise_id0; a.sg = o->sigma_gyro; a.sa = o->sigma_att; a.fa = o->field_amp;
+  a.nid0 = (const long long*)noise_id0;
   a.XS = X_sim; a.stats = stats; a.stats_nom = nom;
 }
 

@@ -22,7 +22,9 @@ sys.path.insert(0, ROOT)
 import numpy as np
 from tsat_loader import load_package
 
-load_package()
+pkg = load_package()
+if os.environ.get("TSAT_LIB"):            # developer switch: another build of the same library (tools/alternate_builds.py)
+    pkg._abi.LIB_NAME = os.environ["TSAT_LIB"]
 from tortoisesat_jl_amd import mpc, slew_setup as ss, tracking as tr, trajopt as to
 
 ap = argparse.ArgumentParser()

@@ -263,6 +263,27 @@ inline std::string check_limits(const double* sat_lo, const double* sat_hi, int6
   return "";
 }
 
+// ... as the plants read them: [T][6] = lo[3], hi[3] per slew (SATW of tsat_dispersed.hpp). A NULL limit is +-inf, so that the
+// step has one code path
+inline std::vector<double> pack_limits(const double* sat_lo, const double* sat_hi, int64_t T) {
+  std::vector<double> sat((size_t)T * 6);
+  for (int64_t t = 0; t < T; ++t)
+    for (int c = 0; c < 3; ++c) {
+      sat[6 * t + c] = sat_lo ? sat_lo[3 * t + c] : -HUGE_VAL;
+      sat[6 * t + 3 + c] = sat_hi ? sat_hi[3 * t + c] : HUGE_VAL;
+    }
+  return sat;
+}
+
+// the statistic's thresholds and the plant noise of a closed-loop call, into its EnsArgs (tsat_ensemble.hpp; a template only
+// because this header comes first)
+template <typename Ens>
+inline void fill_ens_options(const tsat_tvlqr_options& o, Ens& e) {
+  e.min_steps = o.min_steps; e.w_tol = o.w_tol; e.ang_tol = o.angle_tol;
+  e.k0 = (unsigned)(o.noise_seed & 0xFFFFFFFFull); e.k1 = (unsigned)(o.noise_seed >> 32);
+  e.sg = o.sigma_gyro; e.sa = o.sigma_att; e.fa = o.field_amp;
+}
+
 // what tsat_mpc_run_dispersed rejects beyond tsat_mpc_run's own checks: "" or the reason (plant 21 x T or null, limits 3 x T or null)
 inline std::string check_mpc_dispersed(const tsat_tvlqr_options& po, int32_t n_steps, int64_t step0, const double* plant,
                                        const double* sat_lo, const double* sat_hi, int64_t T) {

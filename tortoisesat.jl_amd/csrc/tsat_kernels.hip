@@ -32,7 +32,7 @@ TSAT_SOLVE_BUILDS(TSAT_SOLVE_PROTO)
 
 // the plant step of tsat_mpc_run_dispersed (tsat_kernels_mpc_dispersed.hip); step 0 also packs the call's plant records
 hipError_t tsat_launch_mpc_dispersed(const MpcDispArgs<double>& a, const double* plant, hipStream_t stream);
-// the pack, and hold + plan shift after every solve, of tsat_mpc_run_held (tsat_kernels_mpc_held.hip)
+// the pack, the hold, and the plan shift that follows whichever hold ran, of tsat_mpc_run_held (tsat_kernels_mpc_held.hip)
 hipError_t tsat_launch_mpc_held_pack(const MpcHeldArgs<double>& a, const double* plant, hipStream_t stream);
 hipError_t tsat_launch_mpc_held(const MpcHeldArgs<double>& a, int error_state, hipStream_t stream);
 hipError_t tsat_launch_mpc_held_shift(const MpcArgs<double>& m, int r, hipStream_t stream);
@@ -684,12 +684,7 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
     return fail(h, -10, std::string("device allocation failed in ") + name);
   if (!dHX || !dHU || !dTally || (plant && !dPlant) || !dPL || !dSat || (noise_id && !dNid) || !dRec || !dSt || !dClip)
     return fail(h, -10, std::string("device allocation failed in ") + name);
-  std::vector<double> sat(T * SATW);               // a NULL limit is +-inf: the step has one code path
-  for (size_t t = 0; t < T; ++t)
-    for (int c = 0; c < 3; ++c) {
-      sat[SATW * t + c] = sat_lo ? sat_lo[3 * t + c] : -HUGE_VAL;
-      sat[SATW * t + 3 + c] = sat_hi ? sat_hi[3 * t + c] : HUGE_VAL;
-    }
+  const std::vector<double> sat = pack_limits(sat_lo, sat_hi, (int64_t)T);
   TSAT_HIP(h, hipMemcpy(dSat, sat.data(), sat.size() * 8, hipMemcpyHostToDevice));
   if (plant) TSAT_HIP(h, hipMemcpy(dPlant, plant, T * TSAT_PLANT_W * 8, hipMemcpyHostToDevice));
   if (noise_id) TSAT_HIP(h, hipMemcpy(dNid, noise_id, T * sizeof(long long), hipMemcpyHostToDevice));
@@ -708,9 +703,8 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   m.HX = dHX; m.HU = dHU; m.stats = h->stats; m.tally = dTally;
   md.d.PL = dPL; md.d.Mp = 1; md.d.SAT = dSat; md.d.nclip = dClip;
   EnsArgs<double>& e = md.d.e;
-  e.min_steps = po->min_steps; e.w_tol = po->w_tol; e.ang_tol = po->angle_tol;
-  e.k0 = (unsigned)(po->noise_seed & 0xFFFFFFFFull); e.k1 = (unsigned)(po->noise_seed >> 32);
-  e.nid0 = dNid; e.sg = po->sigma_gyro; e.sa = po->sigma_att; e.fa = po->field_amp; e.stats = dSt;
+  fill_ens_options(*po, e);
+  e.nid0 = dNid; e.stats = dSt;
   md.noisy = po->noise_mode; md.step0 = (long long)step0; md.rec = dRec;
   mh.KD = h->KD; mh.feedback = feedback;
   MpcHeldGgArgs<double> mg = {};
@@ -733,17 +727,16 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
       if (launch_solve(h, o, a) != hipSuccess) rc = -10;
       m.step = s;
       mh.r = std::min<int>(replan_every, n_steps - s);
-      if (sc) {        // the hold on measurements (with or without the gravity rows), then the held loop's own plan shift
+      if (sc) {        // the hold on measurements (with or without the gravity rows)
         ms.h = mh;
         if (!rc && tsat_launch_mpc_sensed(ms, o->error_state, h->stream) != hipSuccess) rc = -10;
-        if (!rc && tsat_launch_mpc_held_shift(m, mh.r, h->stream) != hipSuccess) rc = -10;
-      } else if (gravity) {   // the hold through the gravity rows, then the held loop's own plan shift
+      } else if (gravity) {   // the hold through the gravity rows
         mg.h = mh; mg.GT = dGT;
         if (!rc && tsat_launch_mpc_held_gg(mg, o->error_state, h->stream) != hipSuccess) rc = -10;
-        if (!rc && tsat_launch_mpc_held_shift(m, mh.r, h->stream) != hipSuccess) rc = -10;
       } else {
         if (!rc && tsat_launch_mpc_held(mh, o->error_state, h->stream) != hipSuccess) rc = -10;
       }
+      if (!rc && tsat_launch_mpc_held_shift(m, mh.r, h->stream) != hipSuccess) rc = -10;
     }
   } else {
     for (int s = 0; s < n_steps && !rc; ++s) {   // 2 n_steps launches (+ the pack) queued back to back; the stream orders them

@@ -299,12 +299,7 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
     if (X_sim) ENS_HIP(hipMemsetAsync(dXS, 0, nXS * 8, s.stream));
   }
   if (disp) {
-    std::vector<double> sat(Tn * SATW);
-    for (size_t t = 0; t < Tn; ++t)
-      for (int c = 0; c < 3; ++c) {
-        sat[SATW * t + c] = disp->sat_lo ? disp->sat_lo[3 * t + c] : -HUGE_VAL;
-        sat[SATW * t + 3 + c] = disp->sat_hi ? disp->sat_hi[3 * t + c] : HUGE_VAL;
-      }
+    const std::vector<double> sat = pack_limits(disp->sat_lo, disp->sat_hi, T);
     const std::vector<double> model = disp->plant ? std::vector<double>() : model_plants(Jmat, Tn, M);
     ENS_HIP(hipMemcpy(dPlant, disp->plant ? disp->plant : model.data(), nS * TSAT_PLANT_W * 8, hipMemcpyHostToDevice));
     ENS_HIP(hipMemcpy(dSat, sat.data(), sat.size() * 8, hipMemcpyHostToDevice));
@@ -333,11 +328,10 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   ENS_HIP(hipEventRecord(s.ev[1], s.stream));
   {
     EnsArgs<double> a;
-    a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.min_steps = o->min_steps;
-    a.us = o->u_scale; a.w_tol = o->w_tol; a.ang_tol = o->angle_tol;
+    a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.us = o->u_scale;
+    fill_ens_options(*o, a);
     a.P = dP; a.BT = dBT; a.bidx = dbi; a.nk = dnk; a.XUR = dXU; a.KD = dKD; a.X0 = dX0;
-    a.k0 = (unsigned)(o->noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o->noise_seed >> 32);
-    a.nid0 = dnid; a.sg = o->sigma_gyro; a.sa = o->sigma_att; a.fa = o->field_amp;
+    a.nid0 = dnid;
     a.XS = dXS; a.stats = dst; a.stats_nom = dsn;
     if (disp) {
       DispArgs<double> d;
@@ -421,7 +415,8 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
   const int nw = ensemble_waves(M), Mp = nw * WAVE;
   const size_t nX = Tn * N * 7, nU = Tn * (size_t)(N - 1) * 3, nB = (size_t)n_btab * n_tab, nXU = Tn * N * XUW, nS = Tn * (size_t)M,
                nXS = X_sim ? nS * N * 7 : 0;
-  std::vector<double> P(Tn * PSTRIDE), x0n(Tn * 7), zero(Tn * 6, 0.0), gain(Tn * PDGW), sat(Tn * SATW), model;
+  std::vector<double> P(Tn * PSTRIDE), x0n(Tn * 7), zero(Tn * 6, 0.0), gain(Tn * PDGW), model;
+  const std::vector<double> sat = pack_limits(sat_lo, sat_hi, T);
   std::vector<int> bi(Tn);
   for (size_t t = 0; t < Tn; ++t) {
     bi[t] = btab_idx ? btab_idx[t] : (int)t;
@@ -429,8 +424,6 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
     for (int c = 0; c < 3; ++c) {
       gain[PDGW * t + c] = kd[3 * t + c];
       gain[PDGW * t + 3 + c] = kp[3 * t + c];
-      sat[SATW * t + c] = sat_lo ? sat_lo[3 * t + c] : -HUGE_VAL;
-      sat[SATW * t + 3 + c] = sat_hi ? sat_hi[3 * t + c] : HUGE_VAL;
     }
   }
   pack_tv_params<double>(T, x0n.data(), xf, tau0, dtau, dt, Jmat, zero.data(), zero.data(), zero.data(), P.data());
@@ -497,11 +490,10 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
   {
     PdArgs<double> pa;
     EnsArgs<double>& a = pa.d.e;
-    a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.min_steps = o->min_steps;
-    a.us = o->u_scale; a.w_tol = o->w_tol; a.ang_tol = o->angle_tol;
+    a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.us = o->u_scale;
+    fill_ens_options(*o, a);
     a.P = dP; a.BT = dBT; a.bidx = dbi; a.nk = dnk; a.XUR = dXU; a.KD = nullptr; a.X0 = dX0;
-    a.k0 = (unsigned)(o->noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o->noise_seed >> 32);
-    a.nid0 = dnid; a.sg = o->sigma_gyro; a.sa = o->sigma_att; a.fa = o->field_amp;
+    a.nid0 = dnid;
     a.XS = dXS; a.stats = dst; a.stats_nom = dsn;
     pa.d.PL = dPL; pa.d.Mp = Mp; pa.d.SAT = dSat; pa.d.nclip = dClip;
     pa.GT = dGT; pa.GAIN = dGain; pa.X0N = dX0N; pa.feedforward = feedforward; pa.limit_mode = limit_mode;

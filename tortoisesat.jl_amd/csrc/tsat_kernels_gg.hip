@@ -1,7 +1,6 @@
 // tsat_kernels_gg.hip — the kernels of tsat_tvlqr_ensemble_gg and tsat_mpc_run_held_gg (include/tortoise_hip.h; tsat_gg.hpp): the
-// dispersed ensemble and the hold under gravity-gradient torque, and the pack of the orbit table. A translation unit of its own,
-// so that no existing kernel is recompiled differently. The host code of the two entry points (tsat_kernels_ensemble.hip,
-// tsat_kernels.hip) owns the buffers and calls the launchers below.
+// dispersed ensemble and the hold under gravity-gradient torque, and the pack of the orbit table. The host code of the two entry
+// points (tsat_kernels_ensemble.hip, tsat_kernels.hip) owns the buffers and calls the launchers below.
 #include <hip/hip_runtime.h>
 #include "tsat_gg.hpp"
 
@@ -33,7 +32,7 @@ hipError_t tsat_launch_ensemble_gg(const GgEnsArgs<double>& g, int waves, hipStr
   return hipGetLastError();
 }
 
-// the block of a.h.r control steps alone: the plan shift that follows it is the held loop's (tsat_launch_mpc_held_shift)
+// the block of a.h.r control steps, as tsat_launch_mpc_held
 hipError_t tsat_launch_mpc_held_gg(const MpcHeldGgArgs<double>& a, int error_state, hipStream_t stream) {
   const unsigned T = (unsigned)a.h.s.m.T;
   hipLaunchKernelGGL(error_state ? tsat_mpc_held_gg_kernel<1> : tsat_mpc_held_gg_kernel<0>, dim3((T + 63) / 64), dim3(64), 0, stream, a);

@@ -1,6 +1,6 @@
-// tsat_kernels_mpc_dispersed.hip — the plant step of tsat_mpc_run_dispersed (include/tortoise_hip.h; tsat_mpc_dispersed.hpp): a
-// translation unit of its own, so that no existing kernel is recompiled differently. The host loop in tsat_kernels.hip owns the
-// handle's buffers and calls the one launcher below once per control step, where tsat_mpc_run launches its advance kernel.
+// tsat_kernels_mpc_dispersed.hip — the plant step of tsat_mpc_run_dispersed (include/tortoise_hip.h; tsat_mpc_dispersed.hpp). The host loop
+// in tsat_kernels.hip owns the handle's buffers and calls the one launcher below once per control step, where tsat_mpc_run launches
+// its advance kernel.
 #include <hip/hip_runtime.h>
 #include "tsat_mpc_dispersed.hpp"
 

@@ -1,6 +1,6 @@
-// tsat_kernels_mpc_held.hip — the hold and the plan shift of tsat_mpc_run_held (include/tortoise_hip.h; tsat_mpc_held.hpp): a
-// translation unit of its own, so that no existing kernel is recompiled differently. The host loop in tsat_kernels.hip owns the
-// handle's buffers and calls the launchers below: the pack once per call, then hold and shift after every solve.
+// tsat_kernels_mpc_held.hip — the hold and the plan shift of tsat_mpc_run_held (include/tortoise_hip.h; tsat_mpc_held.hpp). The
+// host loop in tsat_kernels.hip owns the handle's buffers and calls the launchers below: the pack once per call, then a hold (this
+// one, or that of tsat_kernels_gg.hip or tsat_kernels_mpc_sensed.hip) and the shift after every solve.
 #include <hip/hip_runtime.h>
 #include "tsat_mpc_held.hpp"
 
@@ -32,17 +32,15 @@ hipError_t tsat_launch_mpc_held_pack(const MpcHeldArgs<double>& a, const double*
   return hipGetLastError();
 }
 
-// the plan shifted by r as the next warm start (also after the hold of tsat_mpc_run_held_gg, tsat_kernels_gg.hip)
+// the plan shifted by r as the next warm start, after whichever hold ran
 hipError_t tsat_launch_mpc_held_shift(const MpcArgs<double>& m, int r, hipStream_t stream) {
   hipLaunchKernelGGL(tsat_mpc_held_shift_kernel, dim3((unsigned)m.T), dim3(64), 0, stream, m, r);
   return hipGetLastError();
 }
 
-// the block of a.r control steps from step a.s.m.step on `stream`, then the plan shift
+// the block of a.r control steps from step a.s.m.step on `stream`
 hipError_t tsat_launch_mpc_held(const MpcHeldArgs<double>& a, int error_state, hipStream_t stream) {
   const unsigned T = (unsigned)a.s.m.T;
   hipLaunchKernelGGL(error_state ? tsat_mpc_held_kernel<1> : tsat_mpc_held_kernel<0>, dim3((T + 63) / 64), dim3(64), 0, stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return tsat_launch_mpc_held_shift(a.s.m, a.r, stream);
+  return hipGetLastError();
 }

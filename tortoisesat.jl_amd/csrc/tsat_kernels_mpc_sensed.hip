@@ -1,8 +1,7 @@
 // tsat_kernels_mpc_sensed.hip — the kernels of tsat_mpc_run_held_sensed (include/tortoise_hip.h; tsat_mpc_sensed.hpp): the hold of
 // the re-planning loop commanding and re-planning from a measurement, with and without the gravity rows, and the pack that makes
-// the bias records and the call's first measurement. A translation unit of its own, so that no existing kernel is recompiled
-// differently. The host loop in tsat_kernels.hip owns the handle's buffers and calls the launchers below; the plan shift after a
-// block is the held loop's own (tsat_launch_mpc_held_shift, tsat_kernels_mpc_held.hip).
+// the bias records and the call's first measurement. The host loop in tsat_kernels.hip owns the handle's buffers and calls the
+// launchers below.
 #include <hip/hip_runtime.h>
 #include "tsat_mpc_sensed.hpp"
 
@@ -31,7 +30,7 @@ hipError_t tsat_launch_mpc_sensed_pack(const MpcSensedArgs<double>& a, const dou
   return hipGetLastError();
 }
 
-// the block of a.h.r control steps alone; a.GT == null: the instantiation without the gravity rows
+// the block of a.h.r control steps, as tsat_launch_mpc_held; a.GT == null: the instantiation without the gravity rows
 hipError_t tsat_launch_mpc_sensed(const MpcSensedArgs<double>& a, int error_state, hipStream_t stream) {
   const unsigned T = (unsigned)a.h.s.m.T;
   auto k = a.GT ? (error_state ? tsat_mpc_sensed_gg_kernel<1> : tsat_mpc_sensed_gg_kernel<0>)

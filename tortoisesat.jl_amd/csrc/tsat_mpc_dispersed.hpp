@@ -9,7 +9,8 @@
 // limits ([T][SATW]); the records are made on the device once per call by dispersed_pack_record (mpc_dispersed_pack), the
 // model's plant when the call gives none, +-inf limits when it gives none — so the step has one code path. dyn_sim_h<real, 0>
 // on the per-trajectory Traj, plant_noise, brow_index and ensemble_angle are the functions the ensemble roll-out calls; the RK4
-// stage sequence is the one of ensemble_rollout (draw the stage's nine values, evaluate, combine).
+// stage sequence is the one of ensemble_rollout (draw the stage's nine values, evaluate, combine). The pieces of a control step
+// (the sample test, the RK4 step, the record, the tally) are functions here and serve the held loops of tsat_mpc_held.hpp as well.
 //
 // Between launches a trajectory keeps two integers in MpcDispRec: the first sample that met the statistic's thresholds and
 // the clipped steps so far. Sample j (1-based) of a call is x_{j-1}; step s judges sample s + 1 before it advances, the last
@@ -47,6 +48,75 @@ TSAT_DEV void mpc_dispersed_pack(const real* plant, const real* P, real us, real
   rec[t].clipped = 0;
 }
 
+// The pieces of a control step, shared by every plant loop: mpc_held_block (tsat_mpc_held.hpp) runs them on every lane,
+// mpc_dispersed_trajectory below on lane 0 — all but mpc_rk4, whose stages it keeps inline for the reason given there.
+
+// sample j (1-based) of the call is judged: the first one inside both thresholds is kept
+template <typename real>
+TSAT_DEV void mpc_sample(const EnsArgs<real>& e, const Traj<real>& tr, const real x[7], int j, int& first) {
+  const real wj = sqrt_(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  if (first == 0 && j > e.min_steps && wj < e.w_tol) {
+    if (ensemble_angle<real>(tr, x) < e.ang_tol) first = j;
+  }
+}
+
+// what acts on the body in an RK4 stage besides m x B: nothing here (GgEnv of tsat_gg.hpp adds the gravity-gradient term).
+// `row`: the table row of the stage, x: the stage state as integrated, k: the stage's increment
+struct NoEnv {
+  template <typename real>
+  TSAT_DEV void stage(const Traj<real>&, int, const real*, real*) const {}
+};
+
+// one RK4 step of the plant tp under the applied dipole us, field rows b0, b1, b2 (table rows i0, i1, i2): the stage sequence of
+// ensemble_rollout (draw the stage's nine values of (gid, knot, stage), evaluate, combine)
+template <typename real, typename Env>
+TSAT_DEV void mpc_rk4(const Traj<real>& tp, const EnsArgs<real>& e, bool noisy, long long gid, int knot, const real x[7],
+                      const real us[3], const real b0[3], const real b1[3], const real b2[3], const Env& env, int i0, int i1, int i2,
+                      real xn[7]) {
+  real k1[7], k2[7], k3[7], k4[7], t[7], nz[9];
+  for (int i = 0; i < 9; ++i) nz[i] = 0;
+  if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 0, e.sg, e.sa, e.fa, nz);
+  dyn_sim_h<real, 0>(tp, x, us, b0, noisy, nz, k1);
+  env.stage(tp, i0, x, k1);
+  for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k1[i];
+  if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 1, e.sg, e.sa, e.fa, nz);
+  dyn_sim_h<real, 0>(tp, t, us, b1, noisy, nz, k2);
+  env.stage(tp, i1, t, k2);
+  for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k2[i];
+  if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 2, e.sg, e.sa, e.fa, nz);
+  dyn_sim_h<real, 0>(tp, t, us, b1, noisy, nz, k3);
+  env.stage(tp, i1, t, k3);
+  for (int i = 0; i < 7; ++i) t[i] = x[i] + k3[i];
+  if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 3, e.sg, e.sa, e.fa, nz);
+  dyn_sim_h<real, 0>(tp, t, us, b2, noisy, nz, k4);
+  env.stage(tp, i2, t, k4);
+  for (int i = 0; i < 7; ++i) xn[i] = x[i] + (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) * (real)(1.0 / 6.0);
+}
+
+// the last sample j = n of the call is judged, then the record of the call's history
+template <typename real>
+TSAT_DEV tsat_tvlqr_stats mpc_record(const EnsArgs<real>& e, const Traj<real>& tr, const real xn[7], int n, int& first) {
+  const real wN = sqrt_(xn[0] * xn[0] + xn[1] * xn[1] + xn[2] * xn[2]);
+  const real angN = ensemble_angle<real>(tr, xn);
+  if (first == 0 && n > e.min_steps && wN < e.w_tol && angN < e.ang_tol) first = n;
+  tsat_tvlqr_stats st;
+  st.slew_index = first;
+  st.failed = first ? 0 : 1;
+  st.slew_time = (double)tr.h * (first ? (double)first : (double)n);
+  st.final_w_norm = (double)wN;
+  st.final_angle = (double)angN;
+  return st;
+}
+
+// executed counts of the solve that has just finished, added to the loop's running sums
+template <typename real>
+TSAT_DEV void mpc_tally(const MpcArgs<real>& m, int traj) {
+  if (!m.tally) return;
+  const tsat_stats& st = m.stats[traj];
+  long long* tl = m.tally + (size_t)traj * 4;
+  tl[0] += st.n_backward; tl[1] += st.n_forward; tl[2] += (st.outer_iters > 1 ? st.outer_iters - 1 : 0); tl[3] += st.inner_iters;
+}
+
 template <typename real>
 TSAT_DEV void mpc_dispersed_trajectory(const MpcDispArgs<real>& a, int traj) {
   const MpcArgs<real>& m = a.m;
@@ -74,12 +144,7 @@ TSAT_DEV void mpc_dispersed_trajectory(const MpcDispArgs<real>& a, int traj) {
     MpcDispRec rec = a.rec[traj];
     real x[7], uc[3], us[3];
     for (int i = 0; i < 7; ++i) x[i] = lds[L_TR + P_X0 + i];
-    {  // sample j = step + 1
-      const real wj = sqrt_(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-      if (rec.first == 0 && m.step + 1 > e.min_steps && wj < e.w_tol) {
-        if (ensemble_angle<real>(tr, x) < e.ang_tol) rec.first = m.step + 1;
-      }
-    }
+    mpc_sample<real>(e, tr, x, m.step + 1, rec.first);
     for (int c = 0; c < 3; ++c) uc[c] = plant.command(c, XUg[7 + c], cs);
     plant.actuate(uc, cs, us);
     rec.clipped += plant.clipped;
@@ -91,6 +156,8 @@ TSAT_DEV void mpc_dispersed_trajectory(const MpcDispArgs<real>& a, int traj) {
     const bool noisy = a.noisy != 0;
     const long long gid = e.nid0 ? e.nid0[traj] : (long long)traj;
     const int knot = (int)(a.step0 + (long long)m.step);
+    // the stages of mpc_rk4 without an Env, kept inline: called as a function they cost this kernel eight registers and 90
+    // instructions (tools/isa_compare.py, tools/resource_usage.py)
     real k1[7], k2[7], k3[7], k4[7], t[7], nz[9];
     for (int i = 0; i < 9; ++i) nz[i] = 0;
     if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 0, e.sg, e.sa, e.fa, nz);
@@ -111,24 +178,10 @@ TSAT_DEV void mpc_dispersed_trajectory(const MpcDispArgs<real>& a, int traj) {
     for (int i = 0; i < 7; ++i) { hx[i] = x[i]; Pg[P_X0 + i] = xn[i]; }
     for (int c = 0; c < 3; ++c) hu[c] = uc[c];                 // the limited command, units of u_scale
     Pg[P_TAU0] = (real)(tr.tau0 + tr.dtau);
-    if (m.tally) {
-      const tsat_stats& st = m.stats[traj];
-      long long* tl = m.tally + (size_t)traj * 4;
-      tl[0] += st.n_backward; tl[1] += st.n_forward; tl[2] += (st.outer_iters > 1 ? st.outer_iters - 1 : 0); tl[3] += st.inner_iters;
-    }
+    mpc_tally<real>(m, traj);
     if (m.step == m.n_steps - 1) {  // last sample j = n_steps + 1, then the record
       for (int i = 0; i < 7; ++i) hx[7 + i] = xn[i];
-      const int n = m.n_steps + 1;
-      const real wN = sqrt_(xn[0] * xn[0] + xn[1] * xn[1] + xn[2] * xn[2]);
-      const real angN = ensemble_angle<real>(tr, xn);
-      if (rec.first == 0 && n > e.min_steps && wN < e.w_tol && angN < e.ang_tol) rec.first = n;
-      tsat_tvlqr_stats st;
-      st.slew_index = rec.first;
-      st.failed = rec.first ? 0 : 1;
-      st.slew_time = (double)tr.h * (rec.first ? (double)rec.first : (double)n);
-      st.final_w_norm = (double)wN;
-      st.final_angle = (double)angN;
-      e.stats[traj] = st;
+      e.stats[traj] = mpc_record<real>(e, tr, xn, m.n_steps + 1, rec.first);
       if (a.d.nclip) a.d.nclip[traj] = rec.clipped;
     }
     a.rec[traj] = rec;

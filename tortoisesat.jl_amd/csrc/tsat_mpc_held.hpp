@@ -10,11 +10,12 @@
 // by mpc_held_pack: the packed plant of dispersed_pack_record, the limits, xf, dt and dtau. x0 and tau0 live in the parameter
 // record the solve reads them from and are advanced there. No LDS, no barrier.
 //
-// The step is the every-step loop's (mpc_dispersed_trajectory, tsat_mpc_dispersed.hpp): DispersedPlant, dyn_sim_h<real, 0>,
-// plant_noise, brow_index and ensemble_angle in the same sequence, so replan_every = 1 repeats tsat_mpc_run_dispersed operation
-// for operation; dx and the gain product are the forward sweeps' policy (mpc_held_state_diff, mpc_held_feedback below). The
-// table clock advances by one rounded addition per step, tau <- tau + dtau, and the rows of a step are those of brow_index at
-// knot 0 of the current clock — the clock the every-step loop has at that step.
+// The step is the every-step loop's: the pieces of tsat_mpc_dispersed.hpp (mpc_sample, mpc_rk4, mpc_record, mpc_tally) around
+// DispersedPlant, so replan_every = 1 repeats tsat_mpc_run_dispersed operation for operation; dx and the gain product are the
+// forward sweeps' policy (mpc_held_state_diff, mpc_held_feedback below). The table clock advances by one rounded addition per step,
+// tau <- tau + dtau, and the rows of a step are those of brow_index at knot 0 of the current clock — the clock the every-step loop
+// has at that step. mpc_held_block is the one block of every held loop: what acts on the body is its Env (NoEnv; GgEnv of
+// tsat_gg.hpp), what the controller is fed its Feed (TrueFeed; SensedFeed of tsat_mpc_sensed.hpp).
 #pragma once
 #include "tsat_mpc_dispersed.hpp"
 
@@ -69,77 +70,6 @@ TSAT_DEV void mpc_held_load(DispersedPlant<real>& pl, const Traj<real>& tr, cons
   for (int c = 0; c < 3; ++c) { pl.lo[c] = hr[(size_t)(HELD_SAT + c) * st]; pl.hi[c] = hr[(size_t)(HELD_SAT + 3 + c) * st]; }
 }
 
-// The pieces of a control step, as mpc_dispersed_trajectory has them inline (tsat_mpc_dispersed.hpp), operation for operation.
-// They are restated here and not factored out of that kernel and of the forward sweeps: either factoring changes the instruction
-// streams of existing kernels (tools/isa_compare.py), and those stay as they are. What holds the copies to their
-// originals: replan_every = 1 is tested bit-equal to tsat_mpc_run_dispersed, the held commands against the oracle's policy.
-
-// sample j (1-based) of the call is judged: the first one inside both thresholds is kept
-template <typename real>
-TSAT_DEV void mpc_held_sample(const EnsArgs<real>& e, const Traj<real>& tr, const real x[7], int j, int& first) {
-  const real wj = sqrt_(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-  if (first == 0 && j > e.min_steps && wj < e.w_tol) {
-    if (ensemble_angle<real>(tr, x) < e.ang_tol) first = j;
-  }
-}
-
-// what acts on the body in an RK4 stage besides m x B: nothing here (GgEnv of tsat_gg.hpp adds the gravity-gradient term).
-// `row`: the table row of the stage, x: the stage state as integrated, k: the stage's increment
-struct NoEnv {
-  template <typename real>
-  TSAT_DEV void stage(const Traj<real>&, int, const real*, real*) const {}
-};
-
-// one RK4 step of the plant tp under the applied dipole us, field rows b0, b1, b2 (table rows i0, i1, i2): the stage sequence of
-// ensemble_rollout (draw the stage's nine values of (gid, knot, stage), evaluate, combine)
-template <typename real, typename Env>
-TSAT_DEV void mpc_held_rk4(const Traj<real>& tp, const EnsArgs<real>& e, bool noisy, long long gid, int knot, const real x[7],
-                           const real us[3], const real b0[3], const real b1[3], const real b2[3], const Env& env, int i0, int i1,
-                           int i2, real xn[7]) {
-  real k1[7], k2[7], k3[7], k4[7], t[7], nz[9];
-  for (int i = 0; i < 9; ++i) nz[i] = 0;
-  if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 0, e.sg, e.sa, e.fa, nz);
-  dyn_sim_h<real, 0>(tp, x, us, b0, noisy, nz, k1);
-  env.stage(tp, i0, x, k1);
-  for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k1[i];
-  if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 1, e.sg, e.sa, e.fa, nz);
-  dyn_sim_h<real, 0>(tp, t, us, b1, noisy, nz, k2);
-  env.stage(tp, i1, t, k2);
-  for (int i = 0; i < 7; ++i) t[i] = x[i] + (real)0.5 * k2[i];
-  if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 2, e.sg, e.sa, e.fa, nz);
-  dyn_sim_h<real, 0>(tp, t, us, b1, noisy, nz, k3);
-  env.stage(tp, i1, t, k3);
-  for (int i = 0; i < 7; ++i) t[i] = x[i] + k3[i];
-  if (noisy) plant_noise<real>(e.k0, e.k1, gid, knot, 3, e.sg, e.sa, e.fa, nz);
-  dyn_sim_h<real, 0>(tp, t, us, b2, noisy, nz, k4);
-  env.stage(tp, i2, t, k4);
-  for (int i = 0; i < 7; ++i) xn[i] = x[i] + (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) * (real)(1.0 / 6.0);
-}
-
-// the last sample j = n of the call is judged, then the record of the call's history
-template <typename real>
-TSAT_DEV tsat_tvlqr_stats mpc_held_record(const EnsArgs<real>& e, const Traj<real>& tr, const real xn[7], int n, int& first) {
-  const real wN = sqrt_(xn[0] * xn[0] + xn[1] * xn[1] + xn[2] * xn[2]);
-  const real angN = ensemble_angle<real>(tr, xn);
-  if (first == 0 && n > e.min_steps && wN < e.w_tol && angN < e.ang_tol) first = n;
-  tsat_tvlqr_stats st;
-  st.slew_index = first;
-  st.failed = first ? 0 : 1;
-  st.slew_time = (double)tr.h * (first ? (double)first : (double)n);
-  st.final_w_norm = (double)wN;
-  st.final_angle = (double)angN;
-  return st;
-}
-
-// executed counts of the solve that has just finished, added to the loop's running sums
-template <typename real>
-TSAT_DEV void mpc_held_tally(const MpcArgs<real>& m, int traj) {
-  if (!m.tally) return;
-  const tsat_stats& st = m.stats[traj];
-  long long* tl = m.tally + (size_t)traj * 4;
-  tl[0] += st.n_backward; tl[1] += st.n_forward; tl[2] += (st.outer_iters > 1 ? st.outer_iters - 1 : 0); tl[3] += st.inner_iters;
-}
-
 // The iLQR policy of the forward sweeps at a knot (forward_sweep, tsat_device.hpp; forward_sweep_packed, tsat_packed.hpp) at
 // alpha = 0: the state difference the gains act on, and component c of u + K dx — the sum starts from u, columns ascending.
 // x: the flown state; xu: the plan's record; kd: the knot's gains, rows of 7.
@@ -167,9 +97,28 @@ TSAT_DEV real mpc_held_feedback(real u, const real kd[21], int c, const real dx[
   return v;
 }
 
+// What the controller is fed, as Env answers what acts on the body: the state y the gains act on (`sn`, a Sensor of
+// ensemble_rollout: y = sn.state(x) at every step after a block's first) and the x0 a solve starts from, which P_X0 carries between
+// launches. TrueFeed: both are the plant's true state. SensedFeed of tsat_mpc_sensed.hpp: measurements.
+struct TrueFeed {
+  TrueState sn;
+  // the block begins: the true state, and the y of its first step
+  template <typename real>
+  TSAT_DEV void load(const TSAT_GLOBAL real* Pg, real x[7], real y[7]) {
+    for (int i = 0; i < 7; ++i) y[i] = x[i] = Pg[P_X0 + i];
+  }
+  // y of step j of the block, for a history of its own
+  template <typename real>
+  TSAT_DEV void row(int, const real*) {}
+  // the block ends in the true state x: what the next solve starts from (`last`: none follows in this call; knot: its step)
+  // the block ends in the true state x: what the next solve starts from (y: room for it)
+  template <typename real>
+  TSAT_DEV const real* next(long long, bool, const real x[7], real*) { return x; }
+};
+
 // trajectory t through the a.r control steps of its block
-template <typename real, int ES, typename Env = NoEnv>
-TSAT_DEV void mpc_held_block(const MpcHeldArgs<real>& a, int t, const Env& env = Env()) {
+template <typename real, int ES, typename Env = NoEnv, typename Feed = TrueFeed>
+TSAT_DEV void mpc_held_block(const MpcHeldArgs<real>& a, int t, const Env& env = Env(), Feed feed = Feed()) {
   const MpcArgs<real>& m = a.s.m;
   const EnsArgs<real>& e = a.s.d.e;
   if (t >= m.T) return;
@@ -193,22 +142,24 @@ TSAT_DEV void mpc_held_block(const MpcHeldArgs<real>& a, int t, const Env& env =
   MpcDispRec rec = a.s.rec[t];
   const bool noisy = a.s.noisy != 0;
   const long long gid = e.nid0 ? e.nid0[t] : (long long)t;
-  real x[7];
-  for (int i = 0; i < 7; ++i) x[i] = Pg[P_X0 + i];
-  mpc_held_tally<real>(m, t);                                     // the block's one solve
+  real x[7], y[7];
+  feed.load(Pg, x, y);
+  mpc_tally<real>(m, t);                                     // the block's one solve
   real* hx = m.HX + ((size_t)t * (m.n_steps + 1) + m.step) * 7;
   real* hu = m.HU + ((size_t)t * m.n_steps + m.step) * 3;
   TSAT_NO_UNROLL
   for (int j = 0; j < a.r; ++j) {
     const int s = m.step + j;
-    mpc_held_sample<real>(e, tr, x, s + 1, rec.first);
+    const int knot = (int)(a.s.step0 + (long long)s);
+    mpc_sample<real>(e, tr, x, s + 1, rec.first);                  // the statistic judges the true state
     real xu[XUW];
     for (int i = 0; i < XUW; ++i) xu[i] = XUg[(size_t)j * XUW + i];
     real v[3] = {xu[7], xu[8], xu[9]};
+    if (j > 0) feed.sn.state(gid, knot, noisy, x, y);              // s >= 1: an older sample exists, and knot > 0 says so
     if (j > 0 && a.feedback) {                                   // the solver's policy around the plan, alpha = 0
       real kd[21], dx[7];
       for (int i = 0; i < 21; ++i) kd[i] = KDg[(size_t)j * KDW + i];
-      mpc_held_state_diff<real, ES>(x, xu, dx);
+      mpc_held_state_diff<real, ES>(y, xu, dx);
       for (int c = 0; c < 3; ++c) v[c] = mpc_held_feedback<real, ES>(v[c], kd, c, dx);
     }
     real uc[3], us[3], xn[7];
@@ -223,17 +174,19 @@ TSAT_DEV void mpc_held_block(const MpcHeldArgs<real>& a, int t, const Env& env =
     const int i2 = brow_index(tr, 0, 1.0);
     const TSAT_GLOBAL real* p2 = tr.bt + (size_t)i2 * 4;
     const real b0[3] = {p0[0], p0[1], p0[2]}, b1[3] = {p1[0], p1[1], p1[2]}, b2[3] = {p2[0], p2[1], p2[2]};
-    mpc_held_rk4<real>(tp, e, noisy, gid, (int)(a.s.step0 + (long long)s), x, us, b0, b1, b2, env, i0, i1, i2, xn);
+    mpc_rk4<real>(tp, e, noisy, gid, knot, x, us, b0, b1, b2, env, i0, i1, i2, xn);
     for (int i = 0; i < 7; ++i) { hx[(size_t)j * 7 + i] = x[i]; x[i] = xn[i]; }
+    feed.row(j, y);
     for (int c = 0; c < 3; ++c) hu[(size_t)j * 3 + c] = uc[c];   // the limited command, units of u_scale
     tr.tau0 = tr.tau0 + tr.dtau;
   }
   rec.clipped += plant.clipped;
-  for (int i = 0; i < 7; ++i) Pg[P_X0 + i] = x[i];
+  const real* x0 = feed.next(gid, noisy, x, y);
+  for (int i = 0; i < 7; ++i) Pg[P_X0 + i] = x0[i];
   Pg[P_TAU0] = (real)tr.tau0;
   if (m.step + a.r == m.n_steps) {  // last sample j = n_steps + 1, then the record
     for (int i = 0; i < 7; ++i) hx[(size_t)a.r * 7 + i] = x[i];
-    e.stats[t] = mpc_held_record<real>(e, tr, x, m.n_steps + 1, rec.first);
+    e.stats[t] = mpc_record<real>(e, tr, x, m.n_steps + 1, rec.first);
     if (a.s.d.nclip) a.s.d.nclip[t] = rec.clipped;
   }
   a.s.rec[t] = rec;

@@ -15,11 +15,7 @@
 // well (step0 >= 0 is validated). The measurement of s = 0, which has no older sample whatever step0 is, is made by the pack
 // launch before the first solve, through a copy of the arguments with latency 0.
 //
-// The block below RESTATES mpc_held_block (tsat_mpc_held.hpp) rather than giving it a Sensor parameter, by the rule that header
-// states for its own copies: the block differs in where the state is read from, what is written back and when a measurement is
-// taken, and threading those through the parent would change the instruction streams of the four existing hold kernels
-// (tools/isa_compare.py). Every piece of a step that is a function there is called here, not copied. What holds the copy to its
-// original: the ideal sensor is tested equal to tsat_mpc_run_held and tsat_mpc_run_held_gg.
+// The block is mpc_held_block itself (tsat_mpc_held.hpp) with SensedFeed below as its Feed, as GgEnv is its Env.
 #pragma once
 #include "tsat_sensed.hpp"
 
@@ -71,96 +67,51 @@ TSAT_DEV void mpc_sensed_pack(const MpcSensedArgs<real>& a, const real* sensor, 
   }
 }
 
-// trajectory t through the a.h.r control steps of its block: mpc_held_block with the command computed from y
-template <typename real, int ES, typename Env>
-TSAT_DEV void mpc_sensed_block(const MpcSensedArgs<real>& a, int t, const Env& env) {
-  const MpcHeldArgs<real>& ha = a.h;
-  const MpcArgs<real>& m = ha.s.m;
-  const EnsArgs<real>& e = ha.s.d.e;
-  const int NS = m.N;
-  const size_t st = (size_t)m.T;
-  const TSAT_GLOBAL real* hr = (const TSAT_GLOBAL real*)(ha.s.d.PL + t);
-  TSAT_GLOBAL real* Pg = (TSAT_GLOBAL real*)(m.P + (size_t)t * PSTRIDE);
-  TSAT_GLOBAL real* xt = (TSAT_GLOBAL real*)(a.XT + t);
-  Traj<real> tr = {};
-  for (int i = 0; i < 7; ++i) tr.xf[i] = hr[(size_t)(HELD_XF + i) * st];
-  tr.h = hr[(size_t)HELD_H * st]; tr.hh = (real)0.5 * tr.h; tr.us = m.us;
-  tr.tau0 = (double)Pg[P_TAU0] + (double)Pg[P_TAU0L]; tr.dtau = (double)hr[(size_t)HELD_DTAU * st];
-  tr.N = m.nk ? m.nk[t] : m.N; tr.n_tab = m.n_tab;
-  tr.bt = (const TSAT_GLOBAL real*)(m.BT + (size_t)m.bidx[t] * m.n_tab * 4);
-  DispersedPlant<real> plant(ha.s.d);
-  mpc_held_load<real>(plant, tr, hr, st);
-  const Traj<real>& tp = plant.traj(tr);
-  const real cs = control_scale<real, 0>(tr);
-  const TSAT_GLOBAL real* XUg = (const TSAT_GLOBAL real*)(m.XU + (size_t)t * NS * XUW);
-  const TSAT_GLOBAL real* KDg = (const TSAT_GLOBAL real*)(ha.KD + (size_t)t * (NS - 1) * KDW);
-  MpcDispRec rec = ha.s.rec[t];
-  const bool noisy = ha.s.noisy != 0;
-  const long long gid = e.nid0 ? e.nid0[t] : (long long)t;
-  Sensed<real> sn(a.s);
-  sn.load(0, t);
-  real x[7], y[7];
-  for (int i = 0; i < 7; ++i) {
-    x[i] = xt[(size_t)(MSX_X + i) * st];
-    sn.hy[i] = xt[(size_t)(MSX_HY + i) * st];
-    y[i] = Pg[P_X0 + i];                                           // y of the block's first step: what the solve started from
+// The Feed of mpc_held_block (tsat_mpc_held.hpp) that hands the controller measurements: `sn` is the sensor of trajectory t with
+// its latency record restored, the true state comes from and goes back to XT, every step's y goes to HY, and P_X0 carries the
+// measurement the next solve starts from until the call's last block puts the true state back.
+template <typename real>
+struct SensedFeed {
+  const MpcHeldArgs<real>& h;
+  Sensed<real> sn;
+  TSAT_GLOBAL real* xt;      // the trajectory's column of XT, stride st
+  const size_t st;
+  real* hy;                  // its row of HY at the block's first step
+  TSAT_DEV SensedFeed(const MpcSensedArgs<real>& a, int t)
+      : h(a.h), sn(a.s), xt((TSAT_GLOBAL real*)(a.XT + t)), st((size_t)a.h.s.m.T),
+        hy(a.HY + ((size_t)t * a.h.s.m.n_steps + a.h.s.m.step) * 7) {
+    sn.load(0, t);
   }
-  mpc_held_tally<real>(m, t);                                     // the block's one solve
-  real* hx = m.HX + ((size_t)t * (m.n_steps + 1) + m.step) * 7;
-  real* hu = m.HU + ((size_t)t * m.n_steps + m.step) * 3;
-  real* hy = a.HY + ((size_t)t * m.n_steps + m.step) * 7;
-  TSAT_NO_UNROLL
-  for (int j = 0; j < ha.r; ++j) {
-    const int s = m.step + j;
-    const int knot = (int)(ha.s.step0 + (long long)s);
-    mpc_held_sample<real>(e, tr, x, s + 1, rec.first);             // the statistic judges the true state
-    if (j > 0) sn.state(gid, knot, noisy, x, y);                   // s >= 1: the old sample exists, and knot > 0 says so
-    real xu[XUW];
-    for (int i = 0; i < XUW; ++i) xu[i] = XUg[(size_t)j * XUW + i];
-    real v[3] = {xu[7], xu[8], xu[9]};
-    if (j > 0 && ha.feedback) {                                    // the solver's policy around the plan, on the measurement
-      real kd[21], dx[7];
-      for (int i = 0; i < 21; ++i) kd[i] = KDg[(size_t)j * KDW + i];
-      mpc_held_state_diff<real, ES>(y, xu, dx);
-      for (int c = 0; c < 3; ++c) v[c] = mpc_held_feedback<real, ES>(v[c], kd, c, dx);
+  // the block begins: the true state, the sensor's memory, and the y of its first step — what the solve started from
+  TSAT_DEV void load(const TSAT_GLOBAL real* Pg, real x[7], real y[7]) {
+    for (int i = 0; i < 7; ++i) {
+      x[i] = xt[(size_t)(MSX_X + i) * st];
+      sn.hy[i] = xt[(size_t)(MSX_HY + i) * st];
+      y[i] = Pg[P_X0 + i];
     }
-    real uc[3], us[3], xn[7];
-    for (int c = 0; c < 3; ++c) uc[c] = plant.command(c, v[c], cs);
-    plant.actuate(uc, cs, us);
-    const int i0 = brow_index(tr, 0, 0.0);
-    const TSAT_GLOBAL real* p0 = tr.bt + (size_t)i0 * 4;
-    const int i1 = brow_index(tr, 0, 0.5);
-    const TSAT_GLOBAL real* p1 = tr.bt + (size_t)i1 * 4;
-    const int i2 = brow_index(tr, 0, 1.0);
-    const TSAT_GLOBAL real* p2 = tr.bt + (size_t)i2 * 4;
-    const real b0[3] = {p0[0], p0[1], p0[2]}, b1[3] = {p1[0], p1[1], p1[2]}, b2[3] = {p2[0], p2[1], p2[2]};
-    mpc_held_rk4<real>(tp, e, noisy, gid, knot, x, us, b0, b1, b2, env, i0, i1, i2, xn);
-    for (int i = 0; i < 7; ++i) { hx[(size_t)j * 7 + i] = x[i]; hy[(size_t)j * 7 + i] = y[i]; x[i] = xn[i]; }
-    for (int c = 0; c < 3; ++c) hu[(size_t)j * 3 + c] = uc[c];   // the limited command, units of u_scale
-    tr.tau0 = tr.tau0 + tr.dtau;
   }
-  rec.clipped += plant.clipped;
-  Pg[P_TAU0] = (real)tr.tau0;
-  if (m.step + ha.r == m.n_steps) {  // the call ends: the TRUE state goes back to the resident batch, then the record
-    for (int i = 0; i < 7; ++i) { Pg[P_X0 + i] = x[i]; hx[(size_t)ha.r * 7 + i] = x[i]; }
-    e.stats[t] = mpc_held_record<real>(e, tr, x, m.n_steps + 1, rec.first);
-    if (ha.s.d.nclip) ha.s.d.nclip[t] = rec.clipped;
-  } else {                           // the next solve starts from the measurement of the step it plans from
-    sn.state(gid, (int)(ha.s.step0 + (long long)(m.step + ha.r)), noisy, x, y);
-    for (int i = 0; i < 7; ++i) Pg[P_X0 + i] = y[i];
+  TSAT_DEV void row(int j, const real y[7]) {
+    for (int i = 0; i < 7; ++i) hy[(size_t)j * 7 + i] = y[i];
   }
-  for (int i = 0; i < 7; ++i) {
-    xt[(size_t)(MSX_X + i) * st] = x[i];
-    xt[(size_t)(MSX_HY + i) * st] = sn.hy[i];
+  // the block ends: the next solve starts from the measurement of the step it plans from; when the call ends here, the resident
+  // batch gets the TRUE state back
+  TSAT_DEV const real* next(long long gid, bool noisy, const real x[7], real y[7]) {
+    const int s = h.s.m.step + h.r;
+    const bool last = s == h.s.m.n_steps;
+    if (!last) sn.state(gid, (int)(h.s.step0 + (long long)s), noisy, x, y);
+    for (int i = 0; i < 7; ++i) {
+      xt[(size_t)(MSX_X + i) * st] = x[i];
+      xt[(size_t)(MSX_HY + i) * st] = sn.hy[i];
+    }
+    return last ? x : y;
   }
-  ha.s.rec[t] = rec;
-}
+};
 
 // the four kernels' bodies: without and with the gravity rows of tsat_gg.hpp
 template <typename real, int ES>
 TSAT_DEV void mpc_sensed_traj(const MpcSensedArgs<real>& a, int t) {
   if (t >= a.h.s.m.T) return;
-  mpc_sensed_block<real, ES>(a, t, NoEnv());
+  mpc_held_block<real, ES>(a.h, t, NoEnv(), SensedFeed<real>(a, t));
 }
 
 template <typename real, int ES>
@@ -168,7 +119,7 @@ TSAT_DEV void mpc_sensed_gg_traj(const MpcSensedArgs<real>& a, int t) {
   const MpcArgs<real>& m = a.h.s.m;
   if (t >= m.T) return;
   const GgEnv<real> env{(const TSAT_GLOBAL real*)(a.GT + (size_t)m.bidx[t] * m.n_tab * 4)};
-  mpc_sensed_block<real, ES>(a, t, env);
+  mpc_held_block<real, ES>(a.h, t, env, SensedFeed<real>(a, t));
 }
 
 }  // namespace tsat

@@ -23,8 +23,8 @@
 // then the limit (0: the component clip of DispersedPlant::command; 1: u / beta when beta = max_c u_c / (u_c > 0 ? hi_c : lo_c)
 // exceeds 1) and the parent's G u_sat + m_res / u_scale held over the four stages.
 //
-// Lane = realisation, and the loop restates ensemble_rollout of tsat_ensemble.hpp with the command lines replaced (as
-// tsat_mpc_held.hpp restates the step), so that ensemble_rollout and every kernel built on it keep their instruction streams. The
+// Lane = realisation, and the loop restates ensemble_rollout of tsat_ensemble.hpp with the command lines replaced, so
+// that ensemble_rollout and every kernel built on it keep their instruction streams. The
 // plant types are the parents' own, DispersedPlant and GgPlant, used as they are: load, traj, command, actuate, disturb, store.
 // No gain rows: per knot the wave reads the reference record (when tracking) and three field rows by scalar loads; the gains,
 // the limits, their reciprocals and xf are loaded once per wave. X == null, feedforward and limit_mode are launch-uniform and
