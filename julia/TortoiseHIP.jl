@@ -624,7 +624,10 @@ end
 # sigma_att, sigma_mag —, then Int32 latency and Int32 reserved: 32 bytes), a struct the static cross-check of this shim against
 # the header has no mapping for, so a `ccall` with a `Ref` to its mirror could not be held to the header; they stay unbound until
 # it can. The Python layer binds them (tracking.attitude_ensemble_sensed, tracking.attitude_ensemble_pd_sensed,
-# mpc.receding_horizon_held_sensed).
-const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsat_pd_ensemble_sensed, :tsat_mpc_run_held_sensed]
+# mpc.receding_horizon_held_sensed). The filtered ensembles take that struct and a `tsat_filter_options*` besides (five Float64 —
+# sigma_v, sigma_u, sigma_a, p0_att, p0_bias —, then Int32 reserved: 48 bytes with the tail padding) and stay unbound for the same
+# reason (tracking.attitude_ensemble_filtered, tracking.attitude_ensemble_pd_filtered).
+const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsat_pd_ensemble_sensed, :tsat_mpc_run_held_sensed,
+                 :tsat_filter_default_options, :tsat_tvlqr_ensemble_filtered, :tsat_pd_ensemble_filtered]
 
 end # module

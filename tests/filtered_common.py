@@ -1,0 +1,399 @@
+"""Shared pieces of tests/test_filtered.py (CPU tier) and tests/test_gpu_filtered.py (GPU tier): the ensemble controllers behind a
+multiplicative EKF (tsat_tvlqr_ensemble_filtered, tsat_pd_ensemble_filtered).
+
+THE REFERENCE (``loop``) is ``sensed_common.loop`` restated, with the recursion of include/tortoise_hip.h (``Ekf``) inserted between
+``measure`` and the law — numpy and the oracle's primitives only (``ol.qmult``, ``ol.inv3``, ``ol.plant_noise``, ``ol.qrot``,
+``ol.dyn7``). With ``filt=None`` it has to equal ``sensed_common.loop`` with max |d| = 0
+(test_filtered.py::test_reference_with_the_filter_off_is_the_sensed_reference); it also returns X_hat and filt_final.
+
+The case of both tiers is ``sensed_common``'s; the filter's levels are FILT below. Every parity test first asserts its conditions on
+references alone with the bar ``gg_common.MOVED`` (``conditions``).
+
+Also: the argument lists of the two entry points and the ctypes binding of the emulated kernels (tests/emu/tsat_emu_filtered.cpp)."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+
+import dispersed_common as dc
+import ensemble_common as ec
+import gg_common as gc
+import pd_common as pc
+import sensed_common as sc
+from conftest import ROOT
+
+FILTER_W = 9
+# the filter of the parity tests: it assumes the sensor's own attitude noise (sensed_common.SIGMAS), a bias random walk and an initial
+# bias spread of the size of sensed_common.BIAS' gyro bias, and a gyro noise of 5e-3 rad/s (near the reference's 0.38 deg/s figure;
+# at the sensor's own 3e-4 rad/s the term (sigma_v h)^2 moves the final states of the 8-slew case by 6e-8 only), so that every option acts
+FILT = dict(sigma_v=5e-3, sigma_u=1e-4, sigma_a=sc.SIGMAS["sigma_att"], p0_att=math.radians(1.0), p0_bias=2e-3)
+# body rate added to the starts of the tests of the prediction across the delay under the PD law: the prediction turns the estimate
+# by h w^, and at the case's own rates (|w| < 1e-3 rad/s) and gains that moves the final state by 5e-8 .. 3e-7, on or under the bar
+FAST = np.array([0.03, -0.02, 0.025])
+
+
+def dq_of(phi):
+    th = math.sqrt(float(phi @ phi))
+    return np.r_[math.cos(th / 2), phi * (0.5 if th == 0.0 else math.sin(th / 2) / th)]
+
+
+def _skew(v):
+    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def _sym(A):
+    """the matrix the upper triangle of A stands for"""
+    return np.triu(A) + np.triu(A, 1).T
+
+
+class Ekf:
+    """the recursion of include/tortoise_hip.h, line for line"""
+
+    def __init__(self, ol, h, filt):
+        self.ol, self.h, self.f = ol, float(h), filt
+
+    def first(self, w_m, q_m):
+        f = self.f
+        self.q = q_m / math.sqrt(float(q_m @ q_m))
+        self.b = np.zeros(3)
+        self.w = np.array(w_m, dtype=np.float64)
+        self.A, self.B, self.D = f["p0_att"] ** 2 * np.eye(3), np.zeros((3, 3)), f["p0_bias"] ** 2 * np.eye(3)
+
+    def step(self, w_m, q_m):
+        ol, h, f, I = self.ol, self.h, self.f, np.eye(3)
+        d = dq_of(h * self.w)                                                          # 1.
+        qm = ol.qmult(self.q, d)
+        V = _skew(d[1:4])
+        Phi = (I + 2 * d[0] * V + 2 * V @ V).T
+        PB = Phi @ self.B                                                              # 2.
+        Am = _sym(Phi @ self.A @ Phi.T - h * (PB + PB.T) + h * h * self.D + (f["sigma_v"] * h) ** 2 * I)
+        Bm = PB - h * self.D
+        Dm = self.D + f["sigma_u"] ** 2 * I
+        e = ol.qmult(np.r_[qm[0], -qm[1:4]], q_m / math.sqrt(float(q_m @ q_m)))        # 3.
+        z = 2.0 * (-1.0 if e[0] < 0 else 1.0) * e[1:4]
+        S = Am + f["sigma_a"] ** 2 * I                                                 # 4.
+        Si = ol.inv3(S)
+        Kt, Kb = Am @ Si, Bm.T @ Si
+        dth, db = Kt @ z, Kb @ z
+        qp = ol.qmult(qm, np.r_[1.0, dth / 2])                                         # 5.
+        self.q = qp / math.sqrt(float(qp @ qp))
+        self.b = self.b + db
+        self.w = w_m - self.b
+        self.A = _sym(Am - Kt @ S @ Kt.T)                                              # 6.
+        self.B = Bm - Kt @ S @ Kb.T
+        self.D = _sym(Dm - Kb @ S @ Kb.T)
+
+    def predicted(self):
+        return self.ol.qmult(self.q, dq_of(self.h * self.w))
+
+    def final(self):
+        return np.r_[self.b, np.sqrt(np.diag(self.A)), np.sqrt(np.diag(self.D))]
+
+
+def loop(ol, law, batch, t, Xr, Ur, gains, x0, opts, gid, Rtab, gm, plant=None, lo=None, hi=None, limit_mode=0, noisy=True, sens=None,
+         latency=0, bias=None, filt=None, predict=True):
+    """``sensed_common.loop`` (from knot 0) with the filter between ``measure`` and the law. ``filt`` None: the raw measurement, the
+    sensed reference itself; ``predict`` False leaves the prediction across the delay out (a condition of the tests, not a mode of
+    the product). Returns X_sim (N, 7), (n_sure, n_maybe), the commands before the limit (N-1, 3), X_hat (N, 7), filt_final (9,),
+    the raw (w_m, q_m) the law would have seen per knot (N, 7)."""
+    NS = batch.N
+    N = NS if batch.n_knots is None else int(batch.n_knots[t])
+    us, h = float(opts.u_scale), float(batch.dt[t])
+    if plant is None:
+        Jp, G, mres = np.asarray(batch.Jmat[t]).reshape(3, 3).T, np.eye(3), np.zeros(3)
+    else:
+        Jp, G, mres = plant[0:9].reshape(3, 3).T, plant[9:18].reshape(3, 3).T, plant[18:21]
+    Xs, Uc, Xh, Ym = np.zeros((NS, 7)), np.zeros((NS - 1, 3)), np.zeros((NS, 7)), np.zeros((NS, 7))
+    x = np.array(x0, dtype=np.float64)
+    n_sure = n_maybe = 0
+    held = None
+    ekf = None if filt is None else Ekf(ol, h, filt)
+    last = N - 1
+    for k in range(0, last):
+        Xs[k] = x
+        xr = batch.xf[t] if Xr is None else Xr[k]
+        b0, b1, b2 = dc._row(batch, t, k, 0.0), dc._row(batch, t, k, 0.5), dc._row(batch, t, k, 1.0)
+        if sens is None:
+            w_m, q_m = x[:3], x[3:7]
+            b_m = ol.qrot(x[3:7] / math.sqrt(float(x[3:7] @ x[3:7])), b0) if law == "pd" else None
+        else:
+            y = sc.measure(ol, batch, t, k, x, opts, gid, sens, bias, noisy)
+            w_m, q_m, b_m = held if (latency and held is not None) else y       # y_max(k-1, 0)
+            held = y
+        Ym[k] = np.r_[w_m, q_m]
+        if ekf is not None:
+            if k == 0:
+                ekf.first(w_m, q_m)
+            elif not (latency and k == 1):                                      # m_0 handed over a second time: no step
+                ekf.step(w_m, q_m)
+            w_m, q_m = ekf.w, (ekf.predicted() if (latency and k > 0 and predict) else ekf.q)
+            Xh[k] = np.r_[w_m, q_m]
+        qe = ol.qmult(np.r_[xr[3], -xr[4:7]], q_m)
+        if law == "tv":
+            dX = np.r_[w_m - xr[:3], qe[1:4]]
+            u = Ur[k] - gains[k].T @ dX
+        else:
+            kd, kp = gains
+            dw = w_m - xr[:3]
+            s = -1.0 if qe[0] < 0 else 1.0
+            treq = -(kd * dw + kp * (s * qe[1:4]))
+            bb = float(b_m @ b_m)
+            m = np.cross(b_m, treq) / bb if bb != 0.0 else np.zeros(3)
+            u = (Ur[k] if Ur is not None else np.zeros(3)) + m / us
+        Uc[k] = u
+        if limit_mode == 1:
+            r = np.array([u[c] / hi[c] if u[c] > 0 else (u[c] / lo[c] if u[c] < 0 else 0.0) for c in range(3)])
+            beta = float(r.max())
+            n_sure += bool(beta - 1.0 > dc.CLIP_BAND)
+            n_maybe += bool(beta - 1.0 > -dc.CLIP_BAND)
+            if beta > 1.0:
+                u = u * (1.0 / beta)
+        elif lo is not None:
+            bl, bh = dc.CLIP_BAND * np.abs(lo), dc.CLIP_BAND * np.abs(hi)
+            n_sure += bool(np.any((lo - u > bl) | (u - hi > bh)))
+            n_maybe += bool(np.any((lo - u > -bl) | (u - hi > -bh)))
+            u = np.minimum(np.maximum(u, lo), hi)
+        ua = G @ u + mres / us
+        nz = [ol.plant_noise(int(opts.noise_seed), int(gid), k, st, opts.sigma_gyro, opts.sigma_att, opts.field_amp) if noisy else None
+              for st in range(4)]
+        rr = [None] * 3 if Rtab is None else [gc._grow(batch, Rtab, t, k, c) for c in (0.0, 0.5, 1.0)]
+
+        def f(xx, bb_, n, r):
+            xn, bn = dc._noisy(ol, xx, bb_, n)
+            kk = h * ol.dyn7(xn, ua, bn, Jp, us)
+            if r is not None:
+                kk[0:3] = kk[0:3] + gc.gg_increment(ol, xx, r, gm, Jp, h)
+            return kk
+
+        k1 = f(x, b0, nz[0], rr[0])
+        k2 = f(x + k1 / 2, b1, nz[1], rr[1])
+        k3 = f(x + k2 / 2, b1, nz[2], rr[1])
+        k4 = f(x + k3, b2, nz[3], rr[2])
+        x = x + (k1 + 2 * k2 + 2 * k3 + k4) / 6
+    Xs[last] = x
+    return Xs, (n_sure, n_maybe), Uc, Xh, (np.zeros(FILTER_W) if ekf is None else ekf.final()), Ym
+
+
+def pairs_of(ol, abi, law, batch, x0_sim, gains, opts, pairs, X=None, U=None, Rtab=None, gm=0.0, plant=None, sat=None, limit_mode=0,
+             x0_nom=None, noise_id0=None, sens=None, latency=0, sensor=None, filt=None, predict=True):
+    """``sensed_common.pairs_of`` through ``loop`` above: its dict plus X_hat (n, N, 7), filt_final (n, 9) and Y_raw (n, N, 7)"""
+    T, M = x0_sim.shape[:2]
+    id0 = np.arange(T, dtype=np.int64) * M if noise_id0 is None else np.asarray(noise_id0, dtype=np.int64)
+    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
+    if law == "pd":
+        gains = (np.broadcast_to(gains[0], (T, 3)), np.broadcast_to(gains[1], (T, 3)))
+    ol.load()
+    res = []
+    for p in pairs:
+        t, m = int(p[0]), int(p[1])
+        g = gains[t] if law == "tv" else (gains[0][t], gains[1][t])
+        kw = dict(lo=None if lo is None else lo[t], hi=None if hi is None else hi[t], limit_mode=limit_mode, sens=sens, latency=latency,
+                  filt=filt, predict=predict)
+        Xr, Ur = None if X is None else X[t], None if U is None else U[t]
+        if m < 0:
+            x0 = x0_nom[t] if x0_nom is not None else X[t, 0]
+            res.append(loop(ol, law, batch, t, Xr, Ur, g, x0, opts, 0, Rtab, gm, None, noisy=False, **kw))
+        else:
+            res.append(loop(ol, law, batch, t, Xr, Ur, g, x0_sim[t, m], opts, id0[t] + m, Rtab, gm, None if plant is None else plant[t, m],
+                            bias=None if sensor is None else sensor[t, m], **kw))
+    pairs = np.asarray(pairs)
+    Xs = np.stack([r[0] for r in res])
+    nk = ec.horizons(batch)[pairs[:, 0]]
+    xf = batch.xf[pairs[:, 0]]
+    st = dc.stats_of(abi, Xs, xf, nk, batch.dt[pairs[:, 0]], opts.min_steps, opts.w_tol, opts.angle_tol)
+    return dict(X_sim=Xs, stats=st, n_sure=np.array([r[1][0] for r in res]), n_maybe=np.array([r[1][1] for r in res]), xf=xf, n_knots=nk,
+                U_cmd=np.stack([r[2] for r in res]), X_hat=np.stack([r[3] for r in res]), filt_final=np.stack([r[4] for r in res]),
+                Y_raw=np.stack([r[5] for r in res]))
+
+
+def conditions(ref_of, sensor, prediction=True):
+    """the conditions of a parity test on references alone (bar gg_common.MOVED, through pd_common.differs). ``ref_of(**over)`` is the
+    reference of the test's call with the named arguments replaced; the call flies sensor biases ``sensor`` with a gyro bias in them.
+    Filtered against raw moves the final state; each of sigma_v, sigma_a, sigma_u and p0_bias moves it; latency 1 against 0 moves it;
+    removing the prediction across the delay moves it (``prediction`` False leaves that one to the test that flies the case on which
+    it shows under the PD law: starts with the body rate FAST under wide limits). Returns the reference of the call itself."""
+    assert np.abs(sensor[..., 0:3]).min() > 0, "the conditions on sigma_u and p0_bias need a gyro bias"
+    ref = ref_of()
+    pc.differs(ref, ref_of(filt=None), "filtered against raw")
+    for name in ("sigma_v", "sigma_a", "sigma_u", "p0_bias"):
+        pc.differs(ref, ref_of(filt=dict(FILT, **{name: 3.0 * FILT[name]})), f"{name} against three times it")
+    pc.differs(ref_of(latency=1), ref_of(latency=0), "latency 1 against 0")
+    if prediction:
+        pc.differs(ref_of(latency=1), ref_of(latency=1, predict=False), "prediction across the delay on against off")
+    return ref
+
+
+def compare_estimates(ref, got, pairs, idx=None):
+    """X_hat and filt_final against the reference to 1e-9, the project's bar for these loops; X_hat zero from the last knot on"""
+    idx = np.arange(len(pairs)) if idx is None else idx
+    t, m = pairs[idx, 0], pairs[idx, 1]
+    dH = float(np.max(np.abs(ref["X_hat"][idx] - got["X_hat"][t, m])))
+    dF = float(np.max(np.abs(ref["filt_final"][idx] - got["filt_final"][t, m])))
+    print(f"max|dX_hat| {dH:.2e}  max|dfilt_final| {dF:.2e} against the reference")
+    assert dH < 1e-9 and dF < 1e-9
+    for i, n in zip(idx, ref["n_knots"][idx]):
+        assert np.all(got["X_hat"][pairs[i, 0], pairs[i, 1], n - 1:] == 0) and np.all(ref["X_hat"][i, n - 1:] == 0)
+        assert np.all(np.abs(got["X_hat"][pairs[i, 0], pairs[i, 1], :n - 1, 3:7]).max(axis=1) > 0)
+
+
+GYRO_BIAS = 2e-3   # rad/s, the long-horizon case
+
+
+def long_case(pkg, ol, N, M):
+    """T = 1, N knots, M realisations: the PD law (10 x pd_common's gains, direction-preserving limit +-0.6) regulating from the
+    workload's start on the model's plant with plant noise, no gravity gradient; the reference's sensor figures (0.38 deg/s, 1 deg),
+    a gyro bias of GYRO_BIAS in a drawn direction per realisation and no other bias, latency 0; the filter with the default figures
+    plus a bias state (p0_bias = GYRO_BIAS). Returns the case with its reference on every realisation."""
+    import mpc_held_common as hc
+    tr = pkg.tracking
+    b = gc.use_3u(pkg, hc.mpc_batch(pkg, T=1, N=N, seed=41, rows=N))
+    x0s = tr.ensemble_initial_states(b.x0, M, np.random.default_rng(5))
+    g = np.random.default_rng(17).standard_normal((1, M, 3))
+    sensor = np.zeros((1, M, 9))
+    sensor[..., 0:3] = GYRO_BIAS * g / np.linalg.norm(g, axis=-1, keepdims=True)
+    sens = dict(sigma_gyro=tr.SENSOR_SIGMA_GYRO, sigma_att=tr.SENSOR_SIGMA_ATT, sigma_mag=0.0)
+    filt = dict(sigma_v=tr.SENSOR_SIGMA_GYRO, sigma_u=0.0, sigma_a=tr.SENSOR_SIGMA_ATT, p0_att=tr.SENSOR_SIGMA_ATT, p0_bias=GYRO_BIAS)
+    kw = dict(X=None, U=None, Rtab=None, gm=0.0, plant=None, sat=hc.SAT, limit_mode=1, x0_nom=np.ascontiguousarray(b.x0),
+              noise_id0=np.array([2 ** 33 + 5], dtype=np.int64), sens=sens, latency=0, sensor=sensor, filt=filt)
+    o = pc.options(ol)
+    pairs = dc.all_pairs(1, M)
+    ref = pairs_of(ol, pkg._abi, "pd", b, x0s, (sc.KD, sc.KP), o, pairs, **kw)
+    return dict(b=b, x0s=x0s, o=o, kw=kw, pairs=pairs, ref=ref, sensor=sensor)
+
+
+def _angles(qa, qb):
+    """rotation angle between rows of two (n, 4) quaternion arrays, neither assumed unit"""
+    c = np.abs(np.sum(qa * qb, axis=1)) / (np.linalg.norm(qa, axis=1) * np.linalg.norm(qb, axis=1))
+    return 2.0 * np.arccos(np.minimum(c, 1.0))
+
+
+def assert_filter_works(c):
+    """on the reference alone, for every realisation: the rms attitude error of X_hat over the last half of the horizon is below
+    that of the raw measurement, and |b^ - bw| at the end is below |bw|"""
+    ref, N = c["ref"], c["b"].N
+    half = slice(N // 2, N - 1)
+    est, raw, db = [], [], []
+    for i, (t, m) in enumerate(c["pairs"]):
+        true = ref["X_sim"][i, half, 3:7]
+        est.append(math.sqrt(float(np.mean(_angles(ref["X_hat"][i, half, 3:7], true) ** 2))))
+        raw.append(math.sqrt(float(np.mean(_angles(ref["Y_raw"][i, half, 3:7], true) ** 2))))
+        db.append(float(np.linalg.norm(ref["filt_final"][i, 0:3] - c["sensor"][t, m, 0:3])))
+    est, raw, db = np.array(est), np.array(raw), np.array(db)
+    print(f"rms attitude error over the last half, deg: raw {np.degrees(raw).min():.3f} .. {np.degrees(raw).max():.3f}, "
+          f"filtered {np.degrees(est).min():.3f} .. {np.degrees(est).max():.3f}; |b^ - bw| {db.min():.2e} .. {db.max():.2e} against {GYRO_BIAS:.1e}")
+    assert np.all(est < raw), "the filter does not beat the raw attitude measurement"
+    assert np.all(db < GYRO_BIAS), "the filter does not estimate the gyro bias"
+
+
+def filter_options(abi, filt):
+    return abi.FilterOptions(sigma_v=filt["sigma_v"], sigma_u=filt["sigma_u"], sigma_a=filt["sigma_a"], p0_att=filt["p0_att"],
+                             p0_bias=filt["p0_bias"], reserved=0)
+
+
+def _outputs(v, abi, filt, fo, estimates):
+    """the three filter arguments of a call: ``fo`` 0 builds the options from ``filt`` (None: f = NULL and no outputs)"""
+    T, M, N = v["T"], v["M"], v["o"].n_knots
+    v["f"] = (None if filt is None else filter_options(abi, filt)) if fo == 0 else fo
+    on = v["f"] is not None
+    v["X_hat"] = np.full((T, M, N, 7), np.nan) if (on and estimates) else None
+    v["filt_final"] = np.full((T, M, FILTER_W), np.nan) if (on and estimates) else None
+
+
+def _tail(v, abi):
+    return [None if v["f"] is None else C.byref(v["f"]), abi.as_dp(v["X_hat"]), abi.as_dp(v["filt_final"])]
+
+
+class TvCall(sc.TvCall):
+    """sensed_common.TvCall followed by the three filter arguments: tsat_tvlqr_ensemble_filtered after the handle, or — ``emu=True`` —
+    emu_tvlqr_ensemble_filtered"""
+
+    def __init__(self, abi, *a, filt=FILT, fo=0, estimates=True, **kw):
+        super().__init__(abi, *a, **kw)
+        _outputs(self.v, abi, filt, fo, estimates)
+
+    def edit(self, **kw):
+        other = sc.TvCall.edit(self, **kw)
+        other.__class__ = TvCall
+        return other
+
+    def c_args(self, emu=False):
+        return super().c_args(emu) + _tail(self.v, self.abi)
+
+    def result(self):
+        return dict(super().result(), X_hat=self.v["X_hat"], filt_final=self.v["filt_final"])
+
+
+class PdCall(sc.PdCall):
+    """sensed_common.PdCall followed by the three filter arguments: tsat_pd_ensemble_filtered after the handle, or
+    emu_pd_ensemble_filtered"""
+
+    def __init__(self, abi, *a, filt=FILT, fo=0, estimates=True, **kw):
+        super().__init__(abi, *a, **kw)
+        _outputs(self.v, abi, filt, fo, estimates)
+
+    def edit(self, **kw):
+        other = sc.PdCall.edit(self, **kw)
+        other.__class__ = PdCall
+        return other
+
+    def c_args(self, names=pc.FIELDS):
+        return super().c_args(names) + _tail(self.v, self.abi)
+
+    def result(self):
+        return dict(super().result(), X_hat=self.v["X_hat"], filt_final=self.v["filt_final"])
+
+
+def filter_rejections(call):
+    """what check_filter and the entry points reject of the filter arguments, as (label, edited call, words of the text)"""
+    abi, f = call.abi, call.v["f"]
+
+    def fo(**kw):
+        o = abi.FilterOptions.from_buffer_copy(f)
+        for k, val in kw.items():
+            setattr(o, k, val)
+        return o
+
+    return [
+        ("sigma_v NaN", call.edit(f=fo(sigma_v=float("nan"))), "must be finite and >= 0"),
+        ("sigma_u inf", call.edit(f=fo(sigma_u=float("inf"))), "must be finite and >= 0"),
+        ("sigma_a negative", call.edit(f=fo(sigma_a=-1e-3)), "must be finite and >= 0"),
+        ("p0_att negative", call.edit(f=fo(p0_att=-1.0)), "must be finite and >= 0"),
+        ("p0_bias NaN", call.edit(f=fo(p0_bias=float("nan"))), "must be finite and >= 0"),
+        ("sigma_a zero", call.edit(f=fo(sigma_a=0.0)), "sigma_a must be > 0"),
+        ("reserved 1", call.edit(f=fo(reserved=1)), "reserved must be 0"),
+    ]
+
+
+class EmuFiltered:
+    """ctypes binding of tests/emu/libtsat_emu_filtered.so (the four emulated kernels), built here by the emulator's pattern rule"""
+
+    def __init__(self, abi):
+        d = os.path.join(ROOT, "tests", "emu")
+        subprocess.check_call(["make", "-C", d, "libtsat_emu_filtered.so"], stdout=subprocess.DEVNULL)
+        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_filtered.so"))
+        self.abi = abi
+
+    def tv(self, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K, **kw):
+        """emu_tvlqr_ensemble_filtered; keyword arguments as ``TvCall``; the result dict of ``tracking.attitude_ensemble_filtered``"""
+        call = TvCall(self.abi, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K=K, **kw)
+        rc = self.lib.emu_tvlqr_ensemble_filtered(*call.c_args(emu=True))
+        if rc != 0:
+            raise RuntimeError(f"emu_tvlqr_ensemble_filtered rc={rc}")
+        return call.result()
+
+    def pd(self, batch, opts, x0_sim, kd, kp, **kw):
+        """emu_pd_ensemble_filtered; keyword arguments as ``PdCall``; the result dict of ``tracking.attitude_ensemble_pd_filtered``"""
+        call = PdCall(self.abi, batch, opts, x0_sim, kd, kp, **kw)
+        rc = self.lib.emu_pd_ensemble_filtered(*call.c_args())
+        if rc != 0:
+            raise RuntimeError(f"emu_pd_ensemble_filtered rc={rc}")
+        return call.result()
+
+    def check(self, call):
+        """check_filter on the filter options of a call"""
+        text = C.create_string_buffer(256)
+        f = call.v["f"]
+        rc = self.lib.emu_filter_check(None if f is None else C.byref(f), text, C.c_int32(256))
+        return rc, text.value.decode()

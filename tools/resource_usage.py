@@ -7,6 +7,9 @@ scratch size and how many scratch_* instructions it contains — i.e. whether th
 driver around them.
 
     python tools/resource_usage.py [profiles/r03/resource_usage.txt]
+    python tools/resource_usage.py profiles/ensemble/filtered_resource_usage.txt --units tsat_kernels_sensed.hip,tsat_kernels_filtered.hip
+With --units every kernel of the named units is listed (the lane-per-realisation roll-outs have no phase functions), not only
+the solve kernels.
 """
 import collections
 import os
@@ -91,22 +94,29 @@ def own_name(full):
 
 
 def main():
-    dst = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r03", "resource_usage.txt")
-    lines = ["Register / scratch / LDS budget of every build of the solve kernel (tools/resource_usage.py; hipcc "
+    argv = list(sys.argv[1:])
+    units, every = UNITS, False
+    if "--units" in argv:
+        i = argv.index("--units")
+        units, every = argv[i + 1].split(","), True
+        del argv[i:i + 2]
+    dst = argv[0] if argv else os.path.join(ROOT, "profiles", "r03", "resource_usage.txt")
+    lines = [("Register / scratch / LDS budget of every kernel of " + ", ".join(units) if every else
+              "Register / scratch / LDS budget of every build of the solve kernel") + " (tools/resource_usage.py; hipcc "
              "-Rpass-analysis=kernel-resource-usage + the ISA listing's per-function info blocks; gfx950, -O3).",
              "Kernels: what the launch reserves. Functions: the non-inlined phase functions, each with its own register allocation;",
              "`scratch insts` = scratch_load / scratch_store instructions in the function's body (spills inside its loops).", ""]
     with tempfile.TemporaryDirectory() as tmp:
-        for unit in UNITS:
+        for unit in units:
             s, err = compile_unit(unit, tmp)
             rem, fi = kernel_remarks(err), function_info(s)
             dm = demangle(list(fi) + list(rem))
             lines.append(f"== {unit}")
             lines.append(f"  {'kernel':<62} {'VGPR':>5} {'AGPR':>5} {'spillV':>6} {'spillS':>6} {'scratch B/lane':>14} {'LDS B':>6} {'waves/SIMD':>10}")
-            solve = [(k, v) for k, v in rem.items() if "solve_kernel" in dm.get(k, k) or "resume_kernel" in dm.get(k, k)]
+            solve = [(k, v) for k, v in rem.items() if every or "solve_kernel" in dm.get(k, k) or "resume_kernel" in dm.get(k, k)]
             solve.sort(key=lambda kv: (not any(b in dm[kv[0]] for b in BENCH), dm[kv[0]]))
             for k, v in solve:
-                name = re.sub(r"\(tsat::KArgs<\w+>\)|void ", "", dm[k])
+                name = re.sub(r"\(tsat::KArgs<\w+>\)|void ", "", dm[k]) if not every else re.sub(r"\(.*\)|void ", "", dm[k])
                 lines.append(f"  {name:<62} {v.get('VGPRs', '?'):>5} {v.get('AGPRs', '?'):>5} {v.get('VGPRs Spill', '?'):>6} {v.get('SGPRs Spill', '?'):>6} "
                              f"{v.get('ScratchSize [bytes/lane]', '?'):>14} {v.get('LDS Size [bytes/block]', '?'):>6} {v.get('Occupancy [waves/SIMD]', '?'):>10}")
             lines.append(f"  {'function (bench variant rk3 / isotropic / hooks on, then the largest scratch user of each name)':<100} {'VGPR':>5} {'AGPR':>5} {'scratch B':>9} {'scratch insts':>13} {'insts':>6}")

@@ -27,6 +27,10 @@
 // tsat_tvlqr_ensemble_sensed and tsat_pd_ensemble_sensed (tsat_sensed.hpp) are run_ensemble and run_pd with a `Sensing`: the host
 // validates the sensor options and biases (check_sensor), a pack kernel lays the biases out per lane, and step 4 launches a kernel
 // of tsat_kernels_sensed.hip. The TVLQR one also takes the model's plant for a NULL plant and no gravity rows for a NULL Rtab.
+//
+// tsat_tvlqr_ensemble_filtered and tsat_pd_ensemble_filtered (tsat_filtered.hpp) are the sensed calls with a `Filtering`: the host
+// validates the filter options (check_filter), zero-fills X_hat when asked for, and step 4 launches a kernel of
+// tsat_kernels_filtered.hip. f == NULL is dispatched to the sensed call itself.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -39,6 +43,7 @@
 #include "tsat_gg.hpp"
 #include "tsat_pd.hpp"
 #include "tsat_sensed.hpp"
+#include "tsat_filtered.hpp"
 
 using namespace tsat;
 
@@ -54,6 +59,9 @@ int tsat_handle_device(const tsat_handle* h);
 hipError_t tsat_launch_sensed_pack(const double* sensor, double* SN, int64_t T, int M, int Mp, hipStream_t stream);
 hipError_t tsat_launch_sensed_tv(const SensedTvArgs<double>& a, int waves, hipStream_t stream);
 hipError_t tsat_launch_sensed_pd(const SensedPdArgs<double>& a, int waves, hipStream_t stream);
+// roll-outs of the filtered calls (tsat_kernels_filtered.hip)
+hipError_t tsat_launch_filtered_tv(const FilteredTvArgs<double>& a, int waves, hipStream_t stream);
+hipError_t tsat_launch_filtered_pd(const FilteredPdArgs<double>& a, int waves, hipStream_t stream);
 
 template <typename real, int DIAGJ>
 __global__ __launch_bounds__(64) void tsat_ensemble_kernel(EnsArgs<real> a) {
@@ -150,6 +158,12 @@ struct Sensing {
   const double* sensor;
 };
 
+// ... and the filtered calls to the sensed ones
+struct Filtering {
+  const tsat_filter_options* f;
+  double *X_hat, *filt_final;
+};
+
 // every realisation flies the model's plant: (Jmat, G = I, m_res = 0); the pack reads the upper triangle of Jp
 std::vector<double> model_plants(const double* Jmat, size_t Tn, int M) {
   std::vector<double> model(Tn * (size_t)M * TSAT_PLANT_W, 0.0);
@@ -170,6 +184,22 @@ SensArgs<double> sens_args(const Sensing& sn, const tsat_tvlqr_options* o, const
   return a;
 }
 
+// the launch block of the filter around that of its sensor
+FiltArgs<double> filt_args(const Filtering& fl, const SensArgs<double>& sa, const EnsArgs<double>& e, double* dXH, double* dFF) {
+  FiltArgs<double> a;
+  a.s = sa; a.P = e.P; a.nk = e.nk; a.M = e.M; a.N = e.N;
+  a.sv = fl.f->sigma_v; a.su = fl.f->sigma_u; a.sa = fl.f->sigma_a; a.p0a = fl.f->p0_att; a.p0b = fl.f->p0_bias;
+  a.XH = dXH; a.FF = dFF;
+  return a;
+}
+
+// f == NULL is the sensed parent, which has no X_hat and no filt_final to fill
+bool unfiltered_outputs(const double* X_hat, const double* filt_final) {
+  if (!X_hat && !filt_final) return false;
+  g_err = "f is NULL (the sensed call): X_hat and filt_final must be NULL";
+  return true;
+}
+
 std::string at_tm(int64_t t, int m) { return " at (t, m) = (" + std::to_string(t) + ", " + std::to_string(m) + ")"; }
 
 // the host only validates the plants: "" or the reason, with the offending (t, m)
@@ -186,13 +216,14 @@ std::string check_dispersion(const Dispersion& d, int64_t T, int M) {
 }
 
 // all entry points: `disp` == nullptr is tsat_tvlqr_ensemble, `grav` != nullptr (with `disp`) tsat_tvlqr_ensemble_gg, `sens` != nullptr
-// (with both) tsat_tvlqr_ensemble_sensed
+// (with both) tsat_tvlqr_ensemble_sensed, `filt` != nullptr (with all three) tsat_tvlqr_ensemble_filtered
 int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
                  const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
                  const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
                  const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
                  tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr,
-                 double* X_sim, const Dispersion* disp, const Gravity* grav = nullptr, const Sensing* sens = nullptr) {
+                 double* X_sim, const Dispersion* disp, const Gravity* grav = nullptr, const Sensing* sens = nullptr,
+                 const Filtering* filt = nullptr) {
   g_err.clear();
   if (!h || !o) return efail(-1, "null handle or options");
   const std::string why = check_tv_options(*o);
@@ -228,6 +259,10 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   }
   if (sens) {
     const std::string bad = check_sensor(sens->s, sens->sensor, T, M);
+    if (!bad.empty()) return efail(-1, bad);
+  }
+  if (filt) {
+    const std::string bad = check_filter(filt->f);
     if (!bad.empty()) return efail(-1, bad);
   }
   // ---- 1. the handle: the library's own checks on slew 0 cut to two knots; its GPU becomes the thread's current device ----
@@ -273,6 +308,10 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   // the sensed call: raw biases (when given) and the per-lane records
   double *dSens = nullptr, *dSN = nullptr;
   if (ok && sens) ok = s.alloc(&dSN, Tn * SNW * (size_t)Mp) && (!sens->sensor || s.alloc(&dSens, nS * SNW));
+  // the filtered call: what the law saw and the filter's last state, when asked for
+  double *dXH = nullptr, *dFF = nullptr;
+  if (ok && filt && filt->X_hat) ok = s.alloc(&dXH, nS * N * 7);
+  if (ok && filt && filt->filt_final) ok = s.alloc(&dFF, nS * FFW);
   if (!ok) return efail(-10, std::string("device allocation failed in ") + name);
 #define ENS_HIP(call)                                                                                   \
   do {                                                                                                  \
@@ -317,6 +356,7 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
     if (sens->sensor) ENS_HIP(hipMemcpy(dSens, sens->sensor, nS * SNW * 8, hipMemcpyHostToDevice));
     ENS_HIP(tsat_launch_sensed_pack(dSens, dSN, T, M, Mp, s.stream));
   }
+  if (dXH) ENS_HIP(hipMemsetAsync(dXH, 0, nS * N * 7 * 8, s.stream));   // the last row of every horizon and all beyond it stay zero
   ENS_HIP(hipEventRecord(s.ev[0], s.stream));
   {
     auto kern = cls == 2 ? tsat_ensemble_gains_kernel<double, 2>
@@ -336,7 +376,12 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
     if (disp) {
       DispArgs<double> d;
       d.e = a; d.PL = dPL; d.Mp = Mp; d.SAT = dSat; d.nclip = dClip;
-      if (sens) {
+      if (filt) {
+        FilteredTvArgs<double> fa;
+        fa.g.d = d; fa.g.GT = dGT;
+        fa.f = filt_args(*filt, sens_args(*sens, o, dSN, Mp), a, dXH, dFF);
+        ENS_HIP(tsat_launch_filtered_tv(fa, nw, s.stream));
+      } else if (sens) {
         SensedTvArgs<double> sa;
         sa.g.d = d; sa.g.GT = dGT;
         sa.s = sens_args(*sens, o, dSN, Mp);
@@ -367,6 +412,8 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   if (K_lqr) ENS_HIP(hipMemcpy(K_lqr, dK, Tn * (size_t)(N - 1) * 18 * 8, hipMemcpyDeviceToHost));
   if (X_sim) ENS_HIP(hipMemcpy(X_sim, dXS, nXS * 8, hipMemcpyDeviceToHost));
   if (dClip) ENS_HIP(hipMemcpy(disp->n_clipped, dClip, nS * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (dXH) ENS_HIP(hipMemcpy(filt->X_hat, dXH, nS * N * 7 * 8, hipMemcpyDeviceToHost));
+  if (dFF) ENS_HIP(hipMemcpy(filt->filt_final, dFF, nS * FFW * 8, hipMemcpyDeviceToHost));
   ensemble_summary(T, M, stats, summary);
   if (const char* v = std::getenv("TSAT_ENSEMBLE_TIMING")) {   // diagnostic (tools/ensemble_timing.py): HIP-event times of the two kernels
     if (v[0] == '1') {
@@ -387,13 +434,13 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
 }
 
 // tsat_pd_ensemble: steps 2, 4 and 5 of run_ensemble around the kernels of tsat_kernels_pd.hip; `sens` != nullptr is
-// tsat_pd_ensemble_sensed
+// tsat_pd_ensemble_sensed, `filt` != nullptr (with it) tsat_pd_ensemble_filtered
 int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X, const double* U,
            const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau, const double* dt,
            const double* Jmat, const double* kd, const double* kp, int32_t feedforward, int32_t limit_mode, const double* x0_sim,
            const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots, const double* plant, const double* sat_lo,
            const double* sat_hi, tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* X_sim,
-           int32_t* n_clipped, const double* Rtab, double gm, const Sensing* sens = nullptr) {
+           int32_t* n_clipped, const double* Rtab, double gm, const Sensing* sens = nullptr, const Filtering* filt = nullptr) {
   g_err.clear();
   if (!h) return efail(-1, "null handle or options");
   const std::string why = check_pd(o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode,
@@ -401,6 +448,10 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
   if (!why.empty()) return efail(-1, why);
   if (sens) {
     const std::string bad = check_sensor(sens->s, sens->sensor, T, M);
+    if (!bad.empty()) return efail(-1, bad);
+  }
+  if (filt) {
+    const std::string bad = check_filter(filt->f);
     if (!bad.empty()) return efail(-1, bad);
   }
 #define ENS_HIP(call)                                                                                   \
@@ -448,6 +499,10 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
   if (ok && Rtab) ok = s.alloc(&dR, nB * 3) && (dGT = tsat_ws_gravity(h, nB * 4 * 8)) != nullptr;
   double *dSens = nullptr, *dSN = nullptr;
   if (ok && sens) ok = s.alloc(&dSN, Tn * SNW * (size_t)Mp) && (!sens->sensor || s.alloc(&dSens, nS * SNW));
+  // the filtered call: what the law saw and the filter's last state, when asked for
+  double *dXH = nullptr, *dFF = nullptr;
+  if (ok && filt && filt->X_hat) ok = s.alloc(&dXH, nS * N * 7);
+  if (ok && filt && filt->filt_final) ok = s.alloc(&dFF, nS * FFW);
   if (!ok) return efail(-10, "device allocation failed in tsat_pd_ensemble");
   ENS_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
   for (hipEvent_t& e : s.ev) ENS_HIP(hipEventCreate(&e));
@@ -485,6 +540,7 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
     if (sens->sensor) ENS_HIP(hipMemcpy(dSens, sens->sensor, nS * SNW * 8, hipMemcpyHostToDevice));
     ENS_HIP(tsat_launch_sensed_pack(dSens, dSN, T, M, Mp, s.stream));
   }
+  if (dXH) ENS_HIP(hipMemsetAsync(dXH, 0, nS * N * 7 * 8, s.stream));   // the last row of every horizon and all beyond it stay zero
   // ---- 4. the roll-out ------------------------------------------------------------------------------------------------
   ENS_HIP(hipEventRecord(s.ev[0], s.stream));
   {
@@ -497,7 +553,12 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
     a.XS = dXS; a.stats = dst; a.stats_nom = dsn;
     pa.d.PL = dPL; pa.d.Mp = Mp; pa.d.SAT = dSat; pa.d.nclip = dClip;
     pa.GT = dGT; pa.GAIN = dGain; pa.X0N = dX0N; pa.feedforward = feedforward; pa.limit_mode = limit_mode;
-    if (sens) {
+    if (filt) {
+      FilteredPdArgs<double> fa;
+      fa.p = pa;
+      fa.f = filt_args(*filt, sens_args(*sens, o, dSN, Mp), a, dXH, dFF);
+      ENS_HIP(tsat_launch_filtered_pd(fa, nw, s.stream));
+    } else if (sens) {
       SensedPdArgs<double> sa;
       sa.p = pa;
       sa.s = sens_args(*sens, o, dSN, Mp);
@@ -513,12 +574,14 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
   if (stats_nominal) ENS_HIP(hipMemcpy(stats_nominal, dsn, Tn * sizeof(tsat_tvlqr_stats), hipMemcpyDeviceToHost));
   if (X_sim) ENS_HIP(hipMemcpy(X_sim, dXS, nXS * 8, hipMemcpyDeviceToHost));
   if (dClip) ENS_HIP(hipMemcpy(n_clipped, dClip, nS * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (dXH) ENS_HIP(hipMemcpy(filt->X_hat, dXH, nS * N * 7 * 8, hipMemcpyDeviceToHost));
+  if (dFF) ENS_HIP(hipMemcpy(filt->filt_final, dFF, nS * FFW * 8, hipMemcpyDeviceToHost));
   ensemble_summary(T, M, stats, summary);
   if (const char* v = std::getenv("TSAT_ENSEMBLE_TIMING")) {   // diagnostic (tools/pd_timing.py): HIP-event time of the roll-out
     if (v[0] == '1') {
       float e = 0;
       (void)hipEventElapsedTime(&e, s.ev[0], s.ev[1]);
-      std::fprintf(stderr, "%s: pd_kernel_ms %.4f\n", sens ? "tsat_pd_ensemble_sensed" : "tsat_pd_ensemble", e);
+      std::fprintf(stderr, "%s: pd_kernel_ms %.4f\n", filt ? "tsat_pd_ensemble_filtered" : (sens ? "tsat_pd_ensemble_sensed" : "tsat_pd_ensemble"), e);
     }
   }
 #undef ENS_HIP
@@ -549,6 +612,30 @@ int tsat_pd_ensemble_sensed(tsat_handle* h, const tsat_tvlqr_options* o, int64_t
   const Sensing se{sn, sensor};
   return run_pd(h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode, x0_sim, x0_nom,
                 noise_id0, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, X_sim, n_clipped, Rtab, gm, &se);
+}
+
+int tsat_pd_ensemble_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                              const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                              const double* dtau, const double* dt, const double* Jmat, const double* kd, const double* kp,
+                              int32_t feedforward, int32_t limit_mode, const double* x0_sim, const double* x0_nom, const int64_t* noise_id0,
+                              const int32_t* n_knots, const double* plant, const double* sat_lo, const double* sat_hi,
+                              tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* X_sim, int32_t* n_clipped,
+                              const double* Rtab, double gm, const tsat_sensor_options* sn, const double* sensor,
+                              const tsat_filter_options* f, double* X_hat, double* filt_final) {
+  if (!f && unfiltered_outputs(X_hat, filt_final)) return -1;
+  const Sensing se{sn, sensor};
+  const Filtering fl{f, X_hat, filt_final};
+  return run_pd(h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode, x0_sim, x0_nom,
+                noise_id0, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, X_sim, n_clipped, Rtab, gm, &se,
+                f ? &fl : nullptr);
+}
+
+void tsat_filter_default_options(tsat_filter_options* f) {
+  if (!f) return;
+  const double pi = 3.14159265358979323846;
+  f->sigma_v = 0.38 * pi / 180.0; f->sigma_u = 0.0; f->sigma_a = pi / 180.0;   // the levels examples/sensed_slew.py flies
+  f->p0_att = pi / 180.0; f->p0_bias = 0.0;
+  f->reserved = 0;
 }
 
 void tsat_sensor_default_options(tsat_sensor_options* s) {
@@ -606,6 +693,24 @@ int tsat_tvlqr_ensemble_sensed(tsat_handle* h, const tsat_tvlqr_options* o, int6
   const Sensing se{sn, sensor};
   return run_ensemble("tsat_tvlqr_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, Qd, Qfd, Rd,
                       x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, K_lqr, X_sim, &d, &g, &se);
+}
+
+int tsat_tvlqr_ensemble_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                                 const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                                 const double* dtau, const double* dt, const double* Jmat, const double* Qd, const double* Qfd,
+                                 const double* Rd, const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                                 const double* plant, const double* sat_lo, const double* sat_hi, tsat_tvlqr_stats* stats,
+                                 double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr, double* X_sim, int32_t* n_clipped,
+                                 const double* Rtab, double gm, const tsat_sensor_options* sn, const double* sensor,
+                                 const tsat_filter_options* f, double* X_hat, double* filt_final) {
+  if (!f && unfiltered_outputs(X_hat, filt_final)) return -1;
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  const Sensing se{sn, sensor};
+  const Filtering fl{f, X_hat, filt_final};
+  return run_ensemble(f ? "tsat_tvlqr_ensemble_filtered" : "tsat_tvlqr_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0,
+                      dtau, dt, Jmat, Qd, Qfd, Rd, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, K_lqr, X_sim, &d, &g, &se,
+                      f ? &fl : nullptr);
 }
 
 }  // extern "C"

@@ -372,8 +372,9 @@ def attitude_ensemble_pd(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X
 
 
 def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0, want_trajectories,
-             sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=None):
-    """``tsat_pd_ensemble``, or with ``sensing`` = (SensorOptions, sensor array or None) ``tsat_pd_ensemble_sensed``"""
+             sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=None, filtering=None):
+    """``tsat_pd_ensemble``, or with ``sensing`` = (SensorOptions, sensor array or None) ``tsat_pd_ensemble_sensed``, or with
+    ``filtering`` = (FilterOptions, X_hat or None, filt_final or None) besides ``tsat_pd_ensemble_filtered``"""
     lib = _abi.load()
     T, N = batch.T, batch.N
     c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
@@ -420,6 +421,9 @@ def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, s
             _abi.as_ip(ncl), d(Rtab), float(gm))
     if sensing is None:
         name, rc = "tsat_pd_ensemble", lib.tsat_pd_ensemble(*args)
+    elif filtering is not None:
+        name, rc = "tsat_pd_ensemble_filtered", lib.tsat_pd_ensemble_filtered(*args, C.byref(sensing[0]), d(sensing[1]),
+                                                                             C.byref(filtering[0]), d(filtering[1]), d(filtering[2]))
     else:
         name, rc = "tsat_pd_ensemble_sensed", lib.tsat_pd_ensemble_sensed(*args, C.byref(sensing[0]), d(sensing[1]))
     if rc != 0:
@@ -505,3 +509,83 @@ def attitude_ensemble_pd_sensed(solver, batch: SlewBatch, x0_sim, kd, kp, noise_
     sensing = _sensing(batch.T, x0.shape[1], sensor, sigma_gyro, sigma_att, sigma_mag, latency)
     return _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
                     want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing)
+
+
+FILTER_W = 9
+
+
+def filter_options(sigma_v, sigma_a, sigma_u=0.0, p0_att=None, p0_bias=0.0):
+    """The ``tsat_filter_options`` of the filtered ensembles: what the multiplicative EKF assumes, all standard deviations — gyro
+    white noise ``sigma_v`` (rad/s), attitude measurement noise ``sigma_a`` (rad, > 0), bias random walk per knot ``sigma_u``
+    (rad/s), initial attitude ``p0_att`` (rad; None: ``sigma_a``) and initial bias ``p0_bias`` (rad/s). ``p0_bias`` = ``sigma_u`` = 0
+    estimates no bias at all."""
+    fo = _abi.FilterOptions()
+    _abi.load().tsat_filter_default_options(C.byref(fo))
+    fo.sigma_v, fo.sigma_a, fo.sigma_u = float(sigma_v), float(sigma_a), float(sigma_u)
+    fo.p0_att, fo.p0_bias = float(sigma_a if p0_att is None else p0_att), float(p0_bias)
+    if min(fo.sigma_v, fo.sigma_u, fo.p0_att, fo.p0_bias) < 0.0 or not fo.sigma_a > 0.0:
+        raise ValueError("filter levels must not be negative, and sigma_a must be positive")
+    return fo
+
+
+def _filtering(T, M, N, filter, want_estimates):
+    """(FilterOptions, X_hat (T, M, N, 7) or None, filt_final (T, M, 9)) of a filtered call; ``filter`` None: the default options"""
+    if filter is None:
+        filter = _abi.FilterOptions()
+        _abi.load().tsat_filter_default_options(C.byref(filter))
+    if not isinstance(filter, _abi.FilterOptions):
+        raise ValueError("filter must come from filter_options()")
+    return filter, (np.empty((T, M, N, 7)) if want_estimates else None), np.empty((T, M, FILTER_W))
+
+
+def attitude_ensemble_filtered(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant=None, Rtab=None, gm=0.0, sat=None,
+                               sensor=None, sigma_gyro=0.0, sigma_att=0.0, sigma_mag=0.0, latency=0, noise_id0=None, sigma_scale=1.0,
+                               want_K=False, want_trajectories=False, linearize_dt_sq=True, u_scale=1e-2, min_steps=10, w_tol=0.05,
+                               angle_tol=0.08727, filter=None, want_estimates=False):
+    """``attitude_ensemble_sensed`` with a multiplicative EKF between the measurement and the TVLQR feedback
+    (``tsat_tvlqr_ensemble_filtered``): six states — attitude error and gyro bias —, propagated by the gyro, updated by the attitude
+    measurement; the recursion is in include/tortoise_hip.h. It removes attitude-sensor noise and estimates the gyro bias; it does
+    NOT smooth white gyro noise (the rate the law sees is w_m - b^). At ``latency`` 1 the law sees the estimate predicted across the
+    delay. ``filter`` from ``filter_options`` (None: the reference's figures, sigma_v = 0.38 deg/s, sigma_a = p0_att = 1 deg, no bias
+    state). Returns the dict of ``attitude_ensemble_sensed`` plus ``filt_final`` (T, M, 9) = [b^, sqrt(diag A), sqrt(diag D)] after
+    the last sample processed and ``X_hat`` (T, M, N, 7), what the law saw per knot (zero from the slew's last knot on), or None
+    without ``want_estimates``. ``nominal`` flies the ideal sensor through the same filter."""
+    lib, head, tail, out = _ensemble_call(solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, noise_id0, sigma_scale, want_K,
+                                          want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol)
+    T, M = out["stats"].shape
+    c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    plant = c(plant)
+    if plant is not None and plant.shape != (T, M, PLANT_W):
+        raise ValueError("plant must be (T, M, 21)")
+    if Rtab is not None:
+        Rtab = orbit_table(batch, Rtab)
+    lo = hi = None
+    if sat is not None:
+        lo, hi = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in sat)
+    so, sensor = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
+    fo, Xh, ff = _filtering(T, M, batch.N, filter, want_estimates)
+    ncl = np.zeros((T, M), dtype=np.int32)
+    d = _abi.as_dp
+    rc = lib.tsat_tvlqr_ensemble_filtered(*head, d(plant), d(lo), d(hi), *tail, _abi.as_ip(ncl), d(Rtab), float(gm), C.byref(so), d(sensor),
+                                          C.byref(fo), d(Xh), d(ff))
+    if rc != 0:
+        raise RuntimeError(f"tsat_tvlqr_ensemble_filtered failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
+    return dict(out, n_clipped=ncl, X_hat=Xh, filt_final=ff)
+
+
+def attitude_ensemble_pd_filtered(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X=None, U=None, plant=None, Rtab=None, gm=0.0,
+                                  sat=None, limit_mode=0, x0_nom=None, sensor=None, sigma_gyro=0.0, sigma_att=0.0, sigma_mag=0.0,
+                                  latency=0, noise_id0=None, want_trajectories=False, sigma_scale=1.0, u_scale=1e-2, min_steps=10,
+                                  w_tol=0.05, angle_tol=0.08727, filter=None, want_estimates=False):
+    """``attitude_ensemble_pd_sensed`` with the filter of ``attitude_ensemble_filtered`` between (w_m, q_m) and the law
+    (``tsat_pd_ensemble_filtered``); the magnetometer reading b_m is not filtered. Returns the dict of ``attitude_ensemble_pd_sensed``
+    plus ``X_hat`` and ``filt_final`` as there."""
+    x0 = np.asarray(x0_sim)
+    if x0.ndim != 3:
+        raise ValueError("x0_sim must be (T, M, 7)")
+    T, M = batch.T, x0.shape[1]
+    sensing = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
+    fo, Xh, ff = _filtering(T, M, batch.N, filter, want_estimates)
+    out = _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
+                   want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing, filtering=(fo, Xh, ff))
+    return dict(out, X_hat=Xh, filt_final=ff)
