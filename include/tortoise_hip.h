@@ -706,6 +706,38 @@ int  tsat_mpc_run_held_sensed(tsat_handle* h, const tsat_options* o, const tsat_
                        int32_t* n_clipped, float* solve_ms, const double* Rtab, double gm,
                        const tsat_sensor_options* s, const double* sensor, double* Y_hist);
 
+/* tsat_mpc_run_held_sensed BEHIND THE FILTER of tsat_tvlqr_ensemble_filtered: the loop above with one change — what the controller
+ * is handed. The raw measurements m_s are the parent's (stage-4 draws at knot step0 + s, biases from `sensor`, the first step of a
+ * call measures itself), and so are the blocks and the j = 0 rule, the clip, the dispersed RK4 step, the gravity rows (Rtab NULL
+ * iff gm == 0), the table clock, the shift, n_clipped, tsat_mpc_tally, the statistic on the TRUE state and the true state written
+ * back at the end of the call. The recursion written out at tsat_filter_options (`first`, `step` 1-6, the prediction across the
+ * delay, h = dt[t]) runs over the samples m_0, m_1, ..., one per control step; the solve's x0 at a block start, the state
+ * U_j + K_j dx acts on, and Y_hist[s] all read the filter's y_s. s is the step RELATIVE TO THE CALL, whatever step0 is:
+ *   latency 0: the filter is at sample s, y_s = (w^_s, q^_s)
+ *   latency 1: y_0 = (w^_0, q^_0); at s = 1 the sensor hands m_0 over a second time, which makes no filter step; for s >= 1 the
+ *              filter is at sample s - 1 and y_s = (w^_{s-1}, q^_{s-1} (x) dq(h w^_{s-1})), predicted across the delay
+ * State between calls: one flat record of TSAT_FILTER_STATE_W = 31 values per trajectory, q^ 4, b^ 3, w^ 3, then A 6, B 9, D 6
+ * (A and D as upper triangles 00 01 02 11 12 22, B row-major).
+ *   filt_init   31 x T or NULL   NULL: the filter starts on the call's m_0 (`first`) and so restarts with every call, as the
+ *                                latency memory does. Given: the record of trajectory t is loaded before the first sample, and m_0
+ *                                makes a `step` instead of `first`; nothing else differs
+ *   filt_state  31 x T out or NULL   the record after the last sample processed
+ *   filt_final  9 x T out or NULL    b^, sqrt(diag A), sqrt(diag D) of that record (the layout of the ensembles' filt_final)
+ * At latency 0 a continuation equals one longer run when step0 = the steps made, there is no upload, filt_init = the previous
+ * call's filt_state, and the first call's n_steps is a multiple of R. Latency 1 STILL RESTARTS THE SENSOR'S MEMORY with every call
+ * (the first step of the second call sees its own measurement), filt_init or not: such a continuation is not the longer run.
+ * f == NULL is tsat_mpc_run_held_sensed, byte for byte (it is dispatched there); the three filter arrays must then be NULL.
+ * Rejected with -1 (text in tsat_last_error; nothing is launched and no workspace grows): a non-finite or negative filter option,
+ * sigma_a == 0, reserved != 0; f NULL with a filter array non-NULL; a non-finite entry of filt_init; a q^ of zero norm in filt_init
+ * (reported with its t); and everything tsat_mpc_run_held_sensed rejects. */
+#define TSAT_FILTER_STATE_W 31
+int  tsat_mpc_run_held_filtered(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                       int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo, const double* sat_hi,
+                       const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
+                       int32_t* n_clipped, float* solve_ms, const double* Rtab, double gm,
+                       const tsat_sensor_options* s, const double* sensor, double* Y_hist,
+                       const tsat_filter_options* f, const double* filt_init, double* filt_state, double* filt_final);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Sweep exchange across GPUs. The reference's Monte-Carlo is a serial loop whose iterations share nothing but the result
  * lists they append to (src/monte_carlo.jl:52-66, 199-235; src/paper_images/heatmap.jl:114-243). Here each rank — one

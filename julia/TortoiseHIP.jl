@@ -626,8 +626,10 @@ end
 # it can. The Python layer binds them (tracking.attitude_ensemble_sensed, tracking.attitude_ensemble_pd_sensed,
 # mpc.receding_horizon_held_sensed). The filtered ensembles take that struct and a `tsat_filter_options*` besides (five Float64 —
 # sigma_v, sigma_u, sigma_a, p0_att, p0_bias —, then Int32 reserved: 48 bytes with the tail padding) and stay unbound for the same
-# reason (tracking.attitude_ensemble_filtered, tracking.attitude_ensemble_pd_filtered).
+# reason (tracking.attitude_ensemble_filtered, tracking.attitude_ensemble_pd_filtered), and so does the held re-planning loop behind
+# the filter, which takes both (mpc.receding_horizon_held_filtered).
 const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsat_pd_ensemble_sensed, :tsat_mpc_run_held_sensed,
-                 :tsat_filter_default_options, :tsat_tvlqr_ensemble_filtered, :tsat_pd_ensemble_filtered]
+                 :tsat_filter_default_options, :tsat_tvlqr_ensemble_filtered, :tsat_pd_ensemble_filtered,
+                 :tsat_mpc_run_held_filtered]
 
 end # module

@@ -15,7 +15,7 @@
 //
 // State of a lane: q^ (4, unit, scalar first), b^ (3), w^ (3) and the 6 x 6 covariance as blocks A (theta theta), B (theta b),
 // D (b b), A and D as upper triangles (00 01 02 11 12 22): 6 + 9 + 6 = 21 values, P symmetric by construction. One flat record of
-// FLW = 31 values (FilterState) with load / save, which the held re-planning loop will carry between launches.
+// FLW = 31 values (FilterState) with load / save, which the held re-planning loop carries between launches (tsat_mpc_filtered.hpp).
 //
 // h is the trajectory's dt from the parameter record (as ensemble_traj reads it), dq(.) the rotation-vector quaternion of
 // tsat_sensed.hpp including its th == 0 select, (x) the quaternion product in the operand order of Sensed::state.
@@ -243,15 +243,10 @@ struct Filtered {
       for (int j = 0; j < 3; ++j)
         st.B[3 * i + j] = Bm[3 * i + j] - (Wt[3 * i] * Kb[3 * j] + Wt[3 * i + 1] * Kb[3 * j + 1] + Wt[3 * i + 2] * Kb[3 * j + 2]);
   }
-  // y: the estimate the law sees at knot k
-  TSAT_DEV void state(long long gid, int k, bool noisy, const real x[7], real y[7]) {
-    real m[7];
-    in.state(gid, k, noisy, x, m);                             // m_k, or m_max(k-1, 0)
-    const int lat = f.s.latency;
-    if (k == 0) first(m);
-    else if (!(lat && k == 1)) step(m);
+  // y: the estimate as it stands, (w^, q^), or — `ahead` — with the attitude predicted across one step of delay
+  TSAT_DEV void estimate(bool ahead, real y[7]) const {
     for (int i = 0; i < 3; ++i) y[i] = st.w[i];
-    if (lat && k > 0) {                                        // predicted across the delay
+    if (ahead) {
       real phi[3], d[4], qp[4];
       for (int i = 0; i < 3; ++i) phi[i] = h * st.w[i];
       filt_dq<real>(phi, d);
@@ -260,6 +255,15 @@ struct Filtered {
     } else {
       for (int i = 0; i < 4; ++i) y[3 + i] = st.q[i];
     }
+  }
+  // y: the estimate the law sees at knot k
+  TSAT_DEV void state(long long gid, int k, bool noisy, const real x[7], real y[7]) {
+    real m[7];
+    in.state(gid, k, noisy, x, m);                             // m_k, or m_max(k-1, 0)
+    const int lat = f.s.latency;
+    if (k == 0) first(m);
+    else if (!(lat && k == 1)) step(m);
+    estimate(lat && k > 0, y);                                 // predicted across the delay
     if (xh)
       for (int i = 0; i < 7; ++i) xh[(size_t)k * 7 + i] = y[i];
     if (ff && k == nt - 2) {                                   // the last knot that commands

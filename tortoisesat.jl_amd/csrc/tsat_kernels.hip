@@ -18,6 +18,7 @@
 #include "tsat_mpc_held.hpp"
 #include "tsat_gg.hpp"
 #include "tsat_mpc_sensed.hpp"
+#include "tsat_mpc_filtered.hpp"
 
 using namespace tsat;
 
@@ -43,6 +44,10 @@ hipError_t tsat_launch_mpc_held_gg(const MpcHeldGgArgs<double>& a, int error_sta
 // (tsat_kernels_mpc_sensed.hip)
 hipError_t tsat_launch_mpc_sensed_pack(const MpcSensedArgs<double>& a, const double* sensor, hipStream_t stream);
 hipError_t tsat_launch_mpc_sensed(const MpcSensedArgs<double>& a, int error_state, hipStream_t stream);
+// the pack (that of the sensed loop, then the first estimate) and the hold commanding from the filter's estimate of
+// tsat_mpc_run_held_filtered (tsat_kernels_mpc_filtered.hip)
+hipError_t tsat_launch_mpc_filtered_pack(const MpcFilteredArgs<double>& a, const double* sensor, int given, hipStream_t stream);
+hipError_t tsat_launch_mpc_filtered(const MpcFilteredArgs<double>& a, int error_state, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -139,6 +144,7 @@ struct tsat_handle {
          WS_GG_GT,             // packed gravity rows of tsat_tvlqr_ensemble_gg / tsat_mpc_run_held_gg
          WS_MPCS_XT, WS_MPCS_SN, WS_MPCS_IN, WS_MPCS_Y,   // tsat_mpc_run_held_sensed: true state + last measurement [14][T], biases
                                // [9][T], the uploaded sensor array, Y_hist
+         WS_MPCF_FL,           // tsat_mpc_run_held_filtered: the filter's records [31][T]
          WS_COUNT };
   void* ws[WS_COUNT] = {};
   size_t ws_bytes[WS_COUNT] = {};
@@ -615,17 +621,24 @@ namespace {
 // the loop of tsat_mpc_run_dispersed (replan_every = 0: a solve and the one-wavefront-per-trajectory step kernel per control step)
 // and of tsat_mpc_run_held (replan_every >= 1: a solve, the lane-per-trajectory hold and the plan shift per block); with
 // `gravity` the hold is the one of tsat_mpc_run_held_gg (Rtab [n_btab][n_tab][3] of the resident batch, gm); with `sc` the hold of
-// tsat_mpc_run_held_sensed, which reads measurements (tsat_mpc_sensed.hpp) — through the gravity rows when `gravity`
+// tsat_mpc_run_held_sensed, which reads measurements (tsat_mpc_sensed.hpp) — through the gravity rows when `gravity`; with `fc`
+// besides, the hold of tsat_mpc_run_held_filtered, which reads the filter's estimates (tsat_mpc_filtered.hpp)
 struct SensedCall {
   const tsat_sensor_options* s;
   const double* sensor;      // 9 x T or null
   double* Y_hist;            // 7 x n_steps x T or null
 };
+struct FilteredCall {
+  const tsat_filter_options* f;
+  const double* filt_init;   // 31 x T or null
+  double* filt_state;        // 31 x T or null
+  double* filt_final;        // 9 x T or null
+};
 int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps,
                    int64_t step0, int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo,
                    const double* sat_hi, const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last,
                    tsat_tvlqr_stats* stats, int32_t* n_clipped, float* solve_ms, bool gravity = false, const double* Rtab = nullptr,
-                   double gm = 0.0, const SensedCall* sc = nullptr) {
+                   double gm = 0.0, const SensedCall* sc = nullptr, const FilteredCall* fc = nullptr) {
   if (!h || !o || !po) return -1;
   const bool held = replan_every != 0;
   if (!h->uploaded) return fail(h, -1, "tsat_batch_upload has not been called");
@@ -642,6 +655,10 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   if (sc) {
     const std::string bads = check_mpc_sensed(sc->s, sc->sensor, h->T, Rtab, gm);
     if (!bads.empty()) return fail(h, -1, bads);
+  }
+  if (fc) {
+    const std::string badf = check_mpc_filtered(fc->f, fc->filt_init, fc->filt_state, fc->filt_final, h->T);
+    if (!badf.empty()) return fail(h, -1, badf);
   }
   if (!X_hist || !U_hist) return fail(h, -1, "null array");
   TSAT_HIP(h, hipSetDevice(h->dev));
@@ -674,6 +691,8 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
     dY = (double*)ws_get(h, tsat_handle::WS_MPCS_Y, nU / 3 * 7 * 8);
     if (!dXT || !dSN || (sc->sensor && !dSIn) || !dY) return fail(h, -10, std::string("device allocation failed in ") + name);
   }
+  double* dFL = fc ? (double*)ws_get(h, tsat_handle::WS_MPCF_FL, T * FLW * 8) : nullptr;
+  if (fc && !dFL) return fail(h, -10, std::string("device allocation failed in ") + name);
   // the gravity call: the packed rows are the handle's, the raw orbit table lives until the pack has run
   double* dGT = gravity ? tsat_ws_gravity(h, n_rows * 4 * 8) : nullptr;
   struct Raw {
@@ -690,6 +709,11 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   if (noise_id) TSAT_HIP(h, hipMemcpy(dNid, noise_id, T * sizeof(long long), hipMemcpyHostToDevice));
   if (gravity) TSAT_HIP(h, hipMemcpy(dR.p, Rtab, n_rows * 3 * 8, hipMemcpyHostToDevice));
   if (dSIn) TSAT_HIP(h, hipMemcpy(dSIn, sc->sensor, T * SNW * 8, hipMemcpyHostToDevice));
+  std::vector<double> flh(fc ? T * FLW : 0);   // the filter's records, component-major as the device holds them
+  if (fc && fc->filt_init) {
+    filt_records_pack(fc->filt_init, flh.data(), (int64_t)T);
+    TSAT_HIP(h, hipMemcpy(dFL, flh.data(), flh.size() * 8, hipMemcpyHostToDevice));
+  }
   TSAT_HIP(h, hipMemsetAsync(dTally, 0, T * 4 * sizeof(long long), h->stream));
   h->mpc_tally_T = (int64_t)T;
   const KArgs<double> a = solve_args(h, o);
@@ -714,6 +738,12 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
     ms.s.SN = dSN; ms.s.Mp = (int)T; ms.s.sgy = sc->s->sigma_gyro; ms.s.sat = sc->s->sigma_att; ms.s.smg = sc->s->sigma_mag;
     ms.s.latency = sc->s->latency; ms.s.k0 = e.k0; ms.s.k1 = e.k1;
   }
+  MpcFilteredArgs<double> mf = {};
+  if (fc) {
+    mf.FL = dFL;
+    mf.f.s = ms.s; mf.f.P = h->P; mf.f.nk = m.nk; mf.f.M = 1; mf.f.N = h->N;
+    mf.f.sv = fc->f->sigma_v; mf.f.su = fc->f->sigma_u; mf.f.sa = fc->f->sigma_a; mf.f.p0a = fc->f->p0_att; mf.f.p0b = fc->f->p0_bias;
+  }
   int rc = 0;
   if (hipEventRecord(h->ev0, h->stream) != hipSuccess) rc = -10;
   if (held) {   // the pack, then solve, hold and shift per block queued back to back; the stream orders them
@@ -721,13 +751,21 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
     if (!rc && gravity && tsat_launch_gg_pack(dR.p, gm, dGT, (int64_t)n_rows, h->stream) != hipSuccess) rc = -10;
     if (sc) {   // biases, the true state to its own record, the first measurement into the record the solve reads
       ms.h = mh;
-      if (!rc && tsat_launch_mpc_sensed_pack(ms, dSIn, h->stream) != hipSuccess) rc = -10;
+      if (fc) {
+        mf.ms = ms;
+        if (!rc && tsat_launch_mpc_filtered_pack(mf, dSIn, fc->filt_init != nullptr, h->stream) != hipSuccess) rc = -10;
+      } else {
+        if (!rc && tsat_launch_mpc_sensed_pack(ms, dSIn, h->stream) != hipSuccess) rc = -10;
+      }
     }
     for (int s = 0; s < n_steps && !rc; s += replan_every) {
       if (launch_solve(h, o, a) != hipSuccess) rc = -10;
       m.step = s;
       mh.r = std::min<int>(replan_every, n_steps - s);
-      if (sc) {        // the hold on measurements (with or without the gravity rows)
+      if (fc) {        // the hold on the filter's estimates (with or without the gravity rows)
+        ms.h = mh; mf.ms = ms;
+        if (!rc && tsat_launch_mpc_filtered(mf, o->error_state, h->stream) != hipSuccess) rc = -10;
+      } else if (sc) {        // the hold on measurements (with or without the gravity rows)
         ms.h = mh;
         if (!rc && tsat_launch_mpc_sensed(ms, o->error_state, h->stream) != hipSuccess) rc = -10;
       } else if (gravity) {   // the hold through the gravity rows
@@ -750,6 +788,10 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   if (stats) TSAT_HIP(h, hipMemcpy(stats, dSt, T * sizeof(tsat_tvlqr_stats), hipMemcpyDeviceToHost));
   if (n_clipped) TSAT_HIP(h, hipMemcpy(n_clipped, dClip, T * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (sc && sc->Y_hist) TSAT_HIP(h, hipMemcpy(sc->Y_hist, dY, nU / 3 * 7 * 8, hipMemcpyDeviceToHost));
+  if (fc && (fc->filt_state || fc->filt_final)) {
+    TSAT_HIP(h, hipMemcpy(flh.data(), dFL, flh.size() * 8, hipMemcpyDeviceToHost));
+    filt_records_unpack(flh.data(), (int64_t)T, fc->filt_state, fc->filt_final);
+  }
   return 0;
 }
 }  // namespace
@@ -789,6 +831,25 @@ int tsat_mpc_run_held_sensed(tsat_handle* h, const tsat_options* o, const tsat_t
   const SensedCall sc = {s, sensor, Y_hist};
   return mpc_plant_loop(h, "tsat_mpc_run_held_sensed", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id,
                         X_hist, U_hist, stats_last, stats, n_clipped, solve_ms, Rtab != nullptr, Rtab, gm, &sc);
+}
+
+int tsat_mpc_run_held_filtered(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                               int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo, const double* sat_hi,
+                               const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
+                               int32_t* n_clipped, float* solve_ms, const double* Rtab, double gm, const tsat_sensor_options* s,
+                               const double* sensor, double* Y_hist, const tsat_filter_options* f, const double* filt_init,
+                               double* filt_state, double* filt_final) {
+  if (!f) {   // the sensed call itself
+    const std::string bad = check_mpc_filtered(f, filt_init, filt_state, filt_final, 0);
+    if (!bad.empty()) return fail(h, -1, bad);
+    return tsat_mpc_run_held_sensed(h, o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id, X_hist, U_hist,
+                                    stats_last, stats, n_clipped, solve_ms, Rtab, gm, s, sensor, Y_hist);
+  }
+  if (replan_every < 1) return fail(h, -1, check_mpc_held(replan_every, feedback, 2));
+  const SensedCall sc = {s, sensor, Y_hist};
+  const FilteredCall fc = {f, filt_init, filt_state, filt_final};
+  return mpc_plant_loop(h, "tsat_mpc_run_held_filtered", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id,
+                        X_hist, U_hist, stats_last, stats, n_clipped, solve_ms, Rtab != nullptr, Rtab, gm, &sc, &fc);
 }
 
 int tsat_batch_export_device(tsat_handle* h, void* X_dev, void* U_dev, void* K_dev, void* stats_dev) {

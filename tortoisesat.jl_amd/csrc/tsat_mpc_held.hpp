@@ -15,7 +15,7 @@
 // forward sweeps' policy (mpc_held_state_diff, mpc_held_feedback below). The table clock advances by one rounded addition per step,
 // tau <- tau + dtau, and the rows of a step are those of brow_index at knot 0 of the current clock — the clock the every-step loop
 // has at that step. mpc_held_block is the one block of every held loop: what acts on the body is its Env (NoEnv; GgEnv of
-// tsat_gg.hpp), what the controller is fed its Feed (TrueFeed; SensedFeed of tsat_mpc_sensed.hpp).
+// tsat_gg.hpp), what the controller is fed its Feed (TrueFeed; SensedFeed of tsat_mpc_sensed.hpp; FilteredFeed of tsat_mpc_filtered.hpp).
 #pragma once
 #include "tsat_mpc_dispersed.hpp"
 

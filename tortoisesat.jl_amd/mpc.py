@@ -52,10 +52,11 @@ def _noise_options(lib, noise_opts):
 
 
 def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
-                gravity=None, sensed=None):
+                gravity=None, sensed=None, filtered=None):
     """``tsat_mpc_run_dispersed`` (``replan_every`` None), ``tsat_mpc_run_held``, — with ``gravity`` = (Rtab, gm) —
     ``tsat_mpc_run_held_gg`` or — with ``sensed`` = (SensorOptions, sensor (T, 9) or None) and ``gravity`` (Rtab may be None) —
-    ``tsat_mpc_run_held_sensed`` on ``prob``: marshalling of all four"""
+    ``tsat_mpc_run_held_sensed`` or — with ``filtered`` = (FilterOptions or None, filt_init (T, 31) or None) besides —
+    ``tsat_mpc_run_held_filtered`` on ``prob``: marshalling of all five"""
     lib = _abi.load()
     b = prob.arrays
     o = solver.opts.to_abi(b.N, b.n_tab, prob.integrator, prob.terminal_mask, error_state=prob.error_state)
@@ -97,9 +98,22 @@ def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise
             if sensor.shape != (T, 9):
                 raise ValueError("sensor must be (T, 9)")
         Yh = np.empty((T, n_steps, 7))
-        solver._check(lib.tsat_mpc_run_held_sensed(*head, int(replan_every), int(feedback), *tail, d(Rtab), float(gravity[1]), C.byref(so),
-                                                   d(sensor), d(Yh)), "tsat_mpc_run_held_sensed")
-        return dict(X_hist=Xh, U_hist=Uh, stats=st, tracking_stats=ts, n_clipped=ncl, ms=float(ms.value), Y_hist=Yh)
+        args = (*head, int(replan_every), int(feedback), *tail, d(Rtab), float(gravity[1]), C.byref(so), d(sensor), d(Yh))
+        res = dict(X_hist=Xh, U_hist=Uh, stats=st, tracking_stats=ts, n_clipped=ncl, Y_hist=Yh)
+        if filtered is None:
+            solver._check(lib.tsat_mpc_run_held_sensed(*args), "tsat_mpc_run_held_sensed")
+        else:
+            fo, init = filtered
+            if init is not None:
+                init = c(init)
+                if init.shape != (T, FILTER_STATE_W):
+                    raise ValueError("filt_init must be (T, 31)")
+            fs, ff = (None, None) if fo is None else (np.empty((T, FILTER_STATE_W)), np.empty((T, 9)))
+            solver._check(lib.tsat_mpc_run_held_filtered(*args, None if fo is None else C.byref(fo), d(init), d(fs), d(ff)),
+                          "tsat_mpc_run_held_filtered")
+            res.update(filt_state=fs, filt_final=ff)
+        res["ms"] = float(ms.value)
+        return res
     if gravity is not None:
         from .tracking import orbit_table
         Rtab = orbit_table(b, gravity[0])
@@ -152,6 +166,19 @@ def receding_horizon_held_gg(prob, solver, n_steps, replan_every, Rtab, gm=3.986
     return r
 
 
+def _sensor_options(sensor_opts, latency):
+    """``tsat_sensor_options`` of the loops fed measurements: None = the ideal sensor, a dict of the three sigmas, or a ready
+    ``_abi.SensorOptions``, whose latency then counts"""
+    if isinstance(sensor_opts, _abi.SensorOptions):
+        return _abi.SensorOptions.from_buffer_copy(sensor_opts)
+    kw = dict(sensor_opts or {})
+    unknown = set(kw) - {"sigma_gyro", "sigma_att", "sigma_mag"}
+    if unknown:
+        raise ValueError(f"unknown tsat_sensor_options field(s) {sorted(unknown)}")
+    return _abi.SensorOptions(sigma_gyro=kw.get("sigma_gyro", 0.0), sigma_att=kw.get("sigma_att", 0.0), sigma_mag=kw.get("sigma_mag", 0.0),
+                              latency=int(latency), reserved=0)
+
+
 def receding_horizon_held_sensed(prob, solver, n_steps, replan_every, sensor_opts=None, sensor=None, latency=0, Rtab=None, gm=0.0,
                                  feedback=True, plant=None, sat=None, noise_opts=None, noise_id=None, step0=0, max_outer=1, max_inner=3,
                                  upload=True):
@@ -164,17 +191,37 @@ def receding_horizon_held_sensed(prob, solver, n_steps, replan_every, sensor_opt
     magnetometer figures are accepted and unused: the loop has no law that reads the field. A continuation equals one longer run
     only with ``latency=0`` (and whole blocks): latency 1 restarts its memory with every call. Returns the dict of
     ``receding_horizon_held`` plus ``Y_hist`` (T, n_steps, 7), the measurement each step's command or solve used."""
-    if isinstance(sensor_opts, _abi.SensorOptions):
-        so = _abi.SensorOptions.from_buffer_copy(sensor_opts)
-    else:
-        kw = dict(sensor_opts or {})
-        unknown = set(kw) - {"sigma_gyro", "sigma_att", "sigma_mag"}
-        if unknown:
-            raise ValueError(f"unknown tsat_sensor_options field(s) {sorted(unknown)}")
-        so = _abi.SensorOptions(sigma_gyro=kw.get("sigma_gyro", 0.0), sigma_att=kw.get("sigma_att", 0.0), sigma_mag=kw.get("sigma_mag", 0.0),
-                                latency=int(latency), reserved=0)
+    so = _sensor_options(sensor_opts, latency)
     r = _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
                     gravity=(Rtab, gm), sensed=(so, sensor))
+    r["n_solves"] = -(-int(n_steps) // int(replan_every))
+    return r
+
+
+FILTER_STATE_W = 31     # TSAT_FILTER_STATE_W: q^ 4, b^ 3, w^ 3, A 6, B 9, D 6
+
+
+def receding_horizon_held_filtered(prob, solver, n_steps, replan_every, filter=None, filt_init=None, sensor_opts=None, sensor=None,
+                                   latency=0, Rtab=None, gm=0.0, feedback=True, plant=None, sat=None, noise_opts=None, noise_id=None,
+                                   step0=0, max_outer=1, max_inner=3, upload=True):
+    """``receding_horizon_held_sensed`` BEHIND THE FILTER of ``tracking.attitude_ensemble_filtered`` (``tsat_mpc_run_held_filtered``):
+    the multiplicative EKF runs over the raw measurements, one per control step, and the block solves' x0, the state the held steps'
+    gains act on and ``Y_hist`` are its estimate (at latency 1 predicted across the delay). ``filter``: a ``tracking.filter_options``
+    result, or a dict of that function's arguments; None passes f = NULL, which is ``receding_horizon_held_sensed`` itself
+    (``filt_state`` and ``filt_final`` are then None, and ``filt_init`` must be None). ``filt_init`` (T, 31): the filter records a
+    previous call returned as ``filt_state`` — sample 0 then makes a filter step instead of starting the filter; None starts it on
+    the call's first measurement. At latency 0 a continuation (``upload=False``, ``step0`` = the steps made, ``filt_init`` = the
+    previous ``filt_state``, whole blocks) equals one longer run; latency 1 still restarts the sensor's memory with every call.
+    Returns the dict of ``receding_horizon_held_sensed`` plus ``filt_state`` (T, 31: q^ 4, b^ 3, w^ 3, A 6, B 9, D 6) and
+    ``filt_final`` (T, 9: b^, sqrt diag A, sqrt diag D) after the last sample processed."""
+    if isinstance(filter, dict):
+        from .tracking import filter_options
+        filter = filter_options(**filter)
+    if filter is not None and not isinstance(filter, _abi.FilterOptions):
+        raise ValueError("filter must be None, a tracking.filter_options() result or a dict of its arguments")
+    so = _sensor_options(sensor_opts, latency)
+    r = _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
+                    gravity=(Rtab, gm), sensed=(so, sensor), filtered=(filter, filt_init))
     r["n_solves"] = -(-int(n_steps) // int(replan_every))
     return r
 
