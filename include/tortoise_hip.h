@@ -574,6 +574,83 @@ int  tsat_pd_ensemble_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int6
                          const tsat_sensor_options* s, const double* sensor,
                          const tsat_filter_options* f, double* X_hat, double* filt_final);
 
+/* A MODEL-BASED rate filter between sensor and law: the two sensed calls with a nine-state multiplicative EKF that uses what the
+ * flight software knows — the model inertia, the field table and the command it has just issued. It carries the body rate as a
+ * state and takes the gyro as a measurement of it, so (unlike the six-state filter above) it smooths white gyro noise, down to
+ * what sigma_w — the un-modelled angular acceleration it assumes — allows.
+ * Options (launch-uniform, all standard deviations):
+ *   sigma_v   attitude process noise (rad/s)                        sigma_w   un-modelled angular acceleration (rad/s^2)
+ *   sigma_u   bias random walk per knot (rad/s)                     sigma_a   attitude measurement noise it assumes (rad), > 0
+ *   sigma_g   gyro measurement noise it assumes (rad/s), > 0        p0_att    initial attitude standard deviation (rad)
+ *   p0_bias   initial bias standard deviation (rad/s)               reserved  0
+ * tsat_model_filter_default_options fills the reference's figures: sigma_g = 0.38 pi / 180, sigma_a = p0_att = pi / 180, the rest
+ * 0 — sigma_w included: no default for it can be derived, a caller has to choose it.
+ * State per realisation: q^ (4, unit, scalar first), w^ (3), b^ (3). Error state (dtheta, dw, db) in the body frame:
+ * q_true = q^ (x) dq(dtheta), dw = w - w^, db = b - b^. P is 9 x 9 symmetric with blocks theta, w, b, kept as its upper triangle
+ * (45 values). h, dq(.), (x), C(.) and the 3 x 3 inverse by cofactors with one reciprocal are those of the six-state filter.
+ *   first(m_0):  q^ = q_m / |q_m|, w^ = w_m, b^ = 0;  P_tt = p0_att^2 I, P_bb = p0_bias^2 I, P_ww = (sigma_g^2 + p0_bias^2) I,
+ *     P_wb = -p0_bias^2 I, P_tw = P_tb = 0 (the consistent start, since w - w_m = -(n + b)).
+ *   predict(u):  u is the command of the knot being crossed as the law issued it: after the limit rule, before the plant's actuator
+ *     matrix and residual dipole. Mean: (w-, q-) is one step from (w^, q^) of the plant's integrator on the MODEL — four stages
+ *     h dyn7(., u, b_c, J_model, u_scale) with the knot's field rows at c = 0, 1/2, 1/2, 1, combined as the roll-out combines them;
+ *     no noise, no disturbance torque, G = I, m_res = 0 (what the noise-free realisation of a dispersed call flies); q- is
+ *     normalised, b- = b^. Covariance: P- = Phi P Phi^T + Q with Phi_tt = C(h w^)^T, Phi_tw = h I,
+ *     Phi_ww = I + h J^-1 ([J w^]x - [w^]x J), Phi_bb = I, every other block 0 (the dependence of the magnetic torque on dtheta is
+ *     neglected in Phi and kept in the mean); Q = diag((sigma_v h)^2 I, (sigma_w h)^2 I, sigma_u^2 I).
+ *   update(m):  two 3-vector updates in this order, each applying its whole 9-vector delta = K z:
+ *     a. attitude  e = conj(q-) (x) q_m / |q_m|, z = 2 s e[1:4] with s = (e0 < 0 ? -1 : 1);  S = P_tt + sigma_a^2 I;
+ *                  K = P[:, theta] S^-1
+ *     b. gyro      z = w_m - (w^ + b^);  S = P_ww + P_wb + P_wb^T + P_bb + sigma_g^2 I;  K = (P[:, w] + P[:, b]) S^-1
+ *     both: q^ <- normalise(q^ (x) [1; dtheta / 2]), w^ += dw, b^ += db;  P <- P - K S K^T.
+ *   What the law sees at knot k, the measurement delivering m_k at latency 0 and m_max(k-1,0) at latency 1 — latency 0: k = 0
+ *   first; k >= 1 predict(u_{k-1}) with the rows of knot k - 1, then update(m_k); y_k = (w^, q^). Latency 1: y_0 from first(m_0);
+ *   k = 1: m_0 arrives a second time and makes no update, then predict(u_0); k >= 2: update(m_{k-1}) on the prior made at knot
+ *   k - 1, then predict(u_{k-1}); for k >= 1, y_k = (w-, q-): the model prediction across the delay, rate included.
+ * The PD law's magnetometer reading b_m is not filtered. stats_nominal flies the ideal sensor through the same filter. The
+ * gravity-gradient torque is not in the filter's model: it is un-modelled torque that sigma_w has to cover.
+ *   X_hat       7 x N x M x T or NULL   row k holds y_k for k < n_knots[t] - 1, the rest is zero (the layout of X_sim)
+ *   filt_final  12 x M x T or NULL      b^ (3), sqrt(diag P_tt) (3), sqrt(diag P_ww) (3), sqrt(diag P_bb) (3), taken directly after
+ *                                       the last update made up to and including the call at k = n_knots[t] - 2; the record of
+ *                                       first when none was made
+ * f == NULL is the sensed call, byte for byte (it is dispatched there); X_hat and filt_final must then be NULL.
+ * Rejected with -1 (text in tsat_ensemble_last_error; nothing is launched and no workspace grows): a non-finite or negative
+ * option; sigma_a == 0; sigma_g == 0; reserved != 0; f NULL with X_hat or filt_final non-NULL; and everything the sensed call
+ * rejects. */
+struct tsat_model_filter_options {
+  double  sigma_v;
+  double  sigma_w;
+  double  sigma_u;
+  double  sigma_a;
+  double  sigma_g;
+  double  p0_att;
+  double  p0_bias;
+  int32_t reserved;         /* 0 */
+};
+typedef struct tsat_model_filter_options tsat_model_filter_options;
+#define TSAT_MODEL_FILTER_W 12
+void tsat_model_filter_default_options(tsat_model_filter_options* f);
+int  tsat_tvlqr_ensemble_model_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                         const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* K_lqr, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor,
+                         const tsat_model_filter_options* f, double* X_hat, double* filt_final);
+int  tsat_pd_ensemble_model_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat,
+                         const double* kd, const double* kp, int32_t feedforward, int32_t limit_mode,
+                         const double* x0_sim, const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor,
+                         const tsat_model_filter_options* f, double* X_hat, double* filt_final);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Receding-horizon re-solve on the RESIDENT batch (BASELINE.json configs[4]). NOT in the reference —
  * it tracks its plan with TVLQR (src/attitude_controller.jl:1-48); defined here as: n_steps times

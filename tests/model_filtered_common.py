@@ -1,0 +1,466 @@
+"""Shared pieces of tests/test_model_filtered.py (CPU tier) and tests/test_gpu_model_filtered.py (GPU tier): the ensemble controllers
+behind the model-based rate filter (tsat_tvlqr_ensemble_model_filtered, tsat_pd_ensemble_model_filtered).
+
+THE REFERENCE (``loop``) is ``filtered_common.loop`` restated with the nine-state recursion of include/tortoise_hip.h (``ModelEkf``)
+in the place of the six-state one — numpy and the oracle's primitives only (``ol.qmult``, ``ol.inv3``, ``ol.dyn7``, ``ol.qrot``,
+``ol.plant_noise``). With ``filt=None`` it has to equal ``sensed_common.loop`` with max |d| = 0
+(test_model_filtered.py::test_reference_with_the_filter_off_is_the_sensed_reference); it also returns X_hat and filt_final.
+
+The case of both tiers is ``sensed_common``'s; the filter's levels are FILT below. Every parity test first asserts its conditions on
+references alone with the bar ``gg_common.MOVED`` (``conditions``): terms of the recursion are switched off through ``variant``, which
+is a device of the tests, not a mode of the product.
+
+Also: the argument lists of the two entry points and the ctypes binding of the emulated kernels
+(tests/emu/tsat_emu_model_filtered.cpp)."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+
+import dispersed_common as dc
+import ensemble_common as ec
+import filtered_common as fc
+import gg_common as gc
+import pd_common as pc
+import sensed_common as sc
+from conftest import ROOT
+
+FILTER_W = 12
+# the filter of the parity tests: the sensor's own attitude noise (sensed_common.SIGMAS), a gyro noise of 5e-3 rad/s as
+# filtered_common.FILT assumes (at the sensor's own 3e-4 rad/s the gyro update is so sharp that sigma_w hardly acts), a bias random
+# walk and an initial bias spread of the size of sensed_common.BIAS' gyro bias, an attitude process noise, and an un-modelled
+# angular acceleration of the size the dispersed plants of the case produce against the model (1e-4 .. 1e-3 rad/s^2), so that every
+# option acts
+FILT = dict(sigma_v=1e-3, sigma_w=3e-4, sigma_u=1e-4, sigma_a=sc.SIGMAS["sigma_att"], sigma_g=5e-3, p0_att=math.radians(1.0),
+            p0_bias=2e-3)
+FAST = fc.FAST
+# the sensor and filter on which the ORDER of the two updates shows. In a linear filter two updates with independent noises commute
+# exactly; here the order acts only through the second-order term of the quaternion correction, (dtheta_a x dtheta_b) / 2, which at
+# the parity levels (0.3 deg, 3e-4 rad/s) moves the final state by 1e-9 .. 4e-8 whatever the starts. At three times the reference's
+# own sensor figures (3 deg, 2e-2 rad/s) it moves it by 2e-7 .. 2e-6 under both laws and latencies.
+LOUD_SENS = dict(sigma_gyro=2e-2, sigma_att=math.radians(3.0), sigma_mag=5e-7)
+LOUD_FILT = dict(sigma_v=1e-3, sigma_w=3e-4, sigma_u=1e-4, sigma_a=math.radians(3.0), sigma_g=2e-2, p0_att=math.radians(3.0), p0_bias=2e-3)
+VARIANT = dict(command=True, gyroscopic=True, cross=True, order="ab", predict=True)
+
+
+def _skew(v):
+    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def _sym(P):
+    """the matrix the upper triangle of P stands for"""
+    return np.triu(P) + np.triu(P, 1).T
+
+
+class ModelEkf:
+    """the recursion of include/tortoise_hip.h, line for line; error state (dtheta, dw, db), P 9 x 9"""
+
+    def __init__(self, ol, h, J, us, filt, variant=VARIANT):
+        self.ol, self.h, self.J, self.us, self.f, self.v = ol, float(h), np.asarray(J, dtype=np.float64), float(us), filt, variant
+
+    def first(self, w_m, q_m):
+        f, I, Z = self.f, np.eye(3), np.zeros((3, 3))
+        self.q = q_m / math.sqrt(float(q_m @ q_m))
+        self.w = np.array(w_m, dtype=np.float64)
+        self.b = np.zeros(3)
+        a, d, g = f["p0_att"] ** 2, f["p0_bias"] ** 2, f["sigma_g"] ** 2
+        c = -d if self.v["cross"] else 0.0
+        self.P = np.block([[a * I, Z, Z], [Z, (g + d) * I, c * I], [Z, c * I, d * I]])
+
+    def predict(self, u, rows):
+        """``rows``: the field rows of the knot being crossed at c = 0, 1/2, 1"""
+        ol, h, f, J, I, Z = self.ol, self.h, self.f, self.J, np.eye(3), np.zeros((3, 3))
+        w = self.w
+        d = fc.dq_of(h * w)
+        V = _skew(d[1:4])
+        F = (I + 2 * d[0] * V + 2 * V @ V).T                                           # C(h w^)^T
+        G = I + h * ol.inv3(J) @ (_skew(J @ w) - _skew(w) @ J) if self.v["gyroscopic"] else I
+        uu = np.asarray(u, dtype=np.float64) if self.v["command"] else np.zeros(3)
+        x = np.r_[w, self.q]
+        b0, b1, b2 = rows
+        k1 = h * ol.dyn7(x, uu, b0, J, self.us)
+        k2 = h * ol.dyn7(x + k1 / 2, uu, b1, J, self.us)
+        k3 = h * ol.dyn7(x + k2 / 2, uu, b1, J, self.us)
+        k4 = h * ol.dyn7(x + k3, uu, b2, J, self.us)
+        x = x + (k1 + 2 * k2 + 2 * k3 + k4) / 6
+        self.w, self.q = x[:3], x[3:7] / math.sqrt(float(x[3:7] @ x[3:7]))
+        Phi = np.block([[F, h * I, Z], [Z, G, Z], [Z, Z, I]])
+        Q = np.diag(np.r_[np.full(3, (f["sigma_v"] * h) ** 2), np.full(3, (f["sigma_w"] * h) ** 2), np.full(3, f["sigma_u"] ** 2)])
+        self.P = _sym(Phi @ self.P @ Phi.T + Q)
+
+    def _apply(self, PH, S, z):
+        ol = self.ol
+        K = PH @ ol.inv3(S)
+        dl = K @ z
+        qp = ol.qmult(self.q, np.r_[1.0, dl[0:3] / 2])
+        self.q = qp / math.sqrt(float(qp @ qp))
+        self.w = self.w + dl[3:6]
+        self.b = self.b + dl[6:9]
+        self.P = _sym(self.P - K @ S @ K.T)
+
+    def _attitude(self, q_m):
+        ol, f, P = self.ol, self.f, self.P
+        e = ol.qmult(np.r_[self.q[0], -self.q[1:4]], q_m / math.sqrt(float(q_m @ q_m)))
+        z = 2.0 * (-1.0 if e[0] < 0 else 1.0) * e[1:4]
+        self._apply(P[:, 0:3], P[0:3, 0:3] + f["sigma_a"] ** 2 * np.eye(3), z)
+
+    def _gyro(self, w_m):
+        f, P = self.f, self.P
+        z = w_m - (self.w + self.b)
+        S = P[3:6, 3:6] + P[3:6, 6:9] + P[3:6, 6:9].T + P[6:9, 6:9] + f["sigma_g"] ** 2 * np.eye(3)
+        self._apply(P[:, 3:6] + P[:, 6:9], S, z)
+
+    def update(self, w_m, q_m):
+        if self.v["order"] == "ab":
+            self._attitude(q_m)
+            self._gyro(w_m)
+        else:
+            self._gyro(w_m)
+            self._attitude(q_m)
+
+    def final(self):
+        d = np.sqrt(np.diag(self.P))
+        return np.r_[self.b, d]
+
+
+def loop(ol, law, batch, t, Xr, Ur, gains, x0, opts, gid, Rtab, gm, plant=None, lo=None, hi=None, limit_mode=0, noisy=True, sens=None,
+         latency=0, bias=None, filt=None, variant=VARIANT):
+    """``filtered_common.loop`` with ``ModelEkf`` between ``measure`` and the law. ``filt`` None: the raw measurement, the sensed
+    reference itself. Returns X_sim (N, 7), (n_sure, n_maybe), the commands before the limit (N-1, 3), X_hat (N, 7),
+    filt_final (12,), the raw (w_m, q_m) the law would have seen per knot (N, 7)."""
+    NS = batch.N
+    N = NS if batch.n_knots is None else int(batch.n_knots[t])
+    us, h = float(opts.u_scale), float(batch.dt[t])
+    Jm = np.asarray(batch.Jmat[t]).reshape(3, 3).T
+    if plant is None:
+        Jp, G, mres = Jm, np.eye(3), np.zeros(3)
+    else:
+        Jp, G, mres = plant[0:9].reshape(3, 3).T, plant[9:18].reshape(3, 3).T, plant[18:21]
+    Xs, Uc, Xh, Ym = np.zeros((NS, 7)), np.zeros((NS - 1, 3)), np.zeros((NS, 7)), np.zeros((NS, 7))
+    x = np.array(x0, dtype=np.float64)
+    n_sure = n_maybe = 0
+    held = None
+    ekf = None if filt is None else ModelEkf(ol, h, Jm, us, filt, variant)
+    fin = np.zeros(FILTER_W)
+    u_prev = None
+    last = N - 1
+    for k in range(0, last):
+        Xs[k] = x
+        xr = batch.xf[t] if Xr is None else Xr[k]
+        b0, b1, b2 = dc._row(batch, t, k, 0.0), dc._row(batch, t, k, 0.5), dc._row(batch, t, k, 1.0)
+        if sens is None:
+            w_m, q_m = x[:3], x[3:7]
+            b_m = ol.qrot(x[3:7] / math.sqrt(float(x[3:7] @ x[3:7])), b0) if law == "pd" else None
+        else:
+            y = sc.measure(ol, batch, t, k, x, opts, gid, sens, bias, noisy)
+            w_m, q_m, b_m = held if (latency and held is not None) else y       # y_max(k-1, 0)
+            held = y
+        Ym[k] = np.r_[w_m, q_m]
+        if ekf is not None:
+            rows = None if k == 0 else tuple(dc._row(batch, t, k - 1, c) for c in (0.0, 0.5, 1.0))
+            if k == 0:
+                ekf.first(w_m, q_m)
+                fin, post = ekf.final(), (ekf.w, ekf.q)
+            elif latency:
+                if k > 1:                                                       # m_0 handed over a second time: no update
+                    ekf.update(w_m, q_m)
+                fin, post = ekf.final(), (ekf.w, ekf.q)
+                ekf.predict(u_prev, rows)
+            else:
+                ekf.predict(u_prev, rows)
+                ekf.update(w_m, q_m)
+                fin, post = ekf.final(), (ekf.w, ekf.q)
+            w_m, q_m = (ekf.w, ekf.q) if variant["predict"] else post
+            Xh[k] = np.r_[w_m, q_m]
+        qe = ol.qmult(np.r_[xr[3], -xr[4:7]], q_m)
+        if law == "tv":
+            dX = np.r_[w_m - xr[:3], qe[1:4]]
+            u = Ur[k] - gains[k].T @ dX
+        else:
+            kd, kp = gains
+            dw = w_m - xr[:3]
+            s = -1.0 if qe[0] < 0 else 1.0
+            treq = -(kd * dw + kp * (s * qe[1:4]))
+            bb = float(b_m @ b_m)
+            m = np.cross(b_m, treq) / bb if bb != 0.0 else np.zeros(3)
+            u = (Ur[k] if Ur is not None else np.zeros(3)) + m / us
+        Uc[k] = u
+        if limit_mode == 1:
+            r = np.array([u[c] / hi[c] if u[c] > 0 else (u[c] / lo[c] if u[c] < 0 else 0.0) for c in range(3)])
+            beta = float(r.max())
+            n_sure += bool(beta - 1.0 > dc.CLIP_BAND)
+            n_maybe += bool(beta - 1.0 > -dc.CLIP_BAND)
+            if beta > 1.0:
+                u = u * (1.0 / beta)
+        elif lo is not None:
+            bl, bh = dc.CLIP_BAND * np.abs(lo), dc.CLIP_BAND * np.abs(hi)
+            n_sure += bool(np.any((lo - u > bl) | (u - hi > bh)))
+            n_maybe += bool(np.any((lo - u > -bl) | (u - hi > -bh)))
+            u = np.minimum(np.maximum(u, lo), hi)
+        u_prev = np.array(u, dtype=np.float64)                                  # as the law issued it: what goes to the actuators
+        ua = G @ u + mres / us
+        nz = [ol.plant_noise(int(opts.noise_seed), int(gid), k, st, opts.sigma_gyro, opts.sigma_att, opts.field_amp) if noisy else None
+              for st in range(4)]
+        rr = [None] * 3 if Rtab is None else [gc._grow(batch, Rtab, t, k, c) for c in (0.0, 0.5, 1.0)]
+
+        def f(xx, bb_, n, r):
+            xn, bn = dc._noisy(ol, xx, bb_, n)
+            kk = h * ol.dyn7(xn, ua, bn, Jp, us)
+            if r is not None:
+                kk[0:3] = kk[0:3] + gc.gg_increment(ol, xx, r, gm, Jp, h)
+            return kk
+
+        k1 = f(x, b0, nz[0], rr[0])
+        k2 = f(x + k1 / 2, b1, nz[1], rr[1])
+        k3 = f(x + k2 / 2, b1, nz[2], rr[1])
+        k4 = f(x + k3, b2, nz[3], rr[2])
+        x = x + (k1 + 2 * k2 + 2 * k3 + k4) / 6
+    Xs[last] = x
+    return Xs, (n_sure, n_maybe), Uc, Xh, fin, Ym
+
+
+def pairs_of(ol, abi, law, batch, x0_sim, gains, opts, pairs, X=None, U=None, Rtab=None, gm=0.0, plant=None, sat=None, limit_mode=0,
+             x0_nom=None, noise_id0=None, sens=None, latency=0, sensor=None, filt=None, variant=VARIANT):
+    """``filtered_common.pairs_of`` through ``loop`` above: its dict with filt_final (n, 12)"""
+    T, M = x0_sim.shape[:2]
+    id0 = np.arange(T, dtype=np.int64) * M if noise_id0 is None else np.asarray(noise_id0, dtype=np.int64)
+    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
+    if law == "pd":
+        gains = (np.broadcast_to(gains[0], (T, 3)), np.broadcast_to(gains[1], (T, 3)))
+    ol.load()
+    res = []
+    for p in pairs:
+        t, m = int(p[0]), int(p[1])
+        g = gains[t] if law == "tv" else (gains[0][t], gains[1][t])
+        kw = dict(lo=None if lo is None else lo[t], hi=None if hi is None else hi[t], limit_mode=limit_mode, sens=sens, latency=latency,
+                  filt=filt, variant=variant)
+        Xr, Ur = None if X is None else X[t], None if U is None else U[t]
+        if m < 0:
+            x0 = x0_nom[t] if x0_nom is not None else X[t, 0]
+            res.append(loop(ol, law, batch, t, Xr, Ur, g, x0, opts, 0, Rtab, gm, None, noisy=False, **kw))
+        else:
+            res.append(loop(ol, law, batch, t, Xr, Ur, g, x0_sim[t, m], opts, id0[t] + m, Rtab, gm, None if plant is None else plant[t, m],
+                            bias=None if sensor is None else sensor[t, m], **kw))
+    pairs = np.asarray(pairs)
+    Xs = np.stack([r[0] for r in res])
+    nk = ec.horizons(batch)[pairs[:, 0]]
+    xf = batch.xf[pairs[:, 0]]
+    st = dc.stats_of(abi, Xs, xf, nk, batch.dt[pairs[:, 0]], opts.min_steps, opts.w_tol, opts.angle_tol)
+    return dict(X_sim=Xs, stats=st, n_sure=np.array([r[1][0] for r in res]), n_maybe=np.array([r[1][1] for r in res]), xf=xf, n_knots=nk,
+                U_cmd=np.stack([r[2] for r in res]), X_hat=np.stack([r[3] for r in res]), filt_final=np.stack([r[4] for r in res]),
+                Y_raw=np.stack([r[5] for r in res]))
+
+
+# the terms a parity test shows to act, as (label, what replaces in the call of ``ref_of``); the latency-1 one is added there
+def terms_of(filt):
+    return [
+        ("sigma_w against three times it", dict(filt=dict(filt, sigma_w=3.0 * filt["sigma_w"]))),
+        ("sigma_g against three times it", dict(filt=dict(filt, sigma_g=3.0 * filt["sigma_g"]))),
+        ("sigma_u with p0_bias against three times them", dict(filt=dict(filt, sigma_u=3.0 * filt["sigma_u"], p0_bias=3.0 * filt["p0_bias"]))),
+        (COMMAND, dict(variant=dict(VARIANT, command=False))),
+        (GYROSCOPIC, dict(variant=dict(VARIANT, gyroscopic=False))),
+        ("the -p0_bias^2 cross block of first against none", dict(variant=dict(VARIANT, cross=False))),
+        (ORDER, dict(variant=dict(VARIANT, order="ba"))),
+    ]
+
+
+COMMAND = "the command in predict against u = 0"
+GYROSCOPIC = "the gyroscopic term of Phi_ww against Phi_ww = I"
+ORDER = "the update order a, b against b, a"
+DELAY = ("the prediction across the delay against y_k = posterior", dict(latency=1, variant=dict(VARIANT, predict=False)))
+
+
+def moved(ref, other):
+    """max |d final state| between two references of the same pairs"""
+    n = ref["n_knots"]
+    i = np.arange(len(n))
+    return float(np.max(np.abs(ref["X_sim"][i, n - 1] - other["X_sim"][i, n - 1])))
+
+
+def conditions(ref_of, sensor, latency, skip=(), filt=FILT):
+    """the conditions of a parity test on references alone (bar gg_common.MOVED on the final states). ``ref_of(**over)`` is the
+    reference of the test's call with the named arguments replaced; the call flies sensor biases ``sensor`` with a gyro bias in them.
+    Filtered against raw moves the final state, and so does each of ``terms_of(filt)``; at latency 1 also DELAY. ``skip`` names the
+    labels that the test leaves to the one that flies the case on which they show (the FAST starts, the LOUD sensor): their figures
+    are printed. Returns the reference of the call itself."""
+    assert np.abs(sensor[..., 0:3]).min() > 0, "the conditions on sigma_u and p0_bias need a gyro bias"
+    ref = ref_of()
+    terms = [("filtered against raw", dict(filt=None))] + terms_of(filt) + ([DELAY] if latency else [])
+    short = []
+    for label, over in terms:
+        d = moved(ref, ref_of(**over))
+        print(f"  condition: {label}: max|d final state| {d:.2e}" + ("  (left to the case that shows it)" if label in skip else ""))
+        if label not in skip and not d >= gc.MOVED:
+            short.append(f"{label} moves the final state by {d:.2e} only")
+    assert not short, short
+    return ref
+
+
+def compare_estimates(ref, got, pairs, idx=None):
+    """X_hat and filt_final against the reference to 1e-9, the project's bar for these loops; X_hat zero from the last knot on"""
+    assert got["filt_final"].shape[-1] == FILTER_W
+    fc.compare_estimates(ref, got, pairs, idx)
+
+
+def filter_options(abi, filt):
+    return abi.ModelFilterOptions(sigma_v=filt["sigma_v"], sigma_w=filt["sigma_w"], sigma_u=filt["sigma_u"], sigma_a=filt["sigma_a"],
+                                  sigma_g=filt["sigma_g"], p0_att=filt["p0_att"], p0_bias=filt["p0_bias"], reserved=0)
+
+
+def first_record(filt):
+    """filt_final when no update was made"""
+    return np.r_[np.zeros(3), np.full(3, filt["p0_att"]), np.full(3, math.sqrt(filt["sigma_g"] ** 2 + filt["p0_bias"] ** 2)),
+                 np.full(3, filt["p0_bias"])]
+
+
+def _outputs(v, abi, filt, fo, estimates):
+    """the three filter arguments of a call: ``fo`` 0 builds the options from ``filt`` (None: f = NULL and no outputs)"""
+    T, M, N = v["T"], v["M"], v["o"].n_knots
+    v["f"] = (None if filt is None else filter_options(abi, filt)) if fo == 0 else fo
+    on = v["f"] is not None
+    v["X_hat"] = np.full((T, M, N, 7), np.nan) if (on and estimates) else None
+    v["filt_final"] = np.full((T, M, FILTER_W), np.nan) if (on and estimates) else None
+
+
+def _tail(v, abi):
+    return [None if v["f"] is None else C.byref(v["f"]), abi.as_dp(v["X_hat"]), abi.as_dp(v["filt_final"])]
+
+
+class TvCall(sc.TvCall):
+    """sensed_common.TvCall followed by the three filter arguments: tsat_tvlqr_ensemble_model_filtered after the handle, or —
+    ``emu=True`` — emu_tvlqr_ensemble_model_filtered"""
+
+    def __init__(self, abi, *a, filt=FILT, fo=0, estimates=True, **kw):
+        super().__init__(abi, *a, **kw)
+        _outputs(self.v, abi, filt, fo, estimates)
+
+    def edit(self, **kw):
+        other = sc.TvCall.edit(self, **kw)
+        other.__class__ = TvCall
+        return other
+
+    def c_args(self, emu=False):
+        return super().c_args(emu) + _tail(self.v, self.abi)
+
+    def result(self):
+        return dict(super().result(), X_hat=self.v["X_hat"], filt_final=self.v["filt_final"])
+
+
+class PdCall(sc.PdCall):
+    """sensed_common.PdCall followed by the three filter arguments: tsat_pd_ensemble_model_filtered after the handle, or
+    emu_pd_ensemble_model_filtered"""
+
+    def __init__(self, abi, *a, filt=FILT, fo=0, estimates=True, **kw):
+        super().__init__(abi, *a, **kw)
+        _outputs(self.v, abi, filt, fo, estimates)
+
+    def edit(self, **kw):
+        other = sc.PdCall.edit(self, **kw)
+        other.__class__ = PdCall
+        return other
+
+    def c_args(self, names=pc.FIELDS):
+        return super().c_args(names) + _tail(self.v, self.abi)
+
+    def result(self):
+        return dict(super().result(), X_hat=self.v["X_hat"], filt_final=self.v["filt_final"])
+
+
+def filter_rejections(call):
+    """what check_model_filter and the entry points reject of the filter arguments, as (label, edited call, words of the text)"""
+    abi, f = call.abi, call.v["f"]
+
+    def fo(**kw):
+        o = abi.ModelFilterOptions.from_buffer_copy(f)
+        for k, val in kw.items():
+            setattr(o, k, val)
+        return o
+
+    return [
+        ("sigma_v NaN", call.edit(f=fo(sigma_v=float("nan"))), "must be finite and >= 0"),
+        ("sigma_w negative", call.edit(f=fo(sigma_w=-1e-6)), "must be finite and >= 0"),
+        ("sigma_w inf", call.edit(f=fo(sigma_w=float("inf"))), "must be finite and >= 0"),
+        ("sigma_u inf", call.edit(f=fo(sigma_u=float("inf"))), "must be finite and >= 0"),
+        ("sigma_a negative", call.edit(f=fo(sigma_a=-1e-3)), "must be finite and >= 0"),
+        ("sigma_g NaN", call.edit(f=fo(sigma_g=float("nan"))), "must be finite and >= 0"),
+        ("p0_att negative", call.edit(f=fo(p0_att=-1.0)), "must be finite and >= 0"),
+        ("p0_bias NaN", call.edit(f=fo(p0_bias=float("nan"))), "must be finite and >= 0"),
+        ("sigma_a zero", call.edit(f=fo(sigma_a=0.0)), "sigma_a must be > 0"),
+        ("sigma_g zero", call.edit(f=fo(sigma_g=0.0)), "sigma_g must be > 0"),
+        ("reserved 1", call.edit(f=fo(reserved=1)), "reserved must be 0"),
+    ]
+
+
+# the long horizon: sigma_w chosen on the reference (tests/test_model_filtered.py prints the ratio it gives)
+LONG_SIGMA_W = 3e-4
+
+
+def long_case(pkg, ol, N, M):
+    """``filtered_common.long_case`` (T = 1, the PD law regulating on the model's plant with plant noise, the reference's sensor
+    figures, a gyro bias of filtered_common.GYRO_BIAS in a drawn direction, latency 0) flown behind this filter — sigma_g, sigma_a =
+    p0_att the sensor's figures, p0_bias the bias' size, sigma_w = LONG_SIGMA_W — next to the six-state reference on the same draws"""
+    c = fc.long_case(pkg, ol, N, M)
+    tr = pkg.tracking
+    filt = dict(sigma_v=0.0, sigma_w=LONG_SIGMA_W, sigma_u=0.0, sigma_a=tr.SENSOR_SIGMA_ATT, sigma_g=tr.SENSOR_SIGMA_GYRO,
+                p0_att=tr.SENSOR_SIGMA_ATT, p0_bias=fc.GYRO_BIAS)
+    kw = dict(c["kw"], filt=filt)
+    ref = pairs_of(ol, pkg._abi, "pd", c["b"], c["x0s"], (sc.KD, sc.KP), c["o"], c["pairs"], **kw)
+    return dict(c, kw=kw, ref=ref, six=c["ref"])
+
+
+def assert_filter_works(c):
+    """on the references alone, over the last half of the horizon: the rms rate error of the estimate is below a quarter of the raw
+    sample's; the rms attitude error is no worse than the six-state reference's on the same draws within 10 %; the bias estimate is
+    inside 3 x its own sqrt(diag P_bb) on every realisation"""
+    ref, six, N = c["ref"], c["six"], c["b"].N
+    half = slice(N // 2, N - 1)
+    we, wr, ae, a6 = [], [], [], []
+    for i, (t, m) in enumerate(c["pairs"]):
+        true = ref["X_sim"][i, half]
+        we.append(np.mean(np.sum((ref["X_hat"][i, half, 0:3] - true[:, 0:3]) ** 2, axis=1)))
+        wr.append(np.mean(np.sum((ref["Y_raw"][i, half, 0:3] - true[:, 0:3]) ** 2, axis=1)))
+        ae.append(np.mean(fc._angles(ref["X_hat"][i, half, 3:7], true[:, 3:7]) ** 2))
+        a6.append(np.mean(fc._angles(six["X_hat"][i, half, 3:7], six["X_sim"][i, half, 3:7]) ** 2))
+    we, wr, ae, a6 = (math.sqrt(float(np.mean(v))) for v in (we, wr, ae, a6))
+    print(f"rms over the last half: rate error of the estimate {we:.2e} rad/s against the raw sample's {wr:.2e}: ratio "
+          f"{we / wr:.3f}; attitude error {math.degrees(ae):.3f} deg against the six-state reference's {math.degrees(a6):.3f} deg")
+    assert we < 0.25 * wr, "the filter does not smooth the gyro noise"
+    assert ae <= 1.10 * a6, "the attitude estimate is worse than the six-state filter's"
+    pr = c["pairs"]
+    db = np.abs(ref["filt_final"][:, 0:3] - c["sensor"][pr[:, 0], pr[:, 1], 0:3])
+    print(f"|b^ - bw| / sqrt(diag P_bb) at the end: max {float(np.max(db / ref['filt_final'][:, 9:12])):.2f}")
+    assert np.all(db < 3.0 * ref["filt_final"][:, 9:12]), "the bias estimate is outside 3 sigma of its own covariance"
+
+
+class EmuModelFiltered:
+    """ctypes binding of tests/emu/libtsat_emu_model_filtered.so (the four emulated kernels), built here by the emulator's pattern
+    rule"""
+
+    def __init__(self, abi):
+        d = os.path.join(ROOT, "tests", "emu")
+        subprocess.check_call(["make", "-C", d, "libtsat_emu_model_filtered.so"], stdout=subprocess.DEVNULL)
+        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_model_filtered.so"))
+        self.abi = abi
+
+    def tv(self, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K, **kw):
+        call = TvCall(self.abi, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K=K, **kw)
+        rc = self.lib.emu_tvlqr_ensemble_model_filtered(*call.c_args(emu=True))
+        if rc != 0:
+            raise RuntimeError(f"emu_tvlqr_ensemble_model_filtered rc={rc}")
+        return call.result()
+
+    def pd(self, batch, opts, x0_sim, kd, kp, **kw):
+        call = PdCall(self.abi, batch, opts, x0_sim, kd, kp, **kw)
+        rc = self.lib.emu_pd_ensemble_model_filtered(*call.c_args())
+        if rc != 0:
+            raise RuntimeError(f"emu_pd_ensemble_model_filtered rc={rc}")
+        return call.result()
+
+    def check(self, call):
+        """check_model_filter on the filter options of a call"""
+        text = C.create_string_buffer(256)
+        f = call.v["f"]
+        rc = self.lib.emu_model_filter_check(None if f is None else C.byref(f), text, C.c_int32(256))
+        return rc, text.value.decode()

@@ -8,6 +8,7 @@ driver around them.
 
     python tools/resource_usage.py [profiles/r03/resource_usage.txt]
     python tools/resource_usage.py profiles/ensemble/filtered_resource_usage.txt --units tsat_kernels_sensed.hip,tsat_kernels_filtered.hip
+    python tools/resource_usage.py profiles/ensemble/model_filtered_resource_usage.txt --units tsat_kernels_filtered.hip,tsat_kernels_model_filtered.hip
 With --units every kernel of the named units is listed (the lane-per-realisation roll-outs have no phase functions), not only
 the solve kernels.
 """

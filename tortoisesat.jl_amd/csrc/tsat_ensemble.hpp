@@ -89,9 +89,12 @@ struct ModelPlant {
 // What the LAW sees of the lane's state, as a plant type answers what the plant is. TrueState: the state itself (`state`) and
 // the stage-0 field row in the body frame of the true attitude (`field`, used by the PD law of tsat_pd.hpp) — every entry point
 // but the sensed ones (Sensed of tsat_sensed.hpp: biases, noise and a one-knot delay). `load` is called once per lane after the
-// plant's; gid, k and noisy name the realisation's generator id, the knot and whether the lane draws noise at all.
+// plant's; gid, k and noisy name the realisation's generator id, the knot and whether the lane draws noise at all. `commanded`
+// is told the command of knot k where it goes to plant.actuate (ModelFiltered of tsat_model_filtered.hpp predicts with it).
 struct TrueState {
   TSAT_DEV void load(int, int) {}
+  template <typename real>
+  TSAT_DEV void commanded(int, const real*) {}                 // the command of knot k on its way to plant.actuate: not used
   template <typename real>
   TSAT_DEV void state(long long, int, bool, const real x[7], real y[7]) {
     for (int i = 0; i < 7; ++i) y[i] = x[i];
@@ -170,6 +173,7 @@ TSAT_DEV void ensemble_rollout(const EnsArgs<real>& a, Plant& plant, int traj, i
       for (int j = 0; j < 6; ++j) v += kd[c * 7 + j] * dX[j];   // kd = -K_lqr
       uc[c] = plant.command(c, v, cs);
     }
+    sensor.commanded(k, uc);                                   // the command as the law issued it, for a sensor that models the plant
     plant.actuate(uc, cs, us);
     // rows at tau, tau + dtau/2, tau + dtau: wave-uniform indices, said so (the clock is fp64 arithmetic on the vector unit)
     const TSAT_CONSTMEM real* p0 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tr, k, 0.0)) * 4;

@@ -140,6 +140,7 @@ struct Filtered {
     for (int i = 0; i < 6; ++i) { st.A[i] = 0; st.D[i] = 0; }
     for (int i = 0; i < 9; ++i) st.B[i] = 0;
   }
+  TSAT_DEV void commanded(int, const real*) {}                 // the gyro propagates this filter, not the model
   TSAT_DEV void first(const real m[7]) {
     const real rn = rsqrt_<real>(m[3] * m[3] + m[4] * m[4] + m[5] * m[5] + m[6] * m[6]);
     for (int i = 0; i < 4; ++i) st.q[i] = m[3 + i] * rn;

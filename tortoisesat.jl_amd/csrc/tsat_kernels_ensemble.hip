@@ -31,6 +31,9 @@
 // tsat_tvlqr_ensemble_filtered and tsat_pd_ensemble_filtered (tsat_filtered.hpp) are the sensed calls with a `Filtering`: the host
 // validates the filter options (check_filter), zero-fills X_hat when asked for, and step 4 launches a kernel of
 // tsat_kernels_filtered.hip. f == NULL is dispatched to the sensed call itself.
+//
+// tsat_tvlqr_ensemble_model_filtered and tsat_pd_ensemble_model_filtered (tsat_model_filtered.hpp) are the same with a `Filtering`
+// that names the nine-state filter's options (check_model_filter, the kernels of tsat_kernels_model_filtered.hip).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -44,6 +47,7 @@
 #include "tsat_pd.hpp"
 #include "tsat_sensed.hpp"
 #include "tsat_filtered.hpp"
+#include "tsat_model_filtered.hpp"
 
 using namespace tsat;
 
@@ -62,6 +66,9 @@ hipError_t tsat_launch_sensed_pd(const SensedPdArgs<double>& a, int waves, hipSt
 // roll-outs of the filtered calls (tsat_kernels_filtered.hip)
 hipError_t tsat_launch_filtered_tv(const FilteredTvArgs<double>& a, int waves, hipStream_t stream);
 hipError_t tsat_launch_filtered_pd(const FilteredPdArgs<double>& a, int waves, hipStream_t stream);
+// roll-outs of the model-filtered calls (tsat_kernels_model_filtered.hip)
+hipError_t tsat_launch_model_filtered_tv(const ModelFilteredTvArgs<double>& a, int waves, hipStream_t stream);
+hipError_t tsat_launch_model_filtered_pd(const ModelFilteredPdArgs<double>& a, int waves, hipStream_t stream);
 
 template <typename real, int DIAGJ>
 __global__ __launch_bounds__(64) void tsat_ensemble_kernel(EnsArgs<real> a) {
@@ -162,6 +169,9 @@ struct Sensing {
 struct Filtering {
   const tsat_filter_options* f;
   double *X_hat, *filt_final;
+  const tsat_model_filter_options* mf = nullptr;   // the nine-state filter in place of f
+  std::string check() const { return mf ? check_model_filter(mf) : check_filter(f); }
+  size_t final_w() const { return mf ? (size_t)MFFW : (size_t)FFW; }
 };
 
 // every realisation flies the model's plant: (Jmat, G = I, m_res = 0); the pack reads the upper triangle of Jp
@@ -189,6 +199,16 @@ FiltArgs<double> filt_args(const Filtering& fl, const SensArgs<double>& sa, cons
   FiltArgs<double> a;
   a.s = sa; a.P = e.P; a.nk = e.nk; a.M = e.M; a.N = e.N;
   a.sv = fl.f->sigma_v; a.su = fl.f->sigma_u; a.sa = fl.f->sigma_a; a.p0a = fl.f->p0_att; a.p0b = fl.f->p0_bias;
+  a.XH = dXH; a.FF = dFF;
+  return a;
+}
+
+// ... and of the nine-state filter, which reads the slew's constants and field rows itself
+ModelFiltArgs<double> model_filt_args(const Filtering& fl, const SensArgs<double>& sa, const EnsArgs<double>& e, double* dXH, double* dFF) {
+  ModelFiltArgs<double> a;
+  const tsat_model_filter_options& o = *fl.mf;
+  a.s = sa; a.P = e.P; a.BT = e.BT; a.bidx = e.bidx; a.nk = e.nk; a.M = e.M; a.N = e.N; a.n_tab = e.n_tab; a.us = e.us;
+  a.sv = o.sigma_v; a.sw = o.sigma_w; a.su = o.sigma_u; a.sa = o.sigma_a; a.sg = o.sigma_g; a.p0a = o.p0_att; a.p0b = o.p0_bias;
   a.XH = dXH; a.FF = dFF;
   return a;
 }
@@ -262,7 +282,7 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
     if (!bad.empty()) return efail(-1, bad);
   }
   if (filt) {
-    const std::string bad = check_filter(filt->f);
+    const std::string bad = filt->check();
     if (!bad.empty()) return efail(-1, bad);
   }
   // ---- 1. the handle: the library's own checks on slew 0 cut to two knots; its GPU becomes the thread's current device ----
@@ -311,7 +331,7 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   // the filtered call: what the law saw and the filter's last state, when asked for
   double *dXH = nullptr, *dFF = nullptr;
   if (ok && filt && filt->X_hat) ok = s.alloc(&dXH, nS * N * 7);
-  if (ok && filt && filt->filt_final) ok = s.alloc(&dFF, nS * FFW);
+  if (ok && filt && filt->filt_final) ok = s.alloc(&dFF, nS * filt->final_w());
   if (!ok) return efail(-10, std::string("device allocation failed in ") + name);
 #define ENS_HIP(call)                                                                                   \
   do {                                                                                                  \
@@ -376,7 +396,12 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
     if (disp) {
       DispArgs<double> d;
       d.e = a; d.PL = dPL; d.Mp = Mp; d.SAT = dSat; d.nclip = dClip;
-      if (filt) {
+      if (filt && filt->mf) {
+        ModelFilteredTvArgs<double> fa;
+        fa.g.d = d; fa.g.GT = dGT;
+        fa.f = model_filt_args(*filt, sens_args(*sens, o, dSN, Mp), a, dXH, dFF);
+        ENS_HIP(tsat_launch_model_filtered_tv(fa, nw, s.stream));
+      } else if (filt) {
         FilteredTvArgs<double> fa;
         fa.g.d = d; fa.g.GT = dGT;
         fa.f = filt_args(*filt, sens_args(*sens, o, dSN, Mp), a, dXH, dFF);
@@ -413,7 +438,7 @@ int run_ensemble(const char* name, tsat_handle* h, const tsat_tvlqr_options* o, 
   if (X_sim) ENS_HIP(hipMemcpy(X_sim, dXS, nXS * 8, hipMemcpyDeviceToHost));
   if (dClip) ENS_HIP(hipMemcpy(disp->n_clipped, dClip, nS * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (dXH) ENS_HIP(hipMemcpy(filt->X_hat, dXH, nS * N * 7 * 8, hipMemcpyDeviceToHost));
-  if (dFF) ENS_HIP(hipMemcpy(filt->filt_final, dFF, nS * FFW * 8, hipMemcpyDeviceToHost));
+  if (dFF) ENS_HIP(hipMemcpy(filt->filt_final, dFF, nS * filt->final_w() * 8, hipMemcpyDeviceToHost));
   ensemble_summary(T, M, stats, summary);
   if (const char* v = std::getenv("TSAT_ENSEMBLE_TIMING")) {   // diagnostic (tools/ensemble_timing.py): HIP-event times of the two kernels
     if (v[0] == '1') {
@@ -451,7 +476,7 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
     if (!bad.empty()) return efail(-1, bad);
   }
   if (filt) {
-    const std::string bad = check_filter(filt->f);
+    const std::string bad = filt->check();
     if (!bad.empty()) return efail(-1, bad);
   }
 #define ENS_HIP(call)                                                                                   \
@@ -502,7 +527,7 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
   // the filtered call: what the law saw and the filter's last state, when asked for
   double *dXH = nullptr, *dFF = nullptr;
   if (ok && filt && filt->X_hat) ok = s.alloc(&dXH, nS * N * 7);
-  if (ok && filt && filt->filt_final) ok = s.alloc(&dFF, nS * FFW);
+  if (ok && filt && filt->filt_final) ok = s.alloc(&dFF, nS * filt->final_w());
   if (!ok) return efail(-10, "device allocation failed in tsat_pd_ensemble");
   ENS_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
   for (hipEvent_t& e : s.ev) ENS_HIP(hipEventCreate(&e));
@@ -553,7 +578,12 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
     a.XS = dXS; a.stats = dst; a.stats_nom = dsn;
     pa.d.PL = dPL; pa.d.Mp = Mp; pa.d.SAT = dSat; pa.d.nclip = dClip;
     pa.GT = dGT; pa.GAIN = dGain; pa.X0N = dX0N; pa.feedforward = feedforward; pa.limit_mode = limit_mode;
-    if (filt) {
+    if (filt && filt->mf) {
+      ModelFilteredPdArgs<double> fa;
+      fa.p = pa;
+      fa.f = model_filt_args(*filt, sens_args(*sens, o, dSN, Mp), a, dXH, dFF);
+      ENS_HIP(tsat_launch_model_filtered_pd(fa, nw, s.stream));
+    } else if (filt) {
       FilteredPdArgs<double> fa;
       fa.p = pa;
       fa.f = filt_args(*filt, sens_args(*sens, o, dSN, Mp), a, dXH, dFF);
@@ -575,13 +605,13 @@ int run_pd(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_bta
   if (X_sim) ENS_HIP(hipMemcpy(X_sim, dXS, nXS * 8, hipMemcpyDeviceToHost));
   if (dClip) ENS_HIP(hipMemcpy(n_clipped, dClip, nS * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (dXH) ENS_HIP(hipMemcpy(filt->X_hat, dXH, nS * N * 7 * 8, hipMemcpyDeviceToHost));
-  if (dFF) ENS_HIP(hipMemcpy(filt->filt_final, dFF, nS * FFW * 8, hipMemcpyDeviceToHost));
+  if (dFF) ENS_HIP(hipMemcpy(filt->filt_final, dFF, nS * filt->final_w() * 8, hipMemcpyDeviceToHost));
   ensemble_summary(T, M, stats, summary);
   if (const char* v = std::getenv("TSAT_ENSEMBLE_TIMING")) {   // diagnostic (tools/pd_timing.py): HIP-event time of the roll-out
     if (v[0] == '1') {
       float e = 0;
       (void)hipEventElapsedTime(&e, s.ev[0], s.ev[1]);
-      std::fprintf(stderr, "%s: pd_kernel_ms %.4f\n", filt ? "tsat_pd_ensemble_filtered" : (sens ? "tsat_pd_ensemble_sensed" : "tsat_pd_ensemble"), e);
+      std::fprintf(stderr, "%s: pd_kernel_ms %.4f\n", filt ? (filt->mf ? "tsat_pd_ensemble_model_filtered" : "tsat_pd_ensemble_filtered") : (sens ? "tsat_pd_ensemble_sensed" : "tsat_pd_ensemble"), e);
     }
   }
 #undef ENS_HIP
@@ -628,6 +658,31 @@ int tsat_pd_ensemble_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64
   return run_pd(h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode, x0_sim, x0_nom,
                 noise_id0, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, X_sim, n_clipped, Rtab, gm, &se,
                 f ? &fl : nullptr);
+}
+
+int tsat_pd_ensemble_model_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                                    const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                                    const double* dtau, const double* dt, const double* Jmat, const double* kd, const double* kp,
+                                    int32_t feedforward, int32_t limit_mode, const double* x0_sim, const double* x0_nom,
+                                    const int64_t* noise_id0, const int32_t* n_knots, const double* plant, const double* sat_lo,
+                                    const double* sat_hi, tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                                    double* X_sim, int32_t* n_clipped, const double* Rtab, double gm, const tsat_sensor_options* sn,
+                                    const double* sensor, const tsat_model_filter_options* f, double* X_hat, double* filt_final) {
+  if (!f && unfiltered_outputs(X_hat, filt_final)) return -1;
+  const Sensing se{sn, sensor};
+  const Filtering fl{nullptr, X_hat, filt_final, f};
+  return run_pd(h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode, x0_sim, x0_nom,
+                noise_id0, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, X_sim, n_clipped, Rtab, gm, &se,
+                f ? &fl : nullptr);
+}
+
+void tsat_model_filter_default_options(tsat_model_filter_options* f) {
+  if (!f) return;
+  const double pi = 3.14159265358979323846;
+  f->sigma_v = 0.0; f->sigma_w = 0.0; f->sigma_u = 0.0;       // sigma_w has no default that could be derived: the caller's choice
+  f->sigma_a = pi / 180.0; f->sigma_g = 0.38 * pi / 180.0;     // the levels tsat_filter_default_options takes
+  f->p0_att = pi / 180.0; f->p0_bias = 0.0;
+  f->reserved = 0;
 }
 
 void tsat_filter_default_options(tsat_filter_options* f) {
@@ -711,6 +766,24 @@ int tsat_tvlqr_ensemble_filtered(tsat_handle* h, const tsat_tvlqr_options* o, in
   return run_ensemble(f ? "tsat_tvlqr_ensemble_filtered" : "tsat_tvlqr_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0,
                       dtau, dt, Jmat, Qd, Qfd, Rd, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, K_lqr, X_sim, &d, &g, &se,
                       f ? &fl : nullptr);
+}
+
+int tsat_tvlqr_ensemble_model_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                                       const double* U, const double* xf, const double* Btab, const int32_t* btab_idx,
+                                       const double* tau0, const double* dtau, const double* dt, const double* Jmat, const double* Qd,
+                                       const double* Qfd, const double* Rd, const double* x0_sim, const int64_t* noise_id0,
+                                       const int32_t* n_knots, const double* plant, const double* sat_lo, const double* sat_hi,
+                                       tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr,
+                                       double* X_sim, int32_t* n_clipped, const double* Rtab, double gm, const tsat_sensor_options* sn,
+                                       const double* sensor, const tsat_model_filter_options* f, double* X_hat, double* filt_final) {
+  if (!f && unfiltered_outputs(X_hat, filt_final)) return -1;
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  const Sensing se{sn, sensor};
+  const Filtering fl{nullptr, X_hat, filt_final, f};
+  return run_ensemble(f ? "tsat_tvlqr_ensemble_model_filtered" : "tsat_tvlqr_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx,
+                      tau0, dtau, dt, Jmat, Qd, Qfd, Rd, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, K_lqr, X_sim, &d, &g,
+                      &se, f ? &fl : nullptr);
 }
 
 }  // extern "C"

@@ -152,6 +152,7 @@ TSAT_DEV void pd_rollout(const PdArgs<real>& pa, Plant& plant, int traj, int wav
     } else {
       for (int c = 0; c < 3; ++c) uc[c] = plant.command(c, uc[c], cs);
     }
+    sensor.commanded(k, uc);                                   // as ensemble_rollout hands it over
     plant.actuate(uc, cs, us);
     real k1[7], k2[7], k3[7], k4[7], t[7], nz[9];
     for (int i = 0; i < 9; ++i) nz[i] = 0;

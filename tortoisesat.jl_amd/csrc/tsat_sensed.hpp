@@ -72,6 +72,7 @@ struct Sensed {
     for (int i = 0; i < 7; ++i) hy[i] = 0;
     for (int i = 0; i < 3; ++i) hb[i] = 0;
   }
+  TSAT_DEV void commanded(int, const real*) {}                 // a measurement does not depend on the command
   // y: (w_m, q_m) of knot k, or of knot max(k - 1, 0)
   TSAT_DEV void state(long long gid, int k, bool noisy, const real x[7], real y[7]) {
     real nw[3] = {0, 0, 0}, na[3] = {0, 0, 0};

@@ -374,7 +374,8 @@ def attitude_ensemble_pd(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X
 def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0, want_trajectories,
              sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=None, filtering=None):
     """``tsat_pd_ensemble``, or with ``sensing`` = (SensorOptions, sensor array or None) ``tsat_pd_ensemble_sensed``, or with
-    ``filtering`` = (FilterOptions, X_hat or None, filt_final or None) besides ``tsat_pd_ensemble_filtered``"""
+    ``filtering`` = (FilterOptions, X_hat or None, filt_final or None) besides ``tsat_pd_ensemble_filtered`` — with ModelFilterOptions
+    in its place ``tsat_pd_ensemble_model_filtered``"""
     lib = _abi.load()
     T, N = batch.T, batch.N
     c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
@@ -422,8 +423,8 @@ def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, s
     if sensing is None:
         name, rc = "tsat_pd_ensemble", lib.tsat_pd_ensemble(*args)
     elif filtering is not None:
-        name, rc = "tsat_pd_ensemble_filtered", lib.tsat_pd_ensemble_filtered(*args, C.byref(sensing[0]), d(sensing[1]),
-                                                                             C.byref(filtering[0]), d(filtering[1]), d(filtering[2]))
+        name = "tsat_pd_ensemble_model_filtered" if isinstance(filtering[0], _abi.ModelFilterOptions) else "tsat_pd_ensemble_filtered"
+        rc = getattr(lib, name)(*args, C.byref(sensing[0]), d(sensing[1]), C.byref(filtering[0]), d(filtering[1]), d(filtering[2]))
     else:
         name, rc = "tsat_pd_ensemble_sensed", lib.tsat_pd_ensemble_sensed(*args, C.byref(sensing[0]), d(sensing[1]))
     if rc != 0:
@@ -550,6 +551,16 @@ def attitude_ensemble_filtered(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, 
     state). Returns the dict of ``attitude_ensemble_sensed`` plus ``filt_final`` (T, M, 9) = [b^, sqrt(diag A), sqrt(diag D)] after
     the last sample processed and ``X_hat`` (T, M, N, 7), what the law saw per knot (zero from the slew's last knot on), or None
     without ``want_estimates``. ``nominal`` flies the ideal sensor through the same filter."""
+    return _tv_filtered_call("tsat_tvlqr_ensemble_filtered", _filtering, solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant, Rtab, gm,
+                             sat, sensor, sigma_gyro, sigma_att, sigma_mag, latency, noise_id0, sigma_scale, want_K, want_trajectories,
+                             linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol, filter, want_estimates)
+
+
+def _tv_filtered_call(name, filtering, solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant, Rtab, gm, sat, sensor, sigma_gyro,
+                      sigma_att, sigma_mag, latency, noise_id0, sigma_scale, want_K, want_trajectories, linearize_dt_sq, u_scale,
+                      min_steps, w_tol, angle_tol, filter, want_estimates):
+    """``tsat_tvlqr_ensemble_filtered`` or ``tsat_tvlqr_ensemble_model_filtered`` (``name``), ``filtering`` the function that makes
+    the call's (options, X_hat, filt_final)"""
     lib, head, tail, out = _ensemble_call(solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, noise_id0, sigma_scale, want_K,
                                           want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol)
     T, M = out["stats"].shape
@@ -563,13 +574,13 @@ def attitude_ensemble_filtered(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, 
     if sat is not None:
         lo, hi = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in sat)
     so, sensor = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
-    fo, Xh, ff = _filtering(T, M, batch.N, filter, want_estimates)
+    fo, Xh, ff = filtering(T, M, batch.N, filter, want_estimates)
     ncl = np.zeros((T, M), dtype=np.int32)
     d = _abi.as_dp
-    rc = lib.tsat_tvlqr_ensemble_filtered(*head, d(plant), d(lo), d(hi), *tail, _abi.as_ip(ncl), d(Rtab), float(gm), C.byref(so), d(sensor),
-                                          C.byref(fo), d(Xh), d(ff))
+    rc = getattr(lib, name)(*head, d(plant), d(lo), d(hi), *tail, _abi.as_ip(ncl), d(Rtab), float(gm), C.byref(so), d(sensor),
+                            C.byref(fo), d(Xh), d(ff))
     if rc != 0:
-        raise RuntimeError(f"tsat_tvlqr_ensemble_filtered failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
+        raise RuntimeError(f"{name} failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
     return dict(out, n_clipped=ncl, X_hat=Xh, filt_final=ff)
 
 
@@ -586,6 +597,68 @@ def attitude_ensemble_pd_filtered(solver, batch: SlewBatch, x0_sim, kd, kp, nois
     T, M = batch.T, x0.shape[1]
     sensing = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
     fo, Xh, ff = _filtering(T, M, batch.N, filter, want_estimates)
+    out = _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
+                   want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing, filtering=(fo, Xh, ff))
+    return dict(out, X_hat=Xh, filt_final=ff)
+
+
+MODEL_FILTER_W = 12
+
+
+def model_filter_options(sigma_w, sigma_g, sigma_a, sigma_v=0.0, sigma_u=0.0, p0_att=None, p0_bias=0.0):
+    """The ``tsat_model_filter_options`` of the model-filtered ensembles: what the nine-state multiplicative EKF assumes, all
+    standard deviations — un-modelled angular acceleration ``sigma_w`` (rad/s^2; it has no default: it has to cover what the
+    filter's model leaves out — inertia and actuator mismatch, residual dipole, gravity gradient, plant noise), gyro measurement
+    noise ``sigma_g`` (rad/s, > 0), attitude measurement noise ``sigma_a`` (rad, > 0), attitude process noise ``sigma_v`` (rad/s),
+    bias random walk per knot ``sigma_u`` (rad/s), initial attitude ``p0_att`` (rad; None: ``sigma_a``) and initial bias
+    ``p0_bias`` (rad/s)."""
+    fo = _abi.ModelFilterOptions()
+    _abi.load().tsat_model_filter_default_options(C.byref(fo))
+    fo.sigma_w, fo.sigma_g, fo.sigma_a, fo.sigma_v, fo.sigma_u = float(sigma_w), float(sigma_g), float(sigma_a), float(sigma_v), float(sigma_u)
+    fo.p0_att, fo.p0_bias = float(sigma_a if p0_att is None else p0_att), float(p0_bias)
+    if min(fo.sigma_w, fo.sigma_v, fo.sigma_u, fo.p0_att, fo.p0_bias) < 0.0 or not fo.sigma_a > 0.0 or not fo.sigma_g > 0.0:
+        raise ValueError("filter levels must not be negative, and sigma_a and sigma_g must be positive")
+    if not all(np.isfinite([fo.sigma_w, fo.sigma_v, fo.sigma_u, fo.sigma_a, fo.sigma_g, fo.p0_att, fo.p0_bias])):
+        raise ValueError("filter levels must be finite")
+    return fo
+
+
+def _model_filtering(T, M, N, filter, want_estimates):
+    """(ModelFilterOptions, X_hat (T, M, N, 7) or None, filt_final (T, M, 12)) of a model-filtered call"""
+    if not isinstance(filter, _abi.ModelFilterOptions):
+        raise ValueError("filter must come from model_filter_options(): sigma_w has no default")
+    return filter, (np.empty((T, M, N, 7)) if want_estimates else None), np.empty((T, M, MODEL_FILTER_W))
+
+
+def attitude_ensemble_model_filtered(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant=None, Rtab=None, gm=0.0,
+                                     sat=None, sensor=None, sigma_gyro=0.0, sigma_att=0.0, sigma_mag=0.0, latency=0, noise_id0=None,
+                                     sigma_scale=1.0, want_K=False, want_trajectories=False, linearize_dt_sq=True, u_scale=1e-2,
+                                     min_steps=10, w_tol=0.05, angle_tol=0.08727, filter=None, want_estimates=False):
+    """``attitude_ensemble_sensed`` with a MODEL-BASED rate filter between the measurement and the TVLQR feedback
+    (``tsat_tvlqr_ensemble_model_filtered``): nine states — attitude error, body rate and gyro bias —, rate and attitude propagated
+    by the model's plant under the command the law has just issued, the gyro and the attitude sensor as measurements; the recursion
+    is in include/tortoise_hip.h. Unlike ``attitude_ensemble_filtered`` it smooths white gyro noise. At ``latency`` 1 the law sees
+    the model prediction across the delay. ``filter`` from ``model_filter_options`` (required: ``sigma_w`` has no default). Returns
+    the dict of ``attitude_ensemble_filtered`` with ``filt_final`` (T, M, 12) = [b^, sqrt(diag P_tt), sqrt(diag P_ww),
+    sqrt(diag P_bb)] after the last update made."""
+    return _tv_filtered_call("tsat_tvlqr_ensemble_model_filtered", _model_filtering, solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed,
+                             plant, Rtab, gm, sat, sensor, sigma_gyro, sigma_att, sigma_mag, latency, noise_id0, sigma_scale, want_K,
+                             want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol, filter, want_estimates)
+
+
+def attitude_ensemble_pd_model_filtered(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X=None, U=None, plant=None, Rtab=None,
+                                        gm=0.0, sat=None, limit_mode=0, x0_nom=None, sensor=None, sigma_gyro=0.0, sigma_att=0.0,
+                                        sigma_mag=0.0, latency=0, noise_id0=None, want_trajectories=False, sigma_scale=1.0, u_scale=1e-2,
+                                        min_steps=10, w_tol=0.05, angle_tol=0.08727, filter=None, want_estimates=False):
+    """``attitude_ensemble_pd_sensed`` with the filter of ``attitude_ensemble_model_filtered`` between (w_m, q_m) and the law
+    (``tsat_pd_ensemble_model_filtered``); the magnetometer reading b_m is not filtered. Returns the dict of
+    ``attitude_ensemble_pd_sensed`` plus ``X_hat`` and ``filt_final`` as there."""
+    x0 = np.asarray(x0_sim)
+    if x0.ndim != 3:
+        raise ValueError("x0_sim must be (T, M, 7)")
+    T, M = batch.T, x0.shape[1]
+    sensing = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
+    fo, Xh, ff = _model_filtering(T, M, batch.N, filter, want_estimates)
     out = _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
                    want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing, filtering=(fo, Xh, ff))
     return dict(out, X_hat=Xh, filt_final=ff)
