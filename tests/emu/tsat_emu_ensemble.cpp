@@ -37,11 +37,8 @@ static int run_emu_ensemble(const tsat_tvlqr_options* o, int64_t T, int64_t n_bt
   std::vector<tsat_tvlqr_stats> nom((size_t)T);
   DispArgs<double> d;
   EnsArgs<double>& a = d.e;
-  a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.us = o->u_scale;
-  fill_ens_options(*o, a);
-  a.P = P.data(); a.BT = BT.data(); a.bidx = bidx.data(); a.nk = n_knots; a.XUR = XUR.data(); a.KD = KD.data(); a.X0 = x0_sim;
-  a.nid0 = (const long long*)noise_id0;
-  a.XS = X_sim; a.stats = stats; a.stats_nom = nom.data();
+  a = ens_args<EnsArgs<double>>(*o, T, M, P.data(), BT.data(), bidx.data(), n_knots, XUR.data(), KD.data(), x0_sim,
+                                (const long long*)noise_id0, X_sim, stats, nom.data());
   d.PL = PL.data(); d.Mp = Mp; d.SAT = SAT.data(); d.nclip = n_clipped;
   const int cls = inertia_class(T, Jmat);
   tsat_emu::for_each_wave((int)T * nw, [&](int i) {

@@ -7,19 +7,6 @@
 #include "tsat_emu_sensed.cpp"
 #include "../../tortoisesat.jl_amd/csrc/tsat_filtered.hpp"
 
-namespace {
-
-FiltArgs<double> filt_args(const tsat_filter_options* f, const SensArgs<double>& sa, const EnsArgs<double>& e, double* X_hat,
-                           double* filt_final) {
-  FiltArgs<double> a;
-  a.s = sa; a.P = e.P; a.nk = e.nk; a.M = e.M; a.N = e.N;
-  a.sv = f->sigma_v; a.su = f->sigma_u; a.sa = f->sigma_a; a.p0a = f->p0_att; a.p0b = f->p0_bias;
-  a.XH = X_hat; a.FF = filt_final;
-  return a;
-}
-
-}  // namespace
-
 // arguments as tsat_tvlqr_ensemble_filtered (include/tortoise_hip.h) without the handle, with K_lqr as an INPUT before `stats`
 extern "C" int emu_tvlqr_ensemble_filtered(const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
                                            const double* U, const double* xf, const double* Btab, const int32_t* btab_idx,
@@ -59,10 +46,11 @@ extern "C" int emu_tvlqr_ensemble_filtered(const tsat_tvlqr_options* o, int64_t 
   if (X_hat) std::memset(X_hat, 0, sizeof(double) * (size_t)T * M * N * 7);
   std::vector<tsat_tvlqr_stats> nom((size_t)T);
   FilteredTvArgs<double> fa;
-  ens_args(fa.g.d.e, o, T, M, P.data(), BT.data(), bidx.data(), n_knots, XUR.data(), KD.data(), x0_sim, noise_id0, X_sim, stats, nom.data());
+  fa.g.d.e = ens_args<EnsArgs<double>>(*o, T, M, P.data(), BT.data(), bidx.data(), n_knots, XUR.data(), KD.data(), x0_sim,
+                                       (const long long*)noise_id0, X_sim, stats, nom.data());
   fa.g.d.PL = cm.PL.data(); fa.g.d.Mp = Mp; fa.g.d.SAT = cm.SAT.data(); fa.g.d.nclip = n_clipped;
   fa.g.GT = Rtab ? cm.GT.data() : nullptr;
-  fa.f = filt_args(f, sens_args(s, o, cm.SN.data(), Mp), fa.g.d.e, X_hat, filt_final);
+  fa.f = filt_args(*f, sens_args(*s, *o, cm.SN.data(), Mp), fa.g.d.e, X_hat, filt_final);
   tsat_emu::for_each_wave((int)T * nw, [&](int i) {
     const int t = i / nw, w = i - t * nw;
     tsat_emu::run_wave(64, [&]() { fa.g.GT ? filtered_tv_gg_wave<double>(fa, t, w) : filtered_tv_wave<double>(fa, t, w); });   // no LDS
@@ -116,11 +104,11 @@ extern "C" int emu_pd_ensemble_filtered(const tsat_tvlqr_options* o, int64_t T, 
   std::vector<tsat_tvlqr_stats> nom(Tn);
   FilteredPdArgs<double> fa;
   PdArgs<double>& pa = fa.p;
-  ens_args(pa.d.e, o, T, M, P.data(), BT.data(), bidx.data(), n_knots, X ? XUR.data() : nullptr, nullptr, x0_sim, noise_id0, X_sim, stats,
-           nom.data());
+  pa.d.e = ens_args<EnsArgs<double>>(*o, T, M, P.data(), BT.data(), bidx.data(), n_knots, X ? XUR.data() : nullptr, nullptr, x0_sim,
+                                     (const long long*)noise_id0, X_sim, stats, nom.data());
   pa.d.PL = cm.PL.data(); pa.d.Mp = Mp; pa.d.SAT = cm.SAT.data(); pa.d.nclip = n_clipped;
   pa.GT = Rtab ? cm.GT.data() : nullptr; pa.GAIN = gain.data(); pa.X0N = x0n.data(); pa.feedforward = feedforward; pa.limit_mode = limit_mode;
-  fa.f = filt_args(f, sens_args(s, o, cm.SN.data(), Mp), pa.d.e, X_hat, filt_final);
+  fa.f = filt_args(*f, sens_args(*s, *o, cm.SN.data(), Mp), pa.d.e, X_hat, filt_final);
   tsat_emu::for_each_wave((int)T * nw, [&](int i) {
     const int t = i / nw, w = i - t * nw;
     tsat_emu::run_wave(64, [&]() { pa.GT ? filtered_pd_gg_wave<double>(fa, t, w) : filtered_pd_wave<double>(fa, t, w); });   // no LDS

@@ -42,12 +42,7 @@ extern "C" int emu_pd_ensemble(const tsat_tvlqr_options* o, int64_t T, int64_t n
     pack_xu_records<double>(T, N, X, U, XUR.data());
   }
   if (!plant) {
-    model.assign(nS * TSAT_PLANT_W, 0.0);
-    for (size_t e = 0; e < nS; ++e) {
-      double* pl = model.data() + e * TSAT_PLANT_W;
-      for (int i = 0; i < 9; ++i) pl[i] = Jmat[9 * (e / M) + i];
-      pl[9] = pl[13] = pl[17] = 1.0;
-    }
+    model = model_plants(Jmat, Tn, M);
     plant = model.data();
   }
   for (int64_t e = 0; e < T * (int64_t)(M + 1); ++e) dispersed_pack<double>(plant, P.data(), o->u_scale, PL.data(), T, M, Mp, e);
@@ -59,12 +54,8 @@ extern "C" int emu_pd_ensemble(const tsat_tvlqr_options* o, int64_t T, int64_t n
   if (X_sim) std::memset(X_sim, 0, sizeof(double) * nS * N * 7);
   std::vector<tsat_tvlqr_stats> nom(Tn);
   PdArgs<double> pa;
-  EnsArgs<double>& a = pa.d.e;
-  a.T = (int)T; a.N = N; a.n_tab = n_tab; a.M = M; a.us = o->u_scale;
-  fill_ens_options(*o, a);
-  a.P = P.data(); a.BT = BT.data(); a.bidx = bidx.data(); a.nk = n_knots; a.XUR = X ? XUR.data() : nullptr; a.KD = nullptr; a.X0 = x0_sim;
-  a.nid0 = (const long long*)noise_id0;
-  a.XS = X_sim; a.stats = stats; a.stats_nom = nom.data();
+  pa.d.e = ens_args<EnsArgs<double>>(*o, T, M, P.data(), BT.data(), bidx.data(), n_knots, X ? XUR.data() : nullptr, nullptr, x0_sim,
+                                     (const long long*)noise_id0, X_sim, stats, nom.data());
   pa.d.PL = PL.data(); pa.d.Mp = Mp; pa.d.SAT = SAT.data(); pa.d.nclip = n_clipped;
   pa.GT = Rtab ? GT.data() : nullptr; pa.GAIN = gain.data(); pa.X0N = x0n.data(); pa.feedforward = feedforward; pa.limit_mode = limit_mode;
   tsat_emu::for_each_wave((int)T * nw, [&](int i) {

@@ -16,15 +16,10 @@ struct Common {
   void fill(const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* P, const double* Jmat, const double* plant,
             const double* sat_lo, const double* sat_hi, const double* Rtab, double gm, const double* sensor) {
     const int Mp = ensemble_waves(M) * WAVE;
-    const size_t Tn = (size_t)T, nS = Tn * (size_t)M;
+    const size_t Tn = (size_t)T;
     SAT = pack_limits(sat_lo, sat_hi, T);
     if (!plant) {
-      model.assign(nS * TSAT_PLANT_W, 0.0);
-      for (size_t e = 0; e < nS; ++e) {
-        double* pl = model.data() + e * TSAT_PLANT_W;
-        for (int i = 0; i < 9; ++i) pl[i] = Jmat[9 * (e / M) + i];
-        pl[9] = pl[13] = pl[17] = 1.0;
-      }
+      model = model_plants(Jmat, Tn, M);
       plant = model.data();
     }
     PL.assign(Tn * PLW * Mp, 0.0);
@@ -38,23 +33,6 @@ struct Common {
     for (int64_t e = 0; e < T * (int64_t)Mp; ++e) sensed_pack<double>(sensor, SN.data(), T, M, Mp, e);
   }
 };
-
-SensArgs<double> sens_args(const tsat_sensor_options* s, const tsat_tvlqr_options* o, const double* SN, int Mp) {
-  SensArgs<double> a;
-  a.SN = SN; a.Mp = Mp; a.sgy = s->sigma_gyro; a.sat = s->sigma_att; a.smg = s->sigma_mag; a.latency = s->latency;
-  a.k0 = (unsigned)(o->noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o->noise_seed >> 32);
-  return a;
-}
-
-void ens_args(EnsArgs<double>& a, const tsat_tvlqr_options* o, int64_t T, int32_t M, const double* P, const double* BT, const int* bidx,
-              const int32_t* n_knots, const double* XUR, const double* KD, const double* x0_sim, const int64_t* noise_id0, double* X_sim,
-              tsat_tvlqr_stats* stats, tsat_tvlqr_stats* nom) {
-  a.T = (int)T; a.N = o->n_knots; a.n_tab = o->n_tab; a.M = M; a.us = o->u_scale;
-  fill_ens_options(*o, a);
-  a.P = P; a.BT = BT; a.bidx = bidx; a.nk = n_knots; a.XUR = XUR; a.KD = KD; a.X0 = x0_sim;
-  a.nid0 = (const long long*)noise_id0;
-  a.XS = X_sim; a.stats = stats; a.stats_nom = nom;
-}
 
 }  // namespace
 
@@ -92,10 +70,11 @@ extern "C" int emu_tvlqr_ensemble_sensed(const tsat_tvlqr_options* o, int64_t T,
   if (X_sim) std::memset(X_sim, 0, sizeof(double) * (size_t)T * M * N * 7);
   std::vector<tsat_tvlqr_stats> nom((size_t)T);
   SensedTvArgs<double> sa;
-  ens_args(sa.g.d.e, o, T, M, P.data(), BT.data(), bidx.data(), n_knots, XUR.data(), KD.data(), x0_sim, noise_id0, X_sim, stats, nom.data());
+  sa.g.d.e = ens_args<EnsArgs<double>>(*o, T, M, P.data(), BT.data(), bidx.data(), n_knots, XUR.data(), KD.data(), x0_sim,
+                                       (const long long*)noise_id0, X_sim, stats, nom.data());
   sa.g.d.PL = cm.PL.data(); sa.g.d.Mp = Mp; sa.g.d.SAT = cm.SAT.data(); sa.g.d.nclip = n_clipped;
   sa.g.GT = Rtab ? cm.GT.data() : nullptr;
-  sa.s = sens_args(s, o, cm.SN.data(), Mp);
+  sa.s = sens_args(*s, *o, cm.SN.data(), Mp);
   tsat_emu::for_each_wave((int)T * nw, [&](int i) {
     const int t = i / nw, w = i - t * nw;
     tsat_emu::run_wave(64, [&]() { sa.g.GT ? sensed_tv_gg_wave<double>(sa, t, w) : sensed_tv_wave<double>(sa, t, w); });   // no LDS
@@ -142,11 +121,11 @@ extern "C" int emu_pd_ensemble_sensed(const tsat_tvlqr_options* o, int64_t T, in
   std::vector<tsat_tvlqr_stats> nom(Tn);
   SensedPdArgs<double> sa;
   PdArgs<double>& pa = sa.p;
-  ens_args(pa.d.e, o, T, M, P.data(), BT.data(), bidx.data(), n_knots, X ? XUR.data() : nullptr, nullptr, x0_sim, noise_id0, X_sim, stats,
-           nom.data());
+  pa.d.e = ens_args<EnsArgs<double>>(*o, T, M, P.data(), BT.data(), bidx.data(), n_knots, X ? XUR.data() : nullptr, nullptr, x0_sim,
+                                     (const long long*)noise_id0, X_sim, stats, nom.data());
   pa.d.PL = cm.PL.data(); pa.d.Mp = Mp; pa.d.SAT = cm.SAT.data(); pa.d.nclip = n_clipped;
   pa.GT = Rtab ? cm.GT.data() : nullptr; pa.GAIN = gain.data(); pa.X0N = x0n.data(); pa.feedforward = feedforward; pa.limit_mode = limit_mode;
-  sa.s = sens_args(s, o, cm.SN.data(), Mp);
+  sa.s = sens_args(*s, *o, cm.SN.data(), Mp);
   tsat_emu::for_each_wave((int)T * nw, [&](int i) {
     const int t = i / nw, w = i - t * nw;
     tsat_emu::run_wave(64, [&]() { pa.GT ? sensed_pd_gg_wave<double>(sa, t, w) : sensed_pd_wave<double>(sa, t, w); });   // no LDS

@@ -66,6 +66,15 @@ struct FilteredPdArgs {
   FiltArgs<real> f;
 };
 
+// the launch block of the filter around that of its sensor (host)
+inline FiltArgs<double> filt_args(const tsat_filter_options& f, const SensArgs<double>& sa, const EnsArgs<double>& e, double* XH, double* FF) {
+  FiltArgs<double> a;
+  a.s = sa; a.P = e.P; a.nk = e.nk; a.M = e.M; a.N = e.N;
+  a.sv = f.sigma_v; a.su = f.sigma_u; a.sa = f.sigma_a; a.p0a = f.p0_att; a.p0b = f.p0_bias;
+  a.XH = XH; a.FF = FF;
+  return a;
+}
+
 // the flat record
 template <typename real>
 struct FilterState {

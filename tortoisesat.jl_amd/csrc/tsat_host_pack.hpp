@@ -284,6 +284,34 @@ inline void fill_ens_options(const tsat_tvlqr_options& o, Ens& e) {
   e.sg = o.sigma_gyro; e.sa = o.sigma_att; e.fa = o.field_amp;
 }
 
+// the ensemble launch block (EnsArgs of tsat_ensemble.hpp) from the options of a call and its arrays: the entry points and the
+// emulator drivers fill it here
+template <typename Ens>
+inline Ens ens_args(const tsat_tvlqr_options& o, int64_t T, int32_t M, const double* P, const double* BT, const int* bidx, const int* nk,
+                    const double* XUR, const double* KD, const double* X0, const long long* nid0, double* XS, tsat_tvlqr_stats* stats,
+                    tsat_tvlqr_stats* stats_nom) {
+  Ens a;
+  a.T = (int)T; a.N = o.n_knots; a.n_tab = o.n_tab; a.M = M; a.us = o.u_scale;
+  fill_ens_options(o, a);
+  a.P = P; a.BT = BT; a.bidx = bidx; a.nk = nk; a.XUR = XUR; a.KD = KD; a.X0 = X0;
+  a.nid0 = nid0;
+  a.XS = XS; a.stats = stats; a.stats_nom = stats_nom;
+  return a;
+}
+
+// the plant array of a dispersed call in which every realisation flies the model's plant: (Jmat, G = I, m_res = 0); the pack
+// reads the upper triangle of Jp
+inline std::vector<double> model_plants(const double* Jmat, size_t Tn, int M) {
+  std::vector<double> model(Tn * (size_t)M * TSAT_PLANT_W, 0.0);
+  for (size_t t = 0; t < Tn; ++t)
+    for (int m = 0; m < M; ++m) {
+      double* pl = model.data() + (t * M + m) * TSAT_PLANT_W;
+      for (int i = 0; i < 9; ++i) pl[i] = Jmat[9 * t + i];
+      pl[9] = pl[13] = pl[17] = 1.0;
+    }
+  return model;
+}
+
 // what tsat_mpc_run_dispersed rejects beyond tsat_mpc_run's own checks: "" or the reason (plant 21 x T or null, limits 3 x T or null)
 inline std::string check_mpc_dispersed(const tsat_tvlqr_options& po, int32_t n_steps, int64_t step0, const double* plant,
                                        const double* sat_lo, const double* sat_hi, int64_t T) {

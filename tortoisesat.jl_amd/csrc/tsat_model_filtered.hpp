@@ -73,6 +73,16 @@ struct ModelFilteredPdArgs {
   ModelFiltArgs<real> f;
 };
 
+// the launch block of the nine-state filter around that of its sensor (host); it reads the slew's constants and field rows itself
+inline ModelFiltArgs<double> model_filt_args(const tsat_model_filter_options& f, const SensArgs<double>& sa, const EnsArgs<double>& e,
+                                             double* XH, double* FF) {
+  ModelFiltArgs<double> a;
+  a.s = sa; a.P = e.P; a.BT = e.BT; a.bidx = e.bidx; a.nk = e.nk; a.M = e.M; a.N = e.N; a.n_tab = e.n_tab; a.us = e.us;
+  a.sv = f.sigma_v; a.sw = f.sigma_w; a.su = f.sigma_u; a.sa = f.sigma_a; a.sg = f.sigma_g; a.p0a = f.p0_att; a.p0b = f.p0_bias;
+  a.XH = XH; a.FF = FF;
+  return a;
+}
+
 // the flat record
 template <typename real>
 struct ModelFilterState {

@@ -48,6 +48,14 @@ struct SensedPdArgs {
   SensArgs<real> s;
 };
 
+// the launch block of the sensor from the options of both calls (host)
+inline SensArgs<double> sens_args(const tsat_sensor_options& s, const tsat_tvlqr_options& o, const double* SN, int Mp) {
+  SensArgs<double> a;
+  a.SN = SN; a.Mp = Mp; a.sgy = s.sigma_gyro; a.sat = s.sigma_att; a.smg = s.sigma_mag; a.latency = s.latency;
+  a.k0 = (unsigned)(o.noise_seed & 0xFFFFFFFFull); a.k1 = (unsigned)(o.noise_seed >> 32);
+  return a;
+}
+
 // sensor biases 9 x M x T (or null: zeros) -> [T][SNW][Mp]; thread e of the pack grid: slot e % Mp of slew e / Mp
 template <typename real>
 TSAT_DEV void sensed_pack(const real* sensor, real* SN, int64_t T, int M, int Mp, int64_t e) {
