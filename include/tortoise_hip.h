@@ -213,6 +213,10 @@ typedef struct tsat_tvlqr_options {
  *   gyro   = sigma_gyro (z(w00,w01), z'(w00,w01), z(w02,w03))
  *   att    = sigma_att  (z'(w02,w03), z(w10,w11), z'(w10,w11))
  *   field  = field_amp  (U(w12), U(w13), U(w20))
+ * The plant turns the normalised attitude by the rotation vector att: q (x) [cos(th/2); att * (th == 0 ? 1/2 : sin(th/2)/th)],
+ * th = |att| as computed (a triple whose squares underflow counts as zero). sigma_att = 0 — "gyro noise only", or a wrapper's
+ * sigma_scale = 0 — is therefore no rotation, and all three levels zero is the noise-free plant up to the one extra
+ * normalisation of the quaternion, where the reference's r_noise = q_noise / th_noise (src/simulator.jl:12) is 0/0.
  * id = noise_id[t] (NULL: t), so a sweep draws the same noise however it is sharded or chunked. The reference draws
  * from Julia's global generator inside `simulator`; any generator is as faithful, this one is reproducible. */
 
@@ -236,6 +240,8 @@ void tsat_tvlqr_default_options(tsat_tvlqr_options* o);
  *   x0_sim 7xT                   perturbed initial state x0_lqr (src/TortoiseSat.jl:227-234)
  *   noise 9x4x(N-1)xT or NULL    per step and RK4 stage: gyro noise(3), attitude-noise rotation vector(3), field
  *                                noise(3) — the values the reference draws inside `simulator` (src/simulator.jl:5,10,22);
+ *                                an attitude triple of norm zero (as computed: squares that underflow included) is no
+ *                                rotation, the rule stated at noise_mode = 1 above; zeros are valid values;
  *                                NULL = noise-free plant (`gain_simulator`)
  *   X_sim 7xNxT, U_sim 3x(N-1)xT, K_lqr 3x6x(N-1)xT (each may be NULL: only what is asked for travels back), stats T   outputs
  *   n_knots T or NULL            per-trajectory horizons as for tsat_batch_knots (`t_total[i]`, src/monte_carlo.jl:145):

@@ -926,7 +926,7 @@ static void sim_dyn(const double x[7], const double u[3], const double b[3], con
   if (nz) {
     for (int i = 0; i < 3; ++i) w[i] += nz[i];
     const double th = std::sqrt(nz[3] * nz[3] + nz[4] * nz[4] + nz[5] * nz[5]);
-    const double sh = std::sin(th / 2) / th;
+    const double sh = (th == 0) ? 0.5 : std::sin(th / 2) / th;   // no rotation: the identity, not 0/0
     double dq[4] = {std::cos(th / 2), nz[3] * sh, nz[4] * sh, nz[5] * sh}, qn[4];
     qmult<double>(q, dq, qn);
     for (int i = 0; i < 4; ++i) q[i] = qn[i];

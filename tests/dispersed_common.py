@@ -36,7 +36,7 @@ def _noisy(ol, x, b, nz):
         return x, b
     q = x[3:7] / math.sqrt(float(x[3:7] @ x[3:7]))
     th = math.sqrt(float(nz[3:6] @ nz[3:6]))
-    dq = np.r_[math.cos(th / 2), nz[3:6] * (math.sin(th / 2) / th)]
+    dq = np.r_[math.cos(th / 2), nz[3:6] * (0.5 if th == 0.0 else math.sin(th / 2) / th)]
     return np.r_[x[:3] + nz[:3], ol.qmult(q, dq)], b + nz[6:9]
 
 

@@ -2528,7 +2528,8 @@ TSAT_DEV void dyn_sim_h(const Traj<real>& tr, const real x[7], const real us[3],
     const real q0 = x[3] * rn, q1 = x[4] * rn, q2 = x[5] * rn, q3 = x[6] * rn;
     const real n0 = nz[3], n1 = nz[4], n2 = nz[5];
     const real th = sqrt_(n0 * n0 + n1 * n1 + n2 * n2);
-    const real sh = sin_((real)0.5 * th) / th, ch = cos_((real)0.5 * th);
+    const real sr = sin_((real)0.5 * th) / th, ch = cos_((real)0.5 * th);
+    const real sh = (th == 0) ? (real)0.5 : sr;               // a select, as tsat_sensed.hpp: no rotation is the identity, not 0/0
     const real d1 = n0 * sh, d2 = n1 * sh, d3 = n2 * sh;
     for (int i = 0; i < 3; ++i) { xx[i] = x[i] + nz[i]; bb[i] = b[i] + nz[6 + i]; }
     xx[3] = q0 * ch - (q1 * d1 + q2 * d2 + q3 * d3);          // qmult(q, [cos; r sin])
