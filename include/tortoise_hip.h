@@ -821,6 +821,43 @@ int  tsat_mpc_run_held_filtered(tsat_handle* h, const tsat_options* o, const tsa
                        const tsat_sensor_options* s, const double* sensor, double* Y_hist,
                        const tsat_filter_options* f, const double* filt_init, double* filt_state, double* filt_final);
 
+/* tsat_mpc_run_held_sensed BEHIND THE NINE-STATE FILTER of tsat_tvlqr_ensemble_model_filtered: the loop of tsat_mpc_run_held_sensed
+ * with one change — what the controller is handed. The raw measurements m_s are the parent's, and so are the blocks and the j = 0
+ * rule, the clip, the dispersed RK4 step, the gravity rows (Rtab NULL iff gm == 0), the table clock, the shift, n_clipped,
+ * tsat_mpc_tally, the statistic on the TRUE state and the true state written back at the end of the call. The recursion written out
+ * at tsat_model_filter_options (`first`, `predict`, `update`, h = dt[t]) runs over the samples, s counted FROM THE CALL whatever
+ * step0 is. The filter's model is trajectory t's parameter record: Jmat and u_scale, no actuator matrix, no residual dipole, no
+ * gravity-gradient term — never the dispersed `plant`. In predict(u_s), u is the limited command of step s as U_hist[s] holds it, and
+ * the field rows are the three rows the plant's own step s read (c = 0, 1/2, 1 at the table clock step s had).
+ *   latency 0: s = 0: first(m_0); s >= 1: predict(u_{s-1}), then update(m_s); y_s = (w^, q^)
+ *   latency 1: y_0 from first(m_0); s = 1: m_0 arrives a second time and makes no update, then predict(u_0); s >= 2:
+ *              update(m_{s-1}), then predict(u_{s-1}); for s >= 1, y_s = (w-, q-): the model prediction across the delay
+ * The solve's x0 at a block start, the state U_j + K_j dx acts on, and Y_hist[s] all read y_s.
+ * After the last control step the filter makes ONE MORE predict(u_{n_steps-1}) with that step's rows and no update, at either latency:
+ * the record a call leaves is the prior for x_{n_steps}, the state written back to the batch.
+ * State between calls: one flat record of TSAT_MODEL_FILTER_STATE_W = 58 values per trajectory: q^ 4, w^ 3, b^ 3, the command of the
+ * last predict 3, then the covariance by blocks A (theta theta) 6, W (w w) 6, D (b b) 6 as upper triangles 00 01 02 11 12 22 and
+ * X (theta w) 9, B (theta b) 9, Y (w b) 9 row-major.
+ *   filt_init   58 x T or NULL   NULL: the filter starts on the call's m_0 (`first`) and so restarts with every call. Given: the
+ *                                record of trajectory t is loaded and sample 0 makes update(m_0) on it in place of first(m_0);
+ *                                nothing else differs
+ *   filt_state  58 x T out or NULL   the record the call leaves
+ *   filt_final  12 x T out or NULL   b^, sqrt(diag P_tt), sqrt(diag P_ww), sqrt(diag P_bb) of that record (TSAT_MODEL_FILTER_W)
+ * At latency 0 a continuation equals one longer run BIT FOR BIT when step0 = the steps made, there is no upload, filt_init = the
+ * previous call's filt_state, and the first call's n_steps is a multiple of R. Latency 1 STILL RESTARTS THE SENSOR'S MEMORY with
+ * every call (the first step of the second call sees its own measurement), filt_init or not: such a continuation is not the longer run.
+ * f == NULL is tsat_mpc_run_held_sensed, byte for byte (it is dispatched there); the three filter arrays must then be NULL.
+ * Rejected with -1 (text in tsat_last_error; nothing is launched and no workspace grows): a non-finite or negative filter option,
+ * sigma_a == 0, sigma_g == 0, reserved != 0; f NULL with a filter array non-NULL; a non-finite entry of filt_init; a q^ of zero norm
+ * in filt_init (reported with its t); and everything tsat_mpc_run_held_sensed rejects. */
+#define TSAT_MODEL_FILTER_STATE_W 58
+int  tsat_mpc_run_held_model_filtered(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                       int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo, const double* sat_hi,
+                       const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last, tsat_tvlqr_stats* stats,
+                       int32_t* n_clipped, float* solve_ms, const double* Rtab, double gm,
+                       const tsat_sensor_options* s, const double* sensor, double* Y_hist,
+                       const tsat_model_filter_options* f, const double* filt_init, double* filt_state, double* filt_final);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Sweep exchange across GPUs. The reference's Monte-Carlo is a serial loop whose iterations share nothing but the result
  * lists they append to (src/monte_carlo.jl:52-66, 199-235; src/paper_images/heatmap.jl:114-243). Here each rank — one

@@ -96,6 +96,8 @@ struct TrueState {
   template <typename real>
   TSAT_DEV void commanded(int, const real*) {}                 // the command of knot k on its way to plant.actuate: not used
   template <typename real>
+  TSAT_DEV void flown(const real*, const real*, const real*, const real*) {}   // mpc_held_block's hook (tsat_mpc_held.hpp): not used
+  template <typename real>
   TSAT_DEV void state(long long, int, bool, const real x[7], real y[7]) {
     for (int i = 0; i < 7; ++i) y[i] = x[i];
   }

@@ -19,6 +19,7 @@
 #include "tsat_gg.hpp"
 #include "tsat_mpc_sensed.hpp"
 #include "tsat_mpc_filtered.hpp"
+#include "tsat_mpc_model_filtered.hpp"
 
 using namespace tsat;
 
@@ -48,6 +49,9 @@ hipError_t tsat_launch_mpc_sensed(const MpcSensedArgs<double>& a, int error_stat
 // tsat_mpc_run_held_filtered (tsat_kernels_mpc_filtered.hip)
 hipError_t tsat_launch_mpc_filtered_pack(const MpcFilteredArgs<double>& a, const double* sensor, int given, hipStream_t stream);
 hipError_t tsat_launch_mpc_filtered(const MpcFilteredArgs<double>& a, int error_state, hipStream_t stream);
+// tsat_mpc_run_held_model_filtered (tsat_kernels_mpc_model_filtered.hip)
+hipError_t tsat_launch_mpc_model_filtered_pack(const MpcModelFilteredArgs<double>& a, const double* sensor, int given, hipStream_t stream);
+hipError_t tsat_launch_mpc_model_filtered(const MpcModelFilteredArgs<double>& a, int error_state, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -145,6 +149,7 @@ struct tsat_handle {
          WS_MPCS_XT, WS_MPCS_SN, WS_MPCS_IN, WS_MPCS_Y,   // tsat_mpc_run_held_sensed: true state + last measurement [14][T], biases
                                // [9][T], the uploaded sensor array, Y_hist
          WS_MPCF_FL,           // tsat_mpc_run_held_filtered: the filter's records [31][T]
+         WS_MPCMF_FL,          // tsat_mpc_run_held_model_filtered: the nine-state filter's records [58][T]
          WS_COUNT };
   void* ws[WS_COUNT] = {};
   size_t ws_bytes[WS_COUNT] = {};
@@ -622,7 +627,8 @@ namespace {
 // and of tsat_mpc_run_held (replan_every >= 1: a solve, the lane-per-trajectory hold and the plan shift per block); with
 // `gravity` the hold is the one of tsat_mpc_run_held_gg (Rtab [n_btab][n_tab][3] of the resident batch, gm); with `sc` the hold of
 // tsat_mpc_run_held_sensed, which reads measurements (tsat_mpc_sensed.hpp) — through the gravity rows when `gravity`; with `fc`
-// besides, the hold of tsat_mpc_run_held_filtered, which reads the filter's estimates (tsat_mpc_filtered.hpp)
+// besides, the hold of tsat_mpc_run_held_filtered, which reads the filter's estimates (tsat_mpc_filtered.hpp); with `mc` besides
+// `sc`, the hold of tsat_mpc_run_held_model_filtered, which reads the nine-state filter's (tsat_mpc_model_filtered.hpp)
 struct SensedCall {
   const tsat_sensor_options* s;
   const double* sensor;      // 9 x T or null
@@ -634,11 +640,18 @@ struct FilteredCall {
   double* filt_state;        // 31 x T or null
   double* filt_final;        // 9 x T or null
 };
+struct ModelFilteredCall {
+  const tsat_model_filter_options* f;
+  const double* filt_init;   // 58 x T or null
+  double* filt_state;        // 58 x T or null
+  double* filt_final;        // 12 x T or null
+};
 int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps,
                    int64_t step0, int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo,
                    const double* sat_hi, const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last,
                    tsat_tvlqr_stats* stats, int32_t* n_clipped, float* solve_ms, bool gravity = false, const double* Rtab = nullptr,
-                   double gm = 0.0, const SensedCall* sc = nullptr, const FilteredCall* fc = nullptr) {
+                   double gm = 0.0, const SensedCall* sc = nullptr, const FilteredCall* fc = nullptr,
+                   const ModelFilteredCall* mc = nullptr) {
   if (!h || !o || !po) return -1;
   const bool held = replan_every != 0;
   if (!h->uploaded) return fail(h, -1, "tsat_batch_upload has not been called");
@@ -659,6 +672,10 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   if (fc) {
     const std::string badf = check_mpc_filtered(fc->f, fc->filt_init, fc->filt_state, fc->filt_final, h->T);
     if (!badf.empty()) return fail(h, -1, badf);
+  }
+  if (mc) {
+    const std::string badm = check_mpc_model_filtered(mc->f, mc->filt_init, mc->filt_state, mc->filt_final, h->T);
+    if (!badm.empty()) return fail(h, -1, badm);
   }
   if (!X_hist || !U_hist) return fail(h, -1, "null array");
   TSAT_HIP(h, hipSetDevice(h->dev));
@@ -693,6 +710,8 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   }
   double* dFL = fc ? (double*)ws_get(h, tsat_handle::WS_MPCF_FL, T * FLW * 8) : nullptr;
   if (fc && !dFL) return fail(h, -10, std::string("device allocation failed in ") + name);
+  double* dMFL = mc ? (double*)ws_get(h, tsat_handle::WS_MPCMF_FL, T * MFLW * 8) : nullptr;
+  if (mc && !dMFL) return fail(h, -10, std::string("device allocation failed in ") + name);
   // the gravity call: the packed rows are the handle's, the raw orbit table lives until the pack has run
   double* dGT = gravity ? tsat_ws_gravity(h, n_rows * 4 * 8) : nullptr;
   struct Raw {
@@ -713,6 +732,11 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   if (fc && fc->filt_init) {
     filt_records_pack(fc->filt_init, flh.data(), (int64_t)T);
     TSAT_HIP(h, hipMemcpy(dFL, flh.data(), flh.size() * 8, hipMemcpyHostToDevice));
+  }
+  std::vector<double> mflh(mc ? T * MFLW : 0);   // the nine-state filter's records, likewise
+  if (mc && mc->filt_init) {
+    model_filt_records_pack(mc->filt_init, mflh.data(), (int64_t)T);
+    TSAT_HIP(h, hipMemcpy(dMFL, mflh.data(), mflh.size() * 8, hipMemcpyHostToDevice));
   }
   TSAT_HIP(h, hipMemsetAsync(dTally, 0, T * 4 * sizeof(long long), h->stream));
   h->mpc_tally_T = (int64_t)T;
@@ -744,6 +768,13 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
     mf.f.s = ms.s; mf.f.P = h->P; mf.f.nk = m.nk; mf.f.M = 1; mf.f.N = h->N;
     mf.f.sv = fc->f->sigma_v; mf.f.su = fc->f->sigma_u; mf.f.sa = fc->f->sigma_a; mf.f.p0a = fc->f->p0_att; mf.f.p0b = fc->f->p0_bias;
   }
+  MpcModelFilteredArgs<double> mm = {};
+  if (mc) {
+    mm.FL = dMFL;
+    mm.f.s = ms.s; mm.f.P = h->P; mm.f.M = 1; mm.f.N = h->N; mm.f.n_tab = h->n_tab; mm.f.us = o->u_scale;
+    mm.f.sv = mc->f->sigma_v; mm.f.sw = mc->f->sigma_w; mm.f.su = mc->f->sigma_u; mm.f.sa = mc->f->sigma_a; mm.f.sg = mc->f->sigma_g;
+    mm.f.p0a = mc->f->p0_att; mm.f.p0b = mc->f->p0_bias;
+  }
   int rc = 0;
   if (hipEventRecord(h->ev0, h->stream) != hipSuccess) rc = -10;
   if (held) {   // the pack, then solve, hold and shift per block queued back to back; the stream orders them
@@ -754,6 +785,9 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
       if (fc) {
         mf.ms = ms;
         if (!rc && tsat_launch_mpc_filtered_pack(mf, dSIn, fc->filt_init != nullptr, h->stream) != hipSuccess) rc = -10;
+      } else if (mc) {
+        mm.ms = ms;
+        if (!rc && tsat_launch_mpc_model_filtered_pack(mm, dSIn, mc->filt_init != nullptr, h->stream) != hipSuccess) rc = -10;
       } else {
         if (!rc && tsat_launch_mpc_sensed_pack(ms, dSIn, h->stream) != hipSuccess) rc = -10;
       }
@@ -765,6 +799,9 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
       if (fc) {        // the hold on the filter's estimates (with or without the gravity rows)
         ms.h = mh; mf.ms = ms;
         if (!rc && tsat_launch_mpc_filtered(mf, o->error_state, h->stream) != hipSuccess) rc = -10;
+      } else if (mc) { // the hold on the nine-state filter's estimates (with or without the gravity rows)
+        ms.h = mh; mm.ms = ms;
+        if (!rc && tsat_launch_mpc_model_filtered(mm, o->error_state, h->stream) != hipSuccess) rc = -10;
       } else if (sc) {        // the hold on measurements (with or without the gravity rows)
         ms.h = mh;
         if (!rc && tsat_launch_mpc_sensed(ms, o->error_state, h->stream) != hipSuccess) rc = -10;
@@ -791,6 +828,10 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   if (fc && (fc->filt_state || fc->filt_final)) {
     TSAT_HIP(h, hipMemcpy(flh.data(), dFL, flh.size() * 8, hipMemcpyDeviceToHost));
     filt_records_unpack(flh.data(), (int64_t)T, fc->filt_state, fc->filt_final);
+  }
+  if (mc && (mc->filt_state || mc->filt_final)) {
+    TSAT_HIP(h, hipMemcpy(mflh.data(), dMFL, mflh.size() * 8, hipMemcpyDeviceToHost));
+    model_filt_records_unpack(mflh.data(), (int64_t)T, mc->filt_state, mc->filt_final);
   }
   return 0;
 }
@@ -850,6 +891,26 @@ int tsat_mpc_run_held_filtered(tsat_handle* h, const tsat_options* o, const tsat
   const FilteredCall fc = {f, filt_init, filt_state, filt_final};
   return mpc_plant_loop(h, "tsat_mpc_run_held_filtered", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id,
                         X_hist, U_hist, stats_last, stats, n_clipped, solve_ms, Rtab != nullptr, Rtab, gm, &sc, &fc);
+}
+
+int tsat_mpc_run_held_model_filtered(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps, int64_t step0,
+                                     int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo,
+                                     const double* sat_hi, const int64_t* noise_id, double* X_hist, double* U_hist,
+                                     tsat_stats* stats_last, tsat_tvlqr_stats* stats, int32_t* n_clipped, float* solve_ms,
+                                     const double* Rtab, double gm, const tsat_sensor_options* s, const double* sensor, double* Y_hist,
+                                     const tsat_model_filter_options* f, const double* filt_init, double* filt_state,
+                                     double* filt_final) {
+  if (!f) {   // the sensed call itself
+    const std::string bad = check_mpc_model_filtered(f, filt_init, filt_state, filt_final, 0);
+    if (!bad.empty()) return fail(h, -1, bad);
+    return tsat_mpc_run_held_sensed(h, o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id, X_hist, U_hist,
+                                    stats_last, stats, n_clipped, solve_ms, Rtab, gm, s, sensor, Y_hist);
+  }
+  if (replan_every < 1) return fail(h, -1, check_mpc_held(replan_every, feedback, 2));
+  const SensedCall sc = {s, sensor, Y_hist};
+  const ModelFilteredCall mc = {f, filt_init, filt_state, filt_final};
+  return mpc_plant_loop(h, "tsat_mpc_run_held_model_filtered", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi,
+                        noise_id, X_hist, U_hist, stats_last, stats, n_clipped, solve_ms, Rtab != nullptr, Rtab, gm, &sc, nullptr, &mc);
 }
 
 int tsat_batch_export_device(tsat_handle* h, void* X_dev, void* U_dev, void* K_dev, void* stats_dev) {

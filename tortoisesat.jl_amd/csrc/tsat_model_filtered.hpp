@@ -42,6 +42,8 @@ namespace tsat {
 
 constexpr int MFLW = 58;                       // q^[4], w^[3], b^[3], u[3], A[6], W[6], D[6], X[9], B[9], Y[9]
 constexpr int MFFW = TSAT_MODEL_FILTER_W;      // filt_final: b^[3], sqrt(diag A)[3], sqrt(diag W)[3], sqrt(diag D)[3]
+// TSAT_MODEL_FILTER_STATE_W is the public header's (include/tortoise_hip.h, next to TSAT_FILTER_STATE_W). The same definition, token
+// for token, stays here as well — which the language allows — because tests/test_model_filtered.py reads it in this file.
 #define TSAT_MODEL_FILTER_STATE_W 58
 static_assert(MFLW == TSAT_MODEL_FILTER_STATE_W, "the record of ModelFilterState");
 
@@ -168,16 +170,21 @@ struct ModelFiltered {
       st.Y[i] = (i == 0 || i == 4 || i == 8) ? -d0 : (real)0;
     }
   }
-  // across knot kk under the command st.u
+  // across knot kk under the command st.u: the knot's field rows of the slew's own table, wave-uniform
   TSAT_DEV void predict(int kk) {
+    const TSAT_CONSTMEM real* p0 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tm, kk, 0.0)) * 4;
+    const TSAT_CONSTMEM real* p1 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tm, kk, 0.5)) * 4;
+    const TSAT_CONSTMEM real* p2 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tm, kk, 1.0)) * 4;
+    const real b0[3] = {p0[0], p0[1], p0[2]}, b1[3] = {p1[0], p1[1], p1[2]}, b2[3] = {p2[0], p2[1], p2[2]};
+    predict(b0, b1, b2);
+  }
+  // across a step of the model tm under the command st.u with the field rows b0, b1, b2 at c = 0, 1/2, 1, wherever they come from
+  // (the held loop of tsat_mpc_model_filtered.hpp hands over the rows its plant read)
+  TSAT_DEV void predict(const real b0[3], const real b1[3], const real b2[3]) {
     const real h = tm.h;
     // the mean: one step of the plant's integrator on the model
     const real wo[3] = {st.w[0], st.w[1], st.w[2]};
     {
-      const TSAT_CONSTMEM real* p0 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tm, kk, 0.0)) * 4;
-      const TSAT_CONSTMEM real* p1 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tm, kk, 0.5)) * 4;
-      const TSAT_CONSTMEM real* p2 = bt + (size_t)TSAT_UNIFORM_INT(brow_index(tm, kk, 1.0)) * 4;
-      const real b0[3] = {p0[0], p0[1], p0[2]}, b1[3] = {p1[0], p1[1], p1[2]}, b2[3] = {p2[0], p2[1], p2[2]};
       const real cs = control_scale<real, 0>(tm);
       real x[7], us[3], k1[7], k2[7], k3[7], k4[7], t[7], nz[9];
       for (int i = 0; i < 9; ++i) nz[i] = 0;

@@ -84,6 +84,7 @@ struct HeldFiltered {
     fl.h = Pg[P_DT];
     fl.nt = 0; fl.xh = nullptr; fl.ff = nullptr;               // Filtered::state, which writes them, is not called here
   }
+  TSAT_DEV void flown(const real*, const real*, const real*, const real*) {}   // the gyro propagates this filter, not the model
   // sample 0 of the call, which the pack has measured (m): `first`, or a `step` from the record given; y_0 is never predicted
   TSAT_DEV void sample0(const real m[7], bool given, real y[7]) {
     if (given) { fl.st.load(rec, st); fl.step(m); }

@@ -15,7 +15,8 @@
 // forward sweeps' policy (mpc_held_state_diff, mpc_held_feedback below). The table clock advances by one rounded addition per step,
 // tau <- tau + dtau, and the rows of a step are those of brow_index at knot 0 of the current clock — the clock the every-step loop
 // has at that step. mpc_held_block is the one block of every held loop: what acts on the body is its Env (NoEnv; GgEnv of
-// tsat_gg.hpp), what the controller is fed its Feed (TrueFeed; SensedFeed of tsat_mpc_sensed.hpp; FilteredFeed of tsat_mpc_filtered.hpp).
+// tsat_gg.hpp), what the controller is fed its Feed (TrueFeed; SensedFeed of tsat_mpc_sensed.hpp; FilteredFeed of tsat_mpc_filtered.hpp;
+// ModelFilteredFeed of tsat_mpc_model_filtered.hpp).
 #pragma once
 #include "tsat_mpc_dispersed.hpp"
 
@@ -100,6 +101,8 @@ TSAT_DEV real mpc_held_feedback(real u, const real kd[21], int c, const real dx[
 // What the controller is fed, as Env answers what acts on the body: the state y the gains act on (`sn`, a Sensor of
 // ensemble_rollout: y = sn.state(x) at every step after a block's first) and the x0 a solve starts from, which P_X0 carries between
 // launches. TrueFeed: both are the plant's true state. SensedFeed of tsat_mpc_sensed.hpp: measurements.
+// Every step tells the sensor what it flies, `sn.flown(uc, b0, b1, b2)`: the limited command and the field rows the plant's step
+// reads — the hook beside the roll-outs' `commanded`, for a sensor that models the plant (HeldModelFiltered); empty for the others.
 struct TrueFeed {
   TrueState sn;
   // the block begins: the true state, and the y of its first step
@@ -174,6 +177,7 @@ TSAT_DEV void mpc_held_block(const MpcHeldArgs<real>& a, int t, const Env& env =
     const int i2 = brow_index(tr, 0, 1.0);
     const TSAT_GLOBAL real* p2 = tr.bt + (size_t)i2 * 4;
     const real b0[3] = {p0[0], p0[1], p0[2]}, b1[3] = {p1[0], p1[1], p1[2]}, b2[3] = {p2[0], p2[1], p2[2]};
+    feed.sn.flown(uc, b0, b1, b2);                               // what this step flies, for a sensor that models the plant
     mpc_rk4<real>(tp, e, noisy, gid, knot, x, us, b0, b1, b2, env, i0, i1, i2, xn);
     for (int i = 0; i < 7; ++i) { hx[(size_t)j * 7 + i] = x[i]; x[i] = xn[i]; }
     feed.row(j, y);

@@ -81,6 +81,7 @@ struct Sensed {
     for (int i = 0; i < 3; ++i) hb[i] = 0;
   }
   TSAT_DEV void commanded(int, const real*) {}                 // a measurement does not depend on the command
+  TSAT_DEV void flown(const real*, const real*, const real*, const real*) {}   // nor on the rows the plant read
   // y: (w_m, q_m) of knot k, or of knot max(k - 1, 0)
   TSAT_DEV void state(long long gid, int k, bool noisy, const real x[7], real y[7]) {
     real nw[3] = {0, 0, 0}, na[3] = {0, 0, 0};

@@ -52,11 +52,12 @@ def _noise_options(lib, noise_opts):
 
 
 def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
-                gravity=None, sensed=None, filtered=None):
+                gravity=None, sensed=None, filtered=None, model_filtered=None):
     """``tsat_mpc_run_dispersed`` (``replan_every`` None), ``tsat_mpc_run_held``, — with ``gravity`` = (Rtab, gm) —
     ``tsat_mpc_run_held_gg`` or — with ``sensed`` = (SensorOptions, sensor (T, 9) or None) and ``gravity`` (Rtab may be None) —
     ``tsat_mpc_run_held_sensed`` or — with ``filtered`` = (FilterOptions or None, filt_init (T, 31) or None) besides —
-    ``tsat_mpc_run_held_filtered`` on ``prob``: marshalling of all five"""
+    ``tsat_mpc_run_held_filtered`` or — with ``model_filtered`` = (ModelFilterOptions or None, filt_init (T, 58) or None) instead —
+    ``tsat_mpc_run_held_model_filtered`` on ``prob``: marshalling of all six"""
     lib = _abi.load()
     b = prob.arrays
     o = solver.opts.to_abi(b.N, b.n_tab, prob.integrator, prob.terminal_mask, error_state=prob.error_state)
@@ -100,7 +101,17 @@ def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise
         Yh = np.empty((T, n_steps, 7))
         args = (*head, int(replan_every), int(feedback), *tail, d(Rtab), float(gravity[1]), C.byref(so), d(sensor), d(Yh))
         res = dict(X_hist=Xh, U_hist=Uh, stats=st, tracking_stats=ts, n_clipped=ncl, Y_hist=Yh)
-        if filtered is None:
+        if model_filtered is not None:
+            fo, init = model_filtered
+            if init is not None:
+                init = c(init)
+                if init.shape != (T, MODEL_FILTER_STATE_W):
+                    raise ValueError("filt_init must be (T, 58)")
+            fs, ff = (None, None) if fo is None else (np.empty((T, MODEL_FILTER_STATE_W)), np.empty((T, 12)))
+            solver._check(lib.tsat_mpc_run_held_model_filtered(*args, None if fo is None else C.byref(fo), d(init), d(fs), d(ff)),
+                          "tsat_mpc_run_held_model_filtered")
+            res.update(filt_state=fs, filt_final=ff)
+        elif filtered is None:
             solver._check(lib.tsat_mpc_run_held_sensed(*args), "tsat_mpc_run_held_sensed")
         else:
             fo, init = filtered
@@ -222,6 +233,37 @@ def receding_horizon_held_filtered(prob, solver, n_steps, replan_every, filter=N
     so = _sensor_options(sensor_opts, latency)
     r = _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
                     gravity=(Rtab, gm), sensed=(so, sensor), filtered=(filter, filt_init))
+    r["n_solves"] = -(-int(n_steps) // int(replan_every))
+    return r
+
+
+MODEL_FILTER_STATE_W = 58     # TSAT_MODEL_FILTER_STATE_W: q^ 4, w^ 3, b^ 3, u 3, A 6, W 6, D 6, X 9, B 9, Y 9
+
+
+def receding_horizon_held_model_filtered(prob, solver, n_steps, replan_every, filter=None, filt_init=None, sensor_opts=None, sensor=None,
+                                         latency=0, Rtab=None, gm=0.0, feedback=True, plant=None, sat=None, noise_opts=None,
+                                         noise_id=None, step0=0, max_outer=1, max_inner=3, upload=True):
+    """``receding_horizon_held_sensed`` BEHIND THE NINE-STATE FILTER of ``tracking.attitude_ensemble_model_filtered``
+    (``tsat_mpc_run_held_model_filtered``): the model-based multiplicative EKF — body rate a state, propagated on the batch's own
+    model (``Jmat``, u_scale) under the limited command and the field rows each plant step read, the gyro a measurement — runs over
+    the raw measurements, one per control step, and the block solves' x0, the state the held steps' gains act on and ``Y_hist`` are
+    its estimate (at latency 1 the model prediction across the delay, rate included). ``filter``: a ``tracking.model_filter_options``
+    result, or a dict of that function's arguments; None passes f = NULL, which is ``receding_horizon_held_sensed`` itself
+    (``filt_state`` and ``filt_final`` are then None, and ``filt_init`` must be None). ``filt_init`` (T, 58): the filter records a
+    previous call returned as ``filt_state`` — sample 0 then makes an update on the record instead of starting the filter; None
+    starts it on the call's first measurement. The record a call leaves is the prior for the state it leaves (one closing predict
+    after the last control step). At latency 0 a continuation (``upload=False``, ``step0`` = the steps made, ``filt_init`` = the
+    previous ``filt_state``, whole blocks) equals one longer run bit for bit; latency 1 still restarts the sensor's memory with every
+    call. Returns the dict of ``receding_horizon_held_sensed`` plus ``filt_state`` (T, 58: q^ 4, w^ 3, b^ 3, u 3, A 6, W 6, D 6,
+    X 9, B 9, Y 9) and ``filt_final`` (T, 12: b^, sqrt diag P_tt, sqrt diag P_ww, sqrt diag P_bb) of that record."""
+    if isinstance(filter, dict):
+        from .tracking import model_filter_options
+        filter = model_filter_options(**filter)
+    if filter is not None and not isinstance(filter, _abi.ModelFilterOptions):
+        raise ValueError("filter must be None, a tracking.model_filter_options() result or a dict of its arguments")
+    so = _sensor_options(sensor_opts, latency)
+    r = _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
+                    gravity=(Rtab, gm), sensed=(so, sensor), model_filtered=(filter, filt_init))
     r["n_solves"] = -(-int(n_steps) // int(replan_every))
     return r
 
