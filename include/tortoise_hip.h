@@ -657,6 +657,80 @@ int  tsat_pd_ensemble_model_filtered(tsat_handle* h, const tsat_tvlqr_options* o
                          const tsat_sensor_options* s, const double* sensor,
                          const tsat_model_filter_options* f, double* X_hat, double* filt_final);
 
+/* A MAGNETOMETER-UPDATED attitude filter between sensor and law: the two filtered calls (tsat_filter_options above) with the
+ * attitude update replaced by a magnetometer update. The reference's satellite carries a gyro and a magnetometer and no sensor
+ * that hands over a quaternion: this filter takes ONE attitude fix, the first sample's q_m, and from then on corrects the
+ * gyro-propagated attitude by the measured body field b_m against the slew's own field table. One field vector fixes two of the
+ * three angles; the third comes from the field turning along the orbit, so the estimate is far coarser than the six-state
+ * filter's (the reference loop of tests/mag_filtered_common.py, 400 knots at dt = 0.2 s, sigma_mag = 5e-7 T on a 2.5e-5 T field,
+ * a 2e-3 rad/s gyro bias: rms attitude error over the last half 3.0 deg against 7.1 deg for gyro dead reckoning from the same fix).
+ * Options (launch-uniform, all standard deviations):
+ *   sigma_v   gyro white noise the filter assumes (rad/s)          sigma_u   bias random walk per knot (rad/s)
+ *   sigma_m   magnetometer noise it assumes, in units of Btab, > 0 p0_att    initial attitude standard deviation (rad)
+ *   p0_bias   initial bias standard deviation (rad/s)              reserved  0
+ * tsat_mag_filter_default_options fills the six-state filter's figures — sigma_v = 0.38 pi / 180, p0_att = pi / 180, the rest 0 —
+ * and LEAVES sigma_m 0, which the calls reject: it is in the units of the caller's table and has no default.
+ * State per realisation: the six-state filter's — q^, b^, w^ and A, B, D — in the same 31-value record. h, dq(.), (x) and the
+ * 3 x 3 inverse by cofactors are those of the six-state filter. The filter runs over the samples m_j = (w_m, q_m, b_m) of the
+ * measurement of the sensed calls, j = 0, 1, ...; r_j is the stage-0 field row of knot j, the row b_m of knot j was formed with.
+ *   First sample m_0:  q^ = q_m / |q_m|, b^ = 0, w^ = w_m;  A = p0_att^2 I, B = 0, D = p0_bias^2 I. This is the one attitude fix,
+ *     at acquisition: q_m of every later sample is ignored. No magnetometer update is made at the first sample.
+ *   Step on sample m_j, j >= 1:
+ *     1. phi = h w^, d = dq(phi), q- = q^ (x) d;  C = I + 2 d0 [v]x + 2 [v]x^2 with v = d[1:4];  Phi = C^T
+ *     2. A- = Phi A Phi^T - h (Phi B + (Phi B)^T) + h^2 D + (sigma_v h)^2 I;  B- = Phi B - h D;  D- = D + sigma_u^2 I
+ *     3. n = q- / |q-|;  b^ = qrot(n, r_j), as the true body field is formed;  z = b_m - b^;
+ *        H = -C(n) [r_j]x with C(n) = I + 2 n0 [v]x + 2 [v]x^2, v = n[1:4], the matrix for which qrot(n, v) = C(n) v
+ *        (equivalently H = -[b^]x C(n)): the derivative of qrot(q- (x) [1; dtheta / 2], r_j) in dtheta at 0
+ *     4. G = A- H^T, Gb = B-^T H^T;  S = H G + sigma_m^2 I, 3 x 3 (its upper triangle, mirrored) and positive definite because
+ *        sigma_m > 0;  Ktheta = G S^-1, Kb = Gb S^-1;  dtheta = Ktheta z, db = Kb z
+ *     5. q^ = (q- (x) [1; dtheta / 2]), normalised;  b^ <- b^ + db;  w^ = w_m - b^
+ *     6. P <- P- - K S K^T by blocks (the upper triangles of A and D only)
+ *   A zero field row gives H = 0 and K = 0, an update that changes nothing, without a branch (the last row of a
+ *   magnetic_simulation table is such a row). Nothing asks whether a sigma is zero.
+ *   What the law sees at knot k is the six-state filter's rule word for word — latency 0: the filter is at sample k. Latency 1:
+ *   y_0 from the first sample; m_0 is handed over twice and makes no step the second time; for k >= 1 the filter is at sample
+ *   k - 1 and the estimate is predicted across the delay by q^ (x) dq(h w^). The sample that arrives at knot k at latency 1 is
+ *   knot k - 1's: it is updated against row r_{k-1}, not r_k.
+ * The magnetometer is sampled ONCE per knot: the PD law's b_m is the very reading the filter used (not filtered). Under the TVLQR
+ * law the reading is drawn too (the sensed and filtered TVLQR calls draw none). stats_nominal flies the ideal sensor through the
+ * same filter. The magnetometer bias of `sensor` is not estimated: it enters z unmodelled.
+ *   X_hat       7 x N x M x T or NULL   row k holds y_k for k < n_knots[t] - 1, the rest is zero (the layout of X_sim)
+ *   filt_final  9 x M x T or NULL       b^ (3), sqrt(diag A) (3), sqrt(diag D) (3) after the last sample processed (TSAT_FILTER_W)
+ * f == NULL is the sensed call, byte for byte (it is dispatched there); X_hat and filt_final must then be NULL.
+ * Rejected with -1 (text in tsat_ensemble_last_error; nothing is launched and no workspace grows): a non-finite or negative
+ * option; sigma_m == 0; reserved != 0; f NULL with X_hat or filt_final non-NULL; and everything the sensed call rejects. */
+struct tsat_mag_filter_options {
+  double  sigma_v;
+  double  sigma_u;
+  double  sigma_m;
+  double  p0_att;
+  double  p0_bias;
+  int32_t reserved;         /* 0 */
+};
+typedef struct tsat_mag_filter_options tsat_mag_filter_options;
+void tsat_mag_filter_default_options(tsat_mag_filter_options* f);
+int  tsat_tvlqr_ensemble_mag_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                         const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* K_lqr, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor,
+                         const tsat_mag_filter_options* f, double* X_hat, double* filt_final);
+int  tsat_pd_ensemble_mag_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat,
+                         const double* kd, const double* kp, int32_t feedforward, int32_t limit_mode,
+                         const double* x0_sim, const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor,
+                         const tsat_mag_filter_options* f, double* X_hat, double* filt_final);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Receding-horizon re-solve on the RESIDENT batch (BASELINE.json configs[4]). NOT in the reference —
  * it tracks its plan with TVLQR (src/attitude_controller.jl:1-48); defined here as: n_steps times

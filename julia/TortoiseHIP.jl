@@ -631,11 +631,14 @@ end
 # `tsat_model_filter_options*` (seven Float64 — sigma_v, sigma_w, sigma_u, sigma_a, sigma_g, p0_att, p0_bias —, then Int32
 # reserved: 64 bytes with the tail padding): unbound likewise (tracking.attitude_ensemble_model_filtered,
 # tracking.attitude_ensemble_pd_model_filtered), and so is the held re-planning loop behind that filter
-# (mpc.receding_horizon_held_model_filtered).
+# (mpc.receding_horizon_held_model_filtered). The mag-filtered ensembles take the sensor struct and a `tsat_mag_filter_options*` (five
+# Float64 — sigma_v, sigma_u, sigma_m, p0_att, p0_bias —, then Int32 reserved: 48 bytes with the tail padding): unbound likewise
+# (tracking.attitude_ensemble_mag_filtered, tracking.attitude_ensemble_pd_mag_filtered).
 const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsat_pd_ensemble_sensed, :tsat_mpc_run_held_sensed,
                  :tsat_filter_default_options, :tsat_tvlqr_ensemble_filtered, :tsat_pd_ensemble_filtered,
                  :tsat_mpc_run_held_filtered,
                  :tsat_model_filter_default_options, :tsat_tvlqr_ensemble_model_filtered, :tsat_pd_ensemble_model_filtered,
-                 :tsat_mpc_run_held_model_filtered]
+                 :tsat_mpc_run_held_model_filtered,
+                 :tsat_mag_filter_default_options, :tsat_tvlqr_ensemble_mag_filtered, :tsat_pd_ensemble_mag_filtered]
 
 end # module
