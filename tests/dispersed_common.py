@@ -1,11 +1,12 @@
 """Shared pieces of tests/test_dispersed.py (CPU tier) and tests/test_gpu_dispersed.py (GPU tier).
 
-THE REFERENCE of the dispersed ensemble (tsat_tvlqr_ensemble_dispersed) is a closed loop built here, knot by knot, from the
-unchanged oracle's primitives only: ``ol.tvlqr_batch`` for the gains K (model inertia), then per knot ``ol.qmult`` on the
-conjugate reference attitude for dX, the three rules of the entry point (u_cmd = U - K dX; u_sat = clip(u_cmd); the plant of all
-four RK4 stages sees G u_sat + m_res / u_scale and has inertia Jp), ``ol.plant_noise`` for the draws, the noise injection of
-src/simulator.jl:5-23, ``ol.dyn7(..., Jp)`` per stage, table rows floor((k + c) dtau + tau0) clamped. With the model's plant and
-no limits it has to reproduce ``ol.tvlqr_batch`` (test_dispersed.py::test_reference_is_pinned_to_the_oracle).
+THE REFERENCE of the dispersed ensemble (tsat_tvlqr_ensemble_dispersed) is a closed loop built knot by knot
+(``reference_rollout.ensemble_loop``) from the unchanged oracle's primitives only: ``ol.tvlqr_batch`` for the gains K (model
+inertia), then per knot ``ol.qmult`` on the conjugate reference attitude for dX, the three rules of the entry point (u_cmd =
+U - K dX; u_sat = clip(u_cmd); the plant of all four RK4 stages sees G u_sat + m_res / u_scale and has inertia Jp),
+``ol.plant_noise`` for the draws, the noise injection of src/simulator.jl:5-23 (``_noisy`` here), ``ol.dyn7`` on Jp per stage,
+table rows floor((k + c) dtau + tau0) clamped (``_row`` here). With the model's plant and no limits it has to reproduce
+``ol.tvlqr_batch`` (test_dispersed.py::test_reference_is_pinned_to_the_oracle).
 
 Also: the bracket on the clipped-knot counter, the sampled (t, m) pairs with their replacement cap and the cases of
 tests/ensemble_common.py, which also holds the ctypes binding of the emulated kernel (``EmuEnsemble.run(..., plant=...)``)."""
@@ -41,46 +42,11 @@ def _noisy(ol, x, b, nz):
 
 
 def reference_loop(ol, batch, t, Xr, Ur, K, x0, opts, gid, plant=None, lo=None, hi=None, noisy=True):
-    """one closed loop of slew t. Xr (N,7), Ur (N-1,3) the plan, K (N-1,6,3) the oracle's gains of it, plant (21,) or None for
-    the model's, lo / hi (3,) or None, gid the generator id. Returns X_sim (N,7) zero-filled beyond the slew's horizon,
-    (n_sure, n_maybe)."""
-    NS = batch.N
-    N = NS if batch.n_knots is None else int(batch.n_knots[t])
-    us, h = float(opts.u_scale), float(batch.dt[t])
-    if plant is None:
-        Jp, G, mres = np.asarray(batch.Jmat[t]).reshape(3, 3).T, np.eye(3), np.zeros(3)
-    else:
-        Jp, G, mres = plant[0:9].reshape(3, 3).T, plant[9:18].reshape(3, 3).T, plant[18:21]
-    Xs = np.zeros((NS, 7))
-    x = np.array(x0, dtype=np.float64)
-    n_sure = n_maybe = 0
-    for k in range(N - 1):
-        Xs[k] = x
-        xr = Xr[k]
-        qe = ol.qmult(np.r_[xr[3], -xr[4:7]], x[3:7])
-        dX = np.r_[x[:3] - xr[:3], qe[1:4]]
-        u = Ur[k] - K[k].T @ dX
-        if lo is not None:
-            bl, bh = CLIP_BAND * np.abs(lo), CLIP_BAND * np.abs(hi)
-            n_sure += bool(np.any((lo - u > bl) | (u - hi > bh)))          # beyond a limit by more than the band
-            n_maybe += bool(np.any((lo - u > -bl) | (u - hi > -bh)))       # within the band of a limit, or beyond
-            u = np.minimum(np.maximum(u, lo), hi)
-        ua = G @ u + mres / us
-        nz = [ol.plant_noise(int(opts.noise_seed), int(gid), k, s, opts.sigma_gyro, opts.sigma_att, opts.field_amp) if noisy else None
-              for s in range(4)]
-        b0, b1, b2 = _row(batch, t, k, 0.0), _row(batch, t, k, 0.5), _row(batch, t, k, 1.0)
-
-        def f(xx, bb, n):
-            xn, bn = _noisy(ol, xx, bb, n)
-            return h * ol.dyn7(xn, ua, bn, Jp, us)
-
-        k1 = f(x, b0, nz[0])
-        k2 = f(x + k1 / 2, b1, nz[1])
-        k3 = f(x + k2 / 2, b1, nz[2])
-        k4 = f(x + k3, b2, nz[3])
-        x = x + (k1 + 2 * k2 + 2 * k3 + k4) / 6
-    Xs[N - 1] = x
-    return Xs, (n_sure, n_maybe)
+    """one closed loop of slew t: ``reference_rollout.ensemble_loop`` under the TVLQR law on the true state, no gravity-gradient
+    term. Xr (N,7), Ur (N-1,3) the plan, K (N-1,6,3) the oracle's gains of it, plant (21,) or None for the model's, lo / hi (3,) or
+    None, gid the generator id. Returns X_sim (N,7) zero-filled beyond the slew's horizon, (n_sure, n_maybe)."""
+    import reference_rollout as rr          # here: that module is built on this one
+    return rr.ensemble_loop(ol, "tv", batch, t, Xr, Ur, K, x0, opts, gid, None, 0.0, plant, lo, hi, noisy=noisy)[:2]
 
 
 def stats_of(abi, X_sim, xf, n_knots, dt, min_steps=10, w_tol=0.05, angle_tol=0.08727):
@@ -102,27 +68,9 @@ def stats_of(abi, X_sim, xf, n_knots, dt, min_steps=10, w_tol=0.05, angle_tol=0.
 
 def reference_pairs(ol, abi, batch, X, U, K, x0_sim, opts, pairs, plant=None, sat=None, noise_id0=None):
     """the reference on the (t, m) pairs (n, 2); m = -1 is the noise-free MODEL plant from X[t, 0] (stats_nominal).
-    Returns dict(X_sim (n, N, 7), stats (n,), n_sure (n,), n_maybe (n,), xf (n, 7), n_knots (n,))."""
-    T, M = x0_sim.shape[:2]
-    id0 = np.arange(T, dtype=np.int64) * M if noise_id0 is None else np.asarray(noise_id0, dtype=np.int64)
-    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
-    ol.load()
-
-    def one(p):
-        t, m = int(p[0]), int(p[1])
-        if m < 0:
-            return reference_loop(ol, batch, t, X[t], U[t], K[t], X[t, 0], opts, 0, None, None if lo is None else lo[t],
-                                  None if hi is None else hi[t], noisy=False)
-        return reference_loop(ol, batch, t, X[t], U[t], K[t], x0_sim[t, m], opts, id0[t] + m, None if plant is None else plant[t, m],
-                              None if lo is None else lo[t], None if hi is None else hi[t])
-
-    res = [one(p) for p in pairs]
-    pairs = np.asarray(pairs)
-    Xs = np.stack([r[0] for r in res])
-    nk = ec.horizons(batch)[pairs[:, 0]]
-    xf = batch.xf[pairs[:, 0]]
-    st = stats_of(abi, Xs, xf, nk, batch.dt[pairs[:, 0]], opts.min_steps, opts.w_tol, opts.angle_tol)
-    return dict(X_sim=Xs, stats=st, n_sure=np.array([r[1][0] for r in res]), n_maybe=np.array([r[1][1] for r in res]), xf=xf, n_knots=nk)
+    Returns the dict of ``reference_rollout.pairs_of``."""
+    import reference_rollout as rr
+    return rr.pairs_of(ol, abi, "tv", batch, x0_sim, K, opts, pairs, X=X, U=U, plant=plant, sat=sat, noise_id0=noise_id0)
 
 
 def all_pairs(T, M):

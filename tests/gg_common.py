@@ -1,9 +1,9 @@
 """Shared pieces of tests/test_gg.py (CPU tier) and tests/test_gpu_gg.py (GPU tier): the dispersed ensemble and the held loop UNDER
 GRAVITY-GRADIENT TORQUE (tsat_tvlqr_ensemble_gg, tsat_mpc_run_held_gg).
 
-THE REFERENCES are ``dispersed_common.reference_loop`` and ``mpc_held_common.reference_loop`` restated with the three lines of the
+THE REFERENCES are ``dispersed_common.reference_loop`` and ``mpc_held_common.reference_loop`` with the three lines of the
 definition (include/tortoise_hip.h) added to every RK4 stage — ``gg_increment`` below, built from ``ol.qrot``, ``ol.inv3`` and
-numpy's cross product only —, everything else operation for operation as there. With gm = 0 they have to equal their parents with
+numpy's cross product only, which ``reference_rollout.plant_step`` adds where it is given an orbit table. With gm = 0 they have to equal their parents with
 max |d| = 0 (test_gg.py::test_references_at_gm0_are_their_parents).
 
 Inputs: the model flies the reference's 3U inertia (src/input_parameters.jl:46-51, diag(0.020833, 0.020833, 0.0041666) kg m^2:
@@ -17,7 +17,6 @@ import ctypes as C
 import math
 import os
 import subprocess
-import types
 
 import numpy as np
 
@@ -60,69 +59,21 @@ def gg_increment(ol, x, r_km, gm, Jp, h):
 
 def ensemble_loop(ol, batch, t, Xr, Ur, K, x0, opts, gid, Rtab, gm, plant=None, lo=None, hi=None, noisy=True):
     """dispersed_common.reference_loop with the term; arguments as there, then the orbit table (n_btab, n_tab, 3) and gm"""
-    NS = batch.N
-    N = NS if batch.n_knots is None else int(batch.n_knots[t])
-    us, h = float(opts.u_scale), float(batch.dt[t])
-    if plant is None:
-        Jp, G, mres = np.asarray(batch.Jmat[t]).reshape(3, 3).T, np.eye(3), np.zeros(3)
-    else:
-        Jp, G, mres = plant[0:9].reshape(3, 3).T, plant[9:18].reshape(3, 3).T, plant[18:21]
-    Xs = np.zeros((NS, 7))
-    x = np.array(x0, dtype=np.float64)
-    n_sure = n_maybe = 0
-    for k in range(N - 1):
-        Xs[k] = x
-        xr = Xr[k]
-        qe = ol.qmult(np.r_[xr[3], -xr[4:7]], x[3:7])
-        dX = np.r_[x[:3] - xr[:3], qe[1:4]]
-        u = Ur[k] - K[k].T @ dX
-        if lo is not None:
-            bl, bh = dc.CLIP_BAND * np.abs(lo), dc.CLIP_BAND * np.abs(hi)
-            n_sure += bool(np.any((lo - u > bl) | (u - hi > bh)))
-            n_maybe += bool(np.any((lo - u > -bl) | (u - hi > -bh)))
-            u = np.minimum(np.maximum(u, lo), hi)
-        ua = G @ u + mres / us
-        nz = [ol.plant_noise(int(opts.noise_seed), int(gid), k, s, opts.sigma_gyro, opts.sigma_att, opts.field_amp) if noisy else None
-              for s in range(4)]
-        b0, b1, b2 = dc._row(batch, t, k, 0.0), dc._row(batch, t, k, 0.5), dc._row(batch, t, k, 1.0)
-        r0, r1, r2 = _grow(batch, Rtab, t, k, 0.0), _grow(batch, Rtab, t, k, 0.5), _grow(batch, Rtab, t, k, 1.0)
-
-        def f(xx, bb, n, rr):
-            xn, bn = dc._noisy(ol, xx, bb, n)
-            kk = h * ol.dyn7(xn, ua, bn, Jp, us)
-            kk[0:3] = kk[0:3] + gg_increment(ol, xx, rr, gm, Jp, h)
-            return kk
-
-        k1 = f(x, b0, nz[0], r0)
-        k2 = f(x + k1 / 2, b1, nz[1], r1)
-        k3 = f(x + k2 / 2, b1, nz[2], r1)
-        k4 = f(x + k3, b2, nz[3], r2)
-        x = x + (k1 + 2 * k2 + 2 * k3 + k4) / 6
-    Xs[N - 1] = x
-    return Xs, (n_sure, n_maybe)
+    import reference_rollout as rr          # here: that module is built on this one
+    return rr.ensemble_loop(ol, "tv", batch, t, Xr, Ur, K, x0, opts, gid, Rtab, gm, plant, lo, hi, noisy=noisy)[:2]
 
 
 def ensemble_pairs(ol, abi, batch, X, U, K, x0_sim, opts, pairs, Rtab, gm, plant=None, sat=None, noise_id0=None):
     """dispersed_common.reference_pairs with the term: the (t, m) pairs (n, 2), m = -1 the noise-free MODEL plant"""
-    T, M = x0_sim.shape[:2]
-    id0 = np.arange(T, dtype=np.int64) * M if noise_id0 is None else np.asarray(noise_id0, dtype=np.int64)
-    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
-    ol.load()
-    res = []
-    for p in pairs:
-        t, m = int(p[0]), int(p[1])
-        kw = dict(lo=None if lo is None else lo[t], hi=None if hi is None else hi[t])
-        if m < 0:
-            res.append(ensemble_loop(ol, batch, t, X[t], U[t], K[t], X[t, 0], opts, 0, Rtab, gm, None, noisy=False, **kw))
-        else:
-            res.append(ensemble_loop(ol, batch, t, X[t], U[t], K[t], x0_sim[t, m], opts, id0[t] + m, Rtab, gm,
-                                     None if plant is None else plant[t, m], **kw))
-    pairs = np.asarray(pairs)
-    Xs = np.stack([r[0] for r in res])
-    nk = ec.horizons(batch)[pairs[:, 0]]
-    xf = batch.xf[pairs[:, 0]]
-    st = dc.stats_of(abi, Xs, xf, nk, batch.dt[pairs[:, 0]], opts.min_steps, opts.w_tol, opts.angle_tol)
-    return dict(X_sim=Xs, stats=st, n_sure=np.array([r[1][0] for r in res]), n_maybe=np.array([r[1][1] for r in res]), xf=xf, n_knots=nk)
+    import reference_rollout as rr
+    return rr.pairs_of(ol, abi, "tv", batch, x0_sim, K, opts, pairs, X=X, U=U, Rtab=Rtab, gm=gm, plant=plant, sat=sat, noise_id0=noise_id0)
+
+
+def held_loop(ol, batch, opts, n_steps, replan_every, feedback, po, Rtab, gm, plant=None, sat=None, noise_id=None, step0=0, nthreads=4):
+    """mpc_held_common.reference_loop with the term in every plant step; arguments as there, then the orbit table and gm"""
+    import reference_rollout as rr
+    return rr.held_loop(ol, batch, opts, n_steps, replan_every, feedback, po, plant=plant, sat=sat, noise_id=noise_id, step0=step0,
+                        Rtab=Rtab, gm=gm, nthreads=nthreads)
 
 
 def kept(ref, opts):
@@ -135,80 +86,6 @@ def kept(ref, opts):
           f"{int(np.count_nonzero(ref['stats']['failed'][keep] == 0))}")
     assert keep.size == dc.N_KEPT, "more than 2 of 34 sampled realisations sit on a threshold"
     return keep
-
-
-def held_loop(ol, batch, opts, n_steps, replan_every, feedback, po, Rtab, gm, plant=None, sat=None, noise_id=None, step0=0, nthreads=4):
-    """mpc_held_common.reference_loop with the term in every plant step; arguments as there, then the orbit table and gm"""
-    T, R = batch.T, int(replan_every)
-    nk = ec.horizons(batch)
-    us = float(opts.u_scale)
-    es = int(opts.error_state)
-    nh = 6 if es else 7
-    noisy = int(po.noise_mode) == 1
-    ids = np.arange(T, dtype=np.int64) if noise_id is None else np.asarray(noise_id, dtype=np.int64)
-    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
-    x, U0, tau = batch.x0.copy(), batch.U0.copy(), batch.tau0.copy()
-    Xh, Uh = np.zeros((T, n_steps + 1, 7)), np.zeros((T, n_steps, 3))
-    n_sure, n_maybe = np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
-    statuses, tally = [], np.zeros((T, 4), dtype=np.int64)
-    ol.load()
-    for sb in range(0, n_steps, R):
-        r_len = min(R, n_steps - sb)
-        b2 = batch.slice(0, T)
-        b2.x0, b2.U0, b2.tau0 = np.ascontiguousarray(x), np.ascontiguousarray(U0), np.ascontiguousarray(tau)
-        r = ol.solve_batch(b2, opts, nthreads=min(nthreads, ol.num_procs()), want_K=True)
-        statuses.append(r["stats"]["status"].copy())
-        rs = r["stats"]
-        tally += np.stack([rs["n_backward"], rs["n_forward"], np.maximum(rs["outer_iters"] - 1, 0), rs["inner_iters"]], axis=1)
-        for j in range(r_len):
-            s = sb + j
-            Xh[:, s] = x
-            clock = types.SimpleNamespace(dtau=batch.dtau, tau0=tau, Btab=batch.Btab, btab_idx=batch.btab_idx, n_tab=batch.n_tab)
-            for t in range(T):
-                if plant is None:
-                    Jp, G, mres = np.asarray(batch.Jmat[t]).reshape(3, 3).T, np.eye(3), np.zeros(3)
-                else:
-                    Jp, G, mres = plant[t, 0:9].reshape(3, 3).T, plant[t, 9:18].reshape(3, 3).T, plant[t, 18:21]
-                u = r["U"][t, j].copy()
-                if j > 0 and feedback:
-                    dx = ol.quaternion_error(x[t], r["X"][t, j]) if es else x[t] - r["X"][t, j]
-                    for a in range(3):
-                        v = float(u[a])
-                        for i in range(nh):
-                            v += float(r["K"][t, j, i, a]) * float(dx[i])
-                        u[a] = v
-                if lo is not None:
-                    bl, bh = hc.CLIP_BAND * np.abs(lo[t]), hc.CLIP_BAND * np.abs(hi[t])
-                    n_sure[t] += bool(np.any((lo[t] - u > bl) | (u - hi[t] > bh)))
-                    n_maybe[t] += bool(np.any((lo[t] - u > -bl) | (u - hi[t] > -bh)))
-                    u = np.minimum(np.maximum(u, lo[t]), hi[t])
-                Uh[t, s] = u
-                ua = G @ u + mres / us
-                nz = [ol.plant_noise(int(po.noise_seed), int(ids[t]), int(step0) + s, st, po.sigma_gyro, po.sigma_att, po.field_amp)
-                      if noisy else None for st in range(4)]
-                b0, b1, b2r = dc._row(clock, t, 0, 0.0), dc._row(clock, t, 0, 0.5), dc._row(clock, t, 0, 1.0)
-                r0, r1, r2 = _grow(clock, Rtab, t, 0, 0.0), _grow(clock, Rtab, t, 0, 0.5), _grow(clock, Rtab, t, 0, 1.0)
-                h = float(batch.dt[t])
-
-                def f(xx, bb, n, rr):
-                    xn, bn = dc._noisy(ol, xx, bb, n)
-                    kk = h * ol.dyn7(xn, ua, bn, Jp, us)
-                    kk[0:3] = kk[0:3] + gg_increment(ol, xx, rr, gm, Jp, h)
-                    return kk
-
-                k1 = f(x[t], b0, nz[0], r0)
-                k2 = f(x[t] + k1 / 2, b1, nz[1], r1)
-                k3 = f(x[t] + k2 / 2, b1, nz[2], r1)
-                k4 = f(x[t] + k3, b2r, nz[3], r2)
-                x[t] = x[t] + (k1 + 2 * k2 + 2 * k3 + k4) / 6
-            tau = tau + batch.dtau                           # one rounded addition per step
-        for t in range(T):                                   # the shift by the block's steps inside the trajectory's own horizon
-            n = int(nk[t])
-            U0[t, :n - 1] = r["U"][t, np.minimum(np.arange(n - 1) + r_len, n - 2)]
-    Xh[:, n_steps] = x
-    ts = dc.stats_of(ol._abi, Xh, batch.xf, np.full(T, n_steps + 1), batch.dt, po.min_steps, po.w_tol, po.angle_tol)
-    return dict(X_hist=Xh, U_hist=Uh, stats=r["stats"], X=r["X"], U=r["U"], tracking_stats=ts, n_sure=n_sure, n_maybe=n_maybe,
-                n_solves=len(statuses), statuses=np.array(statuses), tally=tally)
 
 
 def moved(final_with, final_without, label):
@@ -256,31 +133,13 @@ class EmuGg:
 
     def held(self, batch, opts, po, n_steps, replan_every, feedback, Rtab, gm, plant=None, sat=None, noise_id=None, step0=0):
         """emu_mpc_held_gg_batch; arguments and result as mpc_held_common.EmuMpcHeld.run"""
-        T, N = batch.T, batch.N
-        o = opts.copy()
-        o.n_knots, o.n_tab = N, batch.n_tab
-        c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-        plant, Rtab = c(plant), c(Rtab)
+        Rtab = np.ascontiguousarray(Rtab, dtype=np.float64)
         assert Rtab.shape == batch.Btab.shape
-        lo, hi = (None, None) if sat is None else (c(np.broadcast_to(sat[0], (T, 3))), c(np.broadcast_to(sat[1], (T, 3))))
-        ids = None if noise_id is None else np.ascontiguousarray(noise_id, dtype=np.int64)
-        Xh = np.zeros((T, n_steps + 1, 7)); Uh = np.zeros((T, n_steps, 3))
-        X = np.zeros((T, N, 7)); U = np.zeros((T, N - 1, 3))
-        st = np.zeros(T, dtype=self.abi.STATS_DTYPE)
-        ts = np.zeros(T, dtype=self.abi.TVLQR_STATS_DTYPE)
-        ncl = np.full(T, -1, dtype=np.int32)
-        d = self.abi.as_dp
-        rc = self.lib.emu_mpc_held_gg_batch(
-            C.byref(o), C.byref(po), C.c_int64(T), C.c_int64(batch.Btab.shape[0]), d(batch.x0), d(batch.xf), d(batch.Btab),
-            self.abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat), d(batch.Qd), d(batch.Qfd),
-            d(batch.Rd), d(batch.ulo), d(batch.uhi), d(batch.U0), C.c_int32(n_steps), C.c_int64(step0), C.c_int32(replan_every),
-            C.c_int32(feedback), d(plant), d(lo), d(hi), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int64)), d(Xh), d(Uh),
-            st.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p), self.abi.as_ip(ncl), d(X), d(U),
-            None if batch.n_knots is None else self.abi.as_ip(np.ascontiguousarray(batch.n_knots, dtype=np.int32)), d(Rtab),
-            C.c_double(gm))
+        args, out = hc.held_call(self.abi, batch, opts, po, n_steps, replan_every, feedback, plant, sat, noise_id, step0)
+        rc = self.lib.emu_mpc_held_gg_batch(*args, self.abi.as_dp(Rtab), C.c_double(gm))
         if rc != 0:
             raise RuntimeError(f"emu_mpc_held_gg_batch rc={rc}")
-        return dict(X_hist=Xh, U_hist=Uh, stats=st, X=X, U=U, tracking_stats=ts, n_clipped=ncl)
+        return out
 
     def check(self, Rtab, gm):
         text = C.create_string_buffer(256)

@@ -1,11 +1,11 @@
 """Shared pieces of tests/test_mag_filtered.py (CPU tier) and tests/test_gpu_mag_filtered.py (GPU tier): the ensemble controllers
 behind the MAGNETOMETER-updated attitude filter (tsat_tvlqr_ensemble_mag_filtered, tsat_pd_ensemble_mag_filtered).
 
-THE REFERENCE (``loop``) is ``filtered_common.loop`` restated with the recursion of include/tortoise_hip.h (``MagEkf``) between
-``measure`` and the law — numpy and the oracle's primitives only (``ol.qmult``, ``ol.qrot``, ``ol.inv3``, ``ol.dyn7``,
-``ol.plant_noise``). It carries the delayed ROW next to the delayed sample: at latency 1 the sample that arrives at knot k is knot
-k - 1's and is updated against r_{k-1}. The PD law reads the b_m that ``measure`` returned, the very reading the filter used. With
-``filt=None`` it has to equal ``sensed_common.loop`` with max |d| = 0
+THE REFERENCE (``pairs_of``) is ``reference_rollout.ensemble_loop`` with the recursion of include/tortoise_hip.h (``MagEkf``, behind
+``reference_rollout.MagState``) between ``measure`` and the law — numpy and the oracle's primitives only (``ol.qmult``, ``ol.qrot``,
+``ol.inv3``, ``ol.dyn7``, ``ol.plant_noise``). The delayed ROW goes with the delayed sample: at latency 1 the sample that arrives at
+knot k is knot k - 1's and is updated against r_{k-1}. The PD law reads the b_m that ``measure`` returned, the very reading the filter
+used. With ``filt=None`` it has to equal ``sensed_common.pairs_of`` with max |d| = 0
 (test_mag_filtered.py::test_reference_with_the_filter_off_is_the_sensed_reference).
 
 The case of both tiers is ``sensed_common``'s; the filter's levels are MFILT below. Every parity test first asserts its conditions on
@@ -20,10 +20,10 @@ import subprocess
 import numpy as np
 
 import dispersed_common as dc
-import ensemble_common as ec
 import filtered_common as fc
 import gg_common as gc
 import pd_common as pc
+import reference_rollout as rr
 import sensed_common as sc
 from conftest import ROOT
 
@@ -84,124 +84,19 @@ class MagEkf(fc.Ekf):
         self.prior = (qm, Am, Bm, Dm)
 
 
-def loop(ol, law, batch, t, Xr, Ur, gains, x0, opts, gid, Rtab, gm, plant=None, lo=None, hi=None, limit_mode=0, noisy=True, sens=None,
-         latency=0, bias=None, filt=None, predict=True, update=True, pair_own_row=True):
-    """``filtered_common.loop`` with the magnetometer-updated filter between ``measure`` and the law. ``filt`` None: the raw
-    measurement, the sensed reference itself. Conditions of the tests, not modes of the product: ``predict`` False leaves the
-    prediction across the delay out, ``update`` False the magnetometer update (gyro dead reckoning from the first fix),
-    ``pair_own_row`` False updates the delayed sample against r_k in the place of r_{k-1}. Returns what ``filtered_common.loop``
-    returns."""
-    NS = batch.N
-    N = NS if batch.n_knots is None else int(batch.n_knots[t])
-    us, h = float(opts.u_scale), float(batch.dt[t])
-    if plant is None:
-        Jp, G, mres = np.asarray(batch.Jmat[t]).reshape(3, 3).T, np.eye(3), np.zeros(3)
-    else:
-        Jp, G, mres = plant[0:9].reshape(3, 3).T, plant[9:18].reshape(3, 3).T, plant[18:21]
-    Xs, Uc, Xh, Ym = np.zeros((NS, 7)), np.zeros((NS - 1, 3)), np.zeros((NS, 7)), np.zeros((NS, 7))
-    x = np.array(x0, dtype=np.float64)
-    n_sure = n_maybe = 0
-    held = held_row = None
-    ekf = None if filt is None else MagEkf(ol, h, filt, update)
-    last = N - 1
-    for k in range(0, last):
-        Xs[k] = x
-        xr = batch.xf[t] if Xr is None else Xr[k]
-        b0, b1, b2 = dc._row(batch, t, k, 0.0), dc._row(batch, t, k, 0.5), dc._row(batch, t, k, 1.0)
-        r_j = b0
-        if sens is None:
-            w_m, q_m = x[:3], x[3:7]
-            b_m = ol.qrot(x[3:7] / math.sqrt(float(x[3:7] @ x[3:7])), b0) if law == "pd" else None
-        else:
-            y = sc.measure(ol, batch, t, k, x, opts, gid, sens, bias, noisy)
-            delayed = latency and held is not None
-            w_m, q_m, b_m = held if delayed else y                              # y_max(k-1, 0)
-            r_j = held_row if (delayed and pair_own_row) else b0                # ... and the row it was formed with
-            held, held_row = y, b0
-        Ym[k] = np.r_[w_m, q_m]
-        if ekf is not None:
-            if k == 0:
-                ekf.first(w_m, q_m)
-            elif not (latency and k == 1):                                      # m_0 handed over a second time: no step
-                ekf.step(w_m, b_m, r_j)
-            w_m, q_m = ekf.w, (ekf.predicted() if (latency and k > 0 and predict) else ekf.q)
-            Xh[k] = np.r_[w_m, q_m]
-        qe = ol.qmult(np.r_[xr[3], -xr[4:7]], q_m)
-        if law == "tv":
-            dX = np.r_[w_m - xr[:3], qe[1:4]]
-            u = Ur[k] - gains[k].T @ dX
-        else:
-            kd, kp = gains
-            dw = w_m - xr[:3]
-            s = -1.0 if qe[0] < 0 else 1.0
-            treq = -(kd * dw + kp * (s * qe[1:4]))
-            bb = float(b_m @ b_m)
-            m = np.cross(b_m, treq) / bb if bb != 0.0 else np.zeros(3)
-            u = (Ur[k] if Ur is not None else np.zeros(3)) + m / us
-        Uc[k] = u
-        if limit_mode == 1:
-            r = np.array([u[c] / hi[c] if u[c] > 0 else (u[c] / lo[c] if u[c] < 0 else 0.0) for c in range(3)])
-            beta = float(r.max())
-            n_sure += bool(beta - 1.0 > dc.CLIP_BAND)
-            n_maybe += bool(beta - 1.0 > -dc.CLIP_BAND)
-            if beta > 1.0:
-                u = u * (1.0 / beta)
-        elif lo is not None:
-            bl, bh = dc.CLIP_BAND * np.abs(lo), dc.CLIP_BAND * np.abs(hi)
-            n_sure += bool(np.any((lo - u > bl) | (u - hi > bh)))
-            n_maybe += bool(np.any((lo - u > -bl) | (u - hi > -bh)))
-            u = np.minimum(np.maximum(u, lo), hi)
-        ua = G @ u + mres / us
-        nz = [ol.plant_noise(int(opts.noise_seed), int(gid), k, st, opts.sigma_gyro, opts.sigma_att, opts.field_amp) if noisy else None
-              for st in range(4)]
-        rr = [None] * 3 if Rtab is None else [gc._grow(batch, Rtab, t, k, c) for c in (0.0, 0.5, 1.0)]
-
-        def f(xx, bb_, n, r):
-            xn, bn = dc._noisy(ol, xx, bb_, n)
-            kk = h * ol.dyn7(xn, ua, bn, Jp, us)
-            if r is not None:
-                kk[0:3] = kk[0:3] + gc.gg_increment(ol, xx, r, gm, Jp, h)
-            return kk
-
-        k1 = f(x, b0, nz[0], rr[0])
-        k2 = f(x + k1 / 2, b1, nz[1], rr[1])
-        k3 = f(x + k2 / 2, b1, nz[2], rr[1])
-        k4 = f(x + k3, b2, nz[3], rr[2])
-        x = x + (k1 + 2 * k2 + 2 * k3 + k4) / 6
-    Xs[last] = x
-    return Xs, (n_sure, n_maybe), Uc, Xh, (np.zeros(FILTER_W) if ekf is None else ekf.final()), Ym
+def estimator(ol, batch, filt, predict=True, update=True, pair_own_row=True):
+    """t -> the estimator of one loop of slew t: ``MagEkf`` behind ``reference_rollout.MagState``. ``filt`` None: the raw
+    measurement. Conditions of the tests, not modes of the product: ``predict`` False leaves the prediction across the delay out,
+    ``update`` False the magnetometer update (gyro dead reckoning from the first fix), ``pair_own_row`` False updates the delayed
+    sample against r_k in the place of r_{k-1}"""
+    if filt is None:
+        return lambda t: rr.Raw(FILTER_W)
+    return lambda t: rr.MagState(MagEkf(ol, batch.dt[t], filt, update), predict, pair_own_row)
 
 
-def pairs_of(ol, abi, law, batch, x0_sim, gains, opts, pairs, X=None, U=None, Rtab=None, gm=0.0, plant=None, sat=None, limit_mode=0,
-             x0_nom=None, noise_id0=None, sens=None, latency=0, sensor=None, filt=None, predict=True, update=True, pair_own_row=True):
-    """``filtered_common.pairs_of`` through ``loop`` above"""
-    T, M = x0_sim.shape[:2]
-    id0 = np.arange(T, dtype=np.int64) * M if noise_id0 is None else np.asarray(noise_id0, dtype=np.int64)
-    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
-    if law == "pd":
-        gains = (np.broadcast_to(gains[0], (T, 3)), np.broadcast_to(gains[1], (T, 3)))
-    ol.load()
-    res = []
-    for p in pairs:
-        t, m = int(p[0]), int(p[1])
-        g = gains[t] if law == "tv" else (gains[0][t], gains[1][t])
-        kw = dict(lo=None if lo is None else lo[t], hi=None if hi is None else hi[t], limit_mode=limit_mode, sens=sens, latency=latency,
-                  filt=filt, predict=predict, update=update, pair_own_row=pair_own_row)
-        Xr, Ur = None if X is None else X[t], None if U is None else U[t]
-        if m < 0:
-            x0 = x0_nom[t] if x0_nom is not None else X[t, 0]
-            res.append(loop(ol, law, batch, t, Xr, Ur, g, x0, opts, 0, Rtab, gm, None, noisy=False, **kw))
-        else:
-            res.append(loop(ol, law, batch, t, Xr, Ur, g, x0_sim[t, m], opts, id0[t] + m, Rtab, gm, None if plant is None else plant[t, m],
-                            bias=None if sensor is None else sensor[t, m], **kw))
-    pairs = np.asarray(pairs)
-    Xs = np.stack([r[0] for r in res])
-    nk = ec.horizons(batch)[pairs[:, 0]]
-    xf = batch.xf[pairs[:, 0]]
-    st = dc.stats_of(abi, Xs, xf, nk, batch.dt[pairs[:, 0]], opts.min_steps, opts.w_tol, opts.angle_tol)
-    return dict(X_sim=Xs, stats=st, n_sure=np.array([r[1][0] for r in res]), n_maybe=np.array([r[1][1] for r in res]), xf=xf, n_knots=nk,
-                U_cmd=np.stack([r[2] for r in res]), X_hat=np.stack([r[3] for r in res]), filt_final=np.stack([r[4] for r in res]),
-                Y_raw=np.stack([r[5] for r in res]))
+def pairs_of(ol, abi, law, batch, x0_sim, gains, opts, pairs, filt=None, predict=True, update=True, pair_own_row=True, **kw):
+    """``filtered_common.pairs_of`` behind this filter"""
+    return rr.pairs_of(ol, abi, law, batch, x0_sim, gains, opts, pairs, est=estimator(ol, batch, filt, predict, update, pair_own_row), **kw)
 
 
 def conditions(ref_of, sensor, prediction=True, pairing=True):

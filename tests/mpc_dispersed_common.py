@@ -1,9 +1,9 @@
 """Shared pieces of tests/test_mpc_dispersed.py (CPU tier) and tests/test_gpu_mpc_dispersed.py (GPU tier).
 
-THE REFERENCE of the receding-horizon loop on a dispersed plant (tsat_mpc_run_dispersed) is a Python loop built here, control
-step by control step, from the unchanged oracle's primitives only, in the manner of tests/dispersed_common.py: ``ol.solve_batch``
-with the advanced x0, tau0 and warm start; the clip of U[0]; ``ol.plant_noise``, the noise injection and the row lookup of
-``dispersed_common``; ``ol.dyn7(..., Jp)`` per RK4 stage with dipole G u_sat + m_res / u_scale; the plan shifted by one knot
+THE REFERENCE of the receding-horizon loop on a dispersed plant (tsat_mpc_run_dispersed) is a Python loop built control step by
+control step (``reference_rollout.held_loop`` re-planning at every step) from the unchanged oracle's primitives only, in the manner
+of tests/dispersed_common.py: ``ol.solve_batch`` with the advanced x0, tau0 and warm start; the clip of U[0]; ``ol.plant_noise``, the
+noise injection and the row lookup of ``dispersed_common``; ``ol.dyn7`` on Jp per RK4 stage with dipole G u_sat + m_res / u_scale; the plan shifted by one knot
 inside the trajectory's own horizon; ``dispersed_common.stats_of`` on the history. With the model's plant, no noise and no limits
 it has to reproduce ``ol.mpc_batch`` (test_mpc_dispersed.py::test_reference_is_pinned_to_the_oracle_loop).
 
@@ -55,58 +55,14 @@ def plants(pkg, batch, M=None, rng_seed=7):
 
 
 def reference_loop(ol, batch, opts, n_steps, po, plant=None, sat=None, noise_id=None, step0=0, nthreads=4, noise_fn=None):
-    """the loop for the whole batch. plant (T, 21) or None (the model's), sat = (lo, hi) broadcastable to (T, 3) or None,
-    noise_id (T,) or None (= t); noise_fn(t, knot, stage) -> nine values replaces ``ol.plant_noise`` as the source of the draws.
+    """the loop for the whole batch: ``reference_rollout.held_loop`` re-planning at every step (no gains are asked of the solver).
+    plant (T, 21) or None (the model's), sat = (lo, hi) broadcastable to (T, 3) or None, noise_id (T,) or None (= t);
+    noise_fn(t, knot, stage) -> nine values replaces ``ol.plant_noise`` as the source of the draws.
     Returns dict(X_hist, U_hist, stats, X, U of the last solve, tracking_stats, n_sure, n_maybe)."""
-    T = batch.T
-    nk = ec.horizons(batch)
-    us = float(opts.u_scale)
-    noisy = int(po.noise_mode) == 1
-    ids = np.arange(T, dtype=np.int64) if noise_id is None else np.asarray(noise_id, dtype=np.int64)
-    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
-    x, U0, tau = batch.x0.copy(), batch.U0.copy(), batch.tau0.copy()
-    Xh, Uh = np.zeros((T, n_steps + 1, 7)), np.zeros((T, n_steps, 3))
-    n_sure, n_maybe = np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
-    ol.load()
-    for s in range(n_steps):
-        b2 = batch.slice(0, T)
-        b2.x0, b2.U0, b2.tau0 = np.ascontiguousarray(x), np.ascontiguousarray(U0), np.ascontiguousarray(tau)
-        r = ol.solve_batch(b2, opts, nthreads=min(nthreads, ol.num_procs()), want_K=False)
-        Xh[:, s] = x
-        for t in range(T):
-            if plant is None:
-                Jp, G, mres = np.asarray(batch.Jmat[t]).reshape(3, 3).T, np.eye(3), np.zeros(3)
-            else:
-                Jp, G, mres = plant[t, 0:9].reshape(3, 3).T, plant[t, 9:18].reshape(3, 3).T, plant[t, 18:21]
-            u = r["U"][t, 0].copy()
-            if lo is not None:
-                bl, bh = CLIP_BAND * np.abs(lo[t]), CLIP_BAND * np.abs(hi[t])
-                n_sure[t] += bool(np.any((lo[t] - u > bl) | (u - hi[t] > bh)))
-                n_maybe[t] += bool(np.any((lo[t] - u > -bl) | (u - hi[t] > -bh)))
-                u = np.minimum(np.maximum(u, lo[t]), hi[t])
-            Uh[t, s] = u
-            ua = G @ u + mres / us
-            draw = noise_fn or (lambda t_, k_, st_: ol.plant_noise(int(po.noise_seed), int(ids[t_]), k_, st_, po.sigma_gyro,
-                                                                    po.sigma_att, po.field_amp))
-            nz = [draw(t, int(step0) + s, st) if noisy else None for st in range(4)]
-            b0, b1, b2r = dc._row(b2, t, 0, 0.0), dc._row(b2, t, 0, 0.5), dc._row(b2, t, 0, 1.0)
-            h = float(batch.dt[t])
-
-            def f(xx, bb, n):
-                xn, bn = dc._noisy(ol, xx, bb, n)
-                return h * ol.dyn7(xn, ua, bn, Jp, us)
-
-            k1 = f(x[t], b0, nz[0])
-            k2 = f(x[t] + k1 / 2, b1, nz[1])
-            k3 = f(x[t] + k2 / 2, b1, nz[2])
-            k4 = f(x[t] + k3, b2r, nz[3])
-            x[t] = x[t] + (k1 + 2 * k2 + 2 * k3 + k4) / 6
-            n = int(nk[t])                                   # the shift inside the trajectory's own horizon, last control repeated
-            U0[t, :n - 1] = np.concatenate([r["U"][t, 1:n - 1], r["U"][t, n - 2:n - 1]], axis=0)
-        tau = tau + batch.dtau
-    Xh[:, n_steps] = x
-    ts = dc.stats_of(ol._abi, Xh, batch.xf, np.full(T, n_steps + 1), batch.dt, po.min_steps, po.w_tol, po.angle_tol)
-    return dict(X_hist=Xh, U_hist=Uh, stats=r["stats"], X=r["X"], U=r["U"], tracking_stats=ts, n_sure=n_sure, n_maybe=n_maybe)
+    import reference_rollout as rr          # here: that module is built on this one's parents
+    r = rr.held_loop(ol, batch, opts, n_steps, 1, 0, po, plant=plant, sat=sat, noise_id=noise_id, step0=step0, nthreads=nthreads,
+                     want_K=False, noise_fn=noise_fn)
+    return {k: r[k] for k in ("X_hist", "U_hist", "stats", "X", "U", "tracking_stats", "n_sure", "n_maybe")}
 
 
 def margins(ref, batch, po):

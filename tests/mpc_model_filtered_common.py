@@ -1,9 +1,10 @@
 """Shared pieces of tests/test_mpc_model_filtered.py (CPU tier) and tests/test_gpu_mpc_model_filtered.py (GPU tier): the held
 re-planning loop BEHIND THE NINE-STATE FILTER (tsat_mpc_run_held_model_filtered).
 
-THE REFERENCE (``reference_loop``) is ``mpc_filtered_common.reference_loop`` restated with ``model_filtered_common.ModelEkf`` — the
-recursion of include/tortoise_hip.h, line for line — between ``measure`` and solver / gains: numpy and the oracle's primitives only.
-Per control step s, counted FROM THE CALL, the raw sample the sensor hands over (m_s, or m_max(s-1, 0) at latency 1) meets
+THE REFERENCE (``reference_loop``) is ``reference_rollout.held_loop`` with ``model_filtered_common.ModelEkf`` — the recursion of
+include/tortoise_hip.h, line for line — between ``measure`` and solver / gains: numpy and the oracle's primitives only. Per control
+step s, counted FROM THE CALL, the raw sample the sensor hands over (m_s, or m_max(s-1, 0) at latency 1) meets
+(``reference_rollout.ModelState``)
 
     latency 0:  s = 0 first(m_0);  s >= 1 predict(u_{s-1}, rows_{s-1}), update(m_s);            y_s = (w^, q^)
     latency 1:  s = 0 first(m_0);  s = 1 predict(u_0, rows_0) and no update;  s >= 2 update(m_{s-1}), predict(u_{s-1}, rows_{s-1});
@@ -35,21 +36,18 @@ import types
 
 import numpy as np
 
-import dispersed_common as dc
-import ensemble_common as ec
 import gg_common as gc
 import model_filtered_common as mm
 import mpc_filtered_common as mf6
 import mpc_held_common as hc
 import mpc_sensed_common as mc
-import sensed_common as sc
+import reference_rollout as rr
 from conftest import ROOT
 
 FILT = mm.FILT
 STATE_W, FINAL_W = 58, 12
 EST_BAR = mf6.EST_BAR        # Y_hist, filt_state, filt_final: the state bar of the sensed and filtered tests (1e-9)
 VARIANT = dict(command=True, predict=True, rows="flown", inertia="model")
-_IU = np.triu_indices(3)
 
 
 ROW_DT = 10.0                # seconds of orbit per field row in the tests' tables (``coarse_rows``)
@@ -65,166 +63,27 @@ def coarse_rows(pkg, batch, dt_row=ROW_DT):
     return batch
 
 
-def _variant(v):
-    """the ModelEkf's own switches of a VARIANT of this module"""
-    return dict(mm.VARIANT, command=v["command"])
+def estimator(ol, batch, us, filt, plant=None, filt_init=None, variant=VARIANT):
+    """t -> the estimator of trajectory t: ``model_filtered_common.ModelEkf`` behind ``reference_rollout.ModelState``, resumed from
+    the record filt_init[t] where one is given. ``filt`` None: no filter. Of ``variant`` the filter takes ``command`` and its
+    inertia, the adapter ``predict`` and ``rows``"""
+    if filt is None:
+        return None
 
+    def make(t):
+        J = plant[t, 0:9].reshape(3, 3).T if variant["inertia"] == "plant" else np.asarray(batch.Jmat[t]).reshape(3, 3).T
+        ekf = mm.ModelEkf(ol, batch.dt[t], J, us, filt, dict(mm.VARIANT, command=variant["command"]))
+        return rr.ModelState(ekf, variant["predict"], variant["rows"], None if filt_init is None else filt_init[t], FINAL_W)
 
-def record_of(ekf):
-    """the flat record of a ``ModelEkf`` (``ekf.u``: the command of its last predict)"""
-    P = ekf.P
-    return np.r_[ekf.q, ekf.w, ekf.b, ekf.u, P[0:3, 0:3][_IU], P[3:6, 3:6][_IU], P[6:9, 6:9][_IU], P[0:3, 3:6].reshape(9),
-                 P[0:3, 6:9].reshape(9), P[3:6, 6:9].reshape(9)]
-
-
-def load_record(ekf, rec):
-    rec = np.asarray(rec, dtype=np.float64)
-    ekf.q, ekf.w, ekf.b, ekf.u = rec[0:4].copy(), rec[4:7].copy(), rec[7:10].copy(), rec[10:13].copy()
-    A, W, D = np.zeros((3, 3)), np.zeros((3, 3)), np.zeros((3, 3))
-    A[_IU], W[_IU], D[_IU] = rec[13:19], rec[19:25], rec[25:31]
-    A, W, D = mm._sym(A), mm._sym(W), mm._sym(D)
-    X, B, Y = rec[31:40].reshape(3, 3), rec[40:49].reshape(3, 3), rec[49:58].reshape(3, 3)
-    ekf.P = np.block([[A, X, B], [X.T, W, Y], [B.T, Y.T, D]])
-
-
-def _predict(ekf, flown):
-    u, rows = flown
-    ekf.u = np.array(u, dtype=np.float64)
-    ekf.predict(u, rows)
-
-
-def _sample(ekf, s, latency, m, given, flown, predict=True):
-    """sample handed over at step s of the call through the filter: y_s. ``flown`` = (u, rows) of step s - 1"""
-    if s == 0:
-        if given is None:
-            ekf.first(m[:3], m[3:7])
-            ekf.u = np.zeros(3)
-        else:
-            load_record(ekf, given)
-            ekf.update(m[:3], m[3:7])
-        return np.r_[ekf.w, ekf.q]
-    if latency:
-        if s > 1:
-            ekf.update(m[:3], m[3:7])
-        post = np.r_[ekf.w, ekf.q]
-        _predict(ekf, flown)
-        return np.r_[ekf.w, ekf.q] if predict else post
-    _predict(ekf, flown)
-    ekf.update(m[:3], m[3:7])
-    return np.r_[ekf.w, ekf.q]
-
-
-def _filters(ol, batch, us, filt, plant, variant):
-    out = []
-    for t in range(batch.T):
-        J = np.asarray(batch.Jmat[t]).reshape(3, 3).T
-        if variant["inertia"] == "plant":
-            J = plant[t, 0:9].reshape(3, 3).T
-        out.append(mm.ModelEkf(ol, batch.dt[t], J, us, filt, _variant(variant)))
-    return out
-
-
-def _rows(clock, t):
-    return tuple(dc._row(clock, t, 0, c) for c in (0.0, 0.5, 1.0))
+    return make
 
 
 def reference_loop(ol, batch, opts, n_steps, replan_every, feedback, po, sens=None, bias=None, latency=0, plant=None, sat=None,
                    noise_id=None, step0=0, Rtab=None, gm=0.0, nthreads=4, filt=None, filt_init=None, variant=VARIANT):
     """arguments and result as ``mpc_sensed_common.reference_loop`` plus ``filt`` (the seven levels, None: no filter — the sensed
     reference itself), ``filt_init`` (T, 58) or None, ``variant``; and ``filt_state`` (T, 58), ``filt_final`` (T, 12)"""
-    T, R = batch.T, int(replan_every)
-    sens = mc.IDEAL if sens is None else sens
-    nk = ec.horizons(batch)
-    us = float(opts.u_scale)
-    es = int(opts.error_state)
-    nh = 6 if es else 7
-    noisy = int(po.noise_mode) == 1
-    ids = np.arange(T, dtype=np.int64) if noise_id is None else np.asarray(noise_id, dtype=np.int64)
-    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
-    x, U0, tau = batch.x0.copy(), batch.U0.copy(), batch.tau0.copy()          # x: the TRUE state
-    y, held = np.zeros((T, 7)), [None] * T                                    # y: what the solver and the gains are given
-    ekf = None if filt is None else _filters(ol, batch, us, filt, plant, variant)
-    flown = [None] * T                                                        # (limited command, field rows) of the step before
-    Xh, Uh, Yh = np.zeros((T, n_steps + 1, 7)), np.zeros((T, n_steps, 3)), np.zeros((T, n_steps, 7))
-    n_sure, n_maybe = np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
-    statuses, tally = [], np.zeros((T, 4), dtype=np.int64)
-    ol.load()
-    for sb in range(0, n_steps, R):
-        r_len = min(R, n_steps - sb)
-        for j in range(r_len):
-            s = sb + j
-            clock = types.SimpleNamespace(dtau=batch.dtau, tau0=tau, Btab=batch.Btab, btab_idx=batch.btab_idx, n_tab=batch.n_tab)
-            for t in range(T):                               # the sample handed over: m_s, or m_max(s-1, 0); s counts from the call
-                w_m, q_m, _ = sc.measure(ol, clock, t, int(step0) + s, x[t], po, ids[t], sens, None if bias is None else bias[t], noisy)
-                m = np.r_[w_m, q_m]
-                y[t] = held[t] if (latency and s > 0) else m
-                held[t] = m
-                if ekf is not None:                          # the filter between the sample and everything that reads y
-                    fl = flown[t]
-                    if s > 0 and variant["rows"] == "next":  # the off-by-one: the rows of THIS step's clock
-                        fl = (fl[0], _rows(clock, t))
-                    y[t] = _sample(ekf[t], s, latency, y[t], None if filt_init is None else filt_init[t], fl, variant["predict"])
-            if j == 0:                                       # the block's solve starts from the estimate
-                b2 = batch.slice(0, T)
-                b2.x0, b2.U0, b2.tau0 = np.ascontiguousarray(y), np.ascontiguousarray(U0), np.ascontiguousarray(tau)
-                r = ol.solve_batch(b2, opts, nthreads=min(nthreads, ol.num_procs()), want_K=True)
-                statuses.append(r["stats"]["status"].copy())
-                rs = r["stats"]
-                tally += np.stack([rs["n_backward"], rs["n_forward"], np.maximum(rs["outer_iters"] - 1, 0), rs["inner_iters"]], axis=1)
-            Xh[:, s] = x
-            Yh[:, s] = y
-            for t in range(T):
-                if plant is None:
-                    Jp, G, mres = np.asarray(batch.Jmat[t]).reshape(3, 3).T, np.eye(3), np.zeros(3)
-                else:
-                    Jp, G, mres = plant[t, 0:9].reshape(3, 3).T, plant[t, 9:18].reshape(3, 3).T, plant[t, 18:21]
-                u = r["U"][t, j].copy()
-                if j > 0 and feedback:
-                    dx = ol.quaternion_error(y[t], r["X"][t, j]) if es else y[t] - r["X"][t, j]
-                    for a in range(3):
-                        v = float(u[a])
-                        for i in range(nh):
-                            v += float(r["K"][t, j, i, a]) * float(dx[i])
-                        u[a] = v
-                if lo is not None:
-                    bl, bh = hc.CLIP_BAND * np.abs(lo[t]), hc.CLIP_BAND * np.abs(hi[t])
-                    n_sure[t] += bool(np.any((lo[t] - u > bl) | (u - hi[t] > bh)))
-                    n_maybe[t] += bool(np.any((lo[t] - u > -bl) | (u - hi[t] > -bh)))
-                    u = np.minimum(np.maximum(u, lo[t]), hi[t])
-                Uh[t, s] = u
-                ua = G @ u + mres / us
-                nz = [ol.plant_noise(int(po.noise_seed), int(ids[t]), int(step0) + s, st, po.sigma_gyro, po.sigma_att, po.field_amp)
-                      if noisy else None for st in range(4)]
-                b0, b1, b2r = _rows(clock, t)
-                flown[t] = (np.array(u, dtype=np.float64), (b0, b1, b2r))     # what the filter's next predict crosses
-                rr = [None] * 3 if Rtab is None else [gc._grow(clock, Rtab, t, 0, c) for c in (0.0, 0.5, 1.0)]
-                h = float(batch.dt[t])
-
-                def f(xx, bb, n, rk):
-                    xn, bn = dc._noisy(ol, xx, bb, n)
-                    kk = h * ol.dyn7(xn, ua, bn, Jp, us)
-                    if rk is not None:
-                        kk[0:3] = kk[0:3] + gc.gg_increment(ol, xx, rk, gm, Jp, h)
-                    return kk
-
-                k1 = f(x[t], b0, nz[0], rr[0])
-                k2 = f(x[t] + k1 / 2, b1, nz[1], rr[1])
-                k3 = f(x[t] + k2 / 2, b1, nz[2], rr[1])
-                k4 = f(x[t] + k3, b2r, nz[3], rr[2])
-                x[t] = x[t] + (k1 + 2 * k2 + 2 * k3 + k4) / 6
-            tau = tau + batch.dtau                           # one rounded addition per step
-        for t in range(T):                                   # the shift by the block's steps inside the trajectory's own horizon
-            n = int(nk[t])
-            U0[t, :n - 1] = r["U"][t, np.minimum(np.arange(n - 1) + r_len, n - 2)]
-    Xh[:, n_steps] = x
-    ts = dc.stats_of(ol._abi, Xh, batch.xf, np.full(T, n_steps + 1), batch.dt, po.min_steps, po.w_tol, po.angle_tol)
-    out = dict(X_hist=Xh, U_hist=Uh, Y_hist=Yh, stats=r["stats"], X=r["X"], U=r["U"], tracking_stats=ts, n_sure=n_sure, n_maybe=n_maybe,
-               n_solves=len(statuses), statuses=np.array(statuses), tally=tally)
-    if ekf is not None:
-        for t in range(T):                                   # the closing predict across the last step: the prior for x_n
-            _predict(ekf[t], flown[t])
-        out.update(filt_state=np.stack([record_of(e) for e in ekf]), filt_final=np.stack([e.final() for e in ekf]))
-    return out
+    return mc.reference_loop(ol, batch, opts, n_steps, replan_every, feedback, po, sens, bias, latency, plant, sat, noise_id, step0, Rtab,
+                             gm, nthreads, estimator(ol, batch, float(opts.u_scale), filt, plant, filt_init, variant))
 
 
 def estimates(ol, batch, us, filt, handed, U_hist, latency, filt_init=None):
@@ -234,18 +93,21 @@ def estimates(ol, batch, us, filt, handed, U_hist, latency, filt_init=None):
     plant."""
     T, n = handed.shape[:2]
     Y, S, F = np.zeros((T, n, 7)), np.zeros((T, STATE_W)), np.zeros((T, FINAL_W))
-    ekf = _filters(ol, batch, float(us), filt, None, VARIANT)
+    make = estimator(ol, batch, float(us), filt, None, filt_init)
+    ests = [make(t) for t in range(T)]
     tau = batch.tau0.copy()
-    flown = [None] * T
+    rows_prev = [None] * T
     for s in range(n):
         clock = types.SimpleNamespace(dtau=batch.dtau, tau0=tau, Btab=batch.Btab, btab_idx=batch.btab_idx, n_tab=batch.n_tab)
         for t in range(T):
-            Y[t, s] = _sample(ekf[t], s, latency, handed[t, s], None if filt_init is None else filt_init[t], flown[t])
-            flown[t] = (U_hist[t, s], _rows(clock, t))
+            rows = rr.rows_of(clock, t, 0)
+            Y[t, s] = np.r_[ests[t].sample(s, latency, handed[t, s, :3], handed[t, s, 3:7], None, None, rows, rows_prev[t],
+                                           U_hist[t, s - 1] if s else None)]
+            rows_prev[t] = rows
         tau = tau + batch.dtau
     for t in range(T):
-        _predict(ekf[t], flown[t])
-        S[t], F[t] = record_of(ekf[t]), ekf[t].final()
+        ests[t].flown(U_hist[t, n - 1], rows_prev[t])
+        S[t], F[t] = ests[t].record(), ests[t].final()
     return Y, S, F
 
 
@@ -306,35 +168,9 @@ class EmuMpcModelFiltered:
             step0=0, Rtab=None, gm=0.0, filt=FILT, filt_init=None):
         """emu_mpc_held_model_filtered_batch; the result of ``mpc_sensed_common.EmuMpcSensed.run`` plus filt_state (T, 58) and
         filt_final (T, 12), both None with ``filt`` None (f = NULL)"""
-        T, N = batch.T, batch.N
-        o = opts.copy()
-        o.n_knots, o.n_tab = N, batch.n_tab
-        c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-        plant, Rtab, bias, filt_init = c(plant), c(Rtab), c(bias), c(filt_init)
-        so = sc.sensor_options(self.abi, mc.IDEAL if sens is None else sens, latency)
         fo = None if filt is None else mm.filter_options(self.abi, filt)
-        lo, hi = (None, None) if sat is None else (c(np.broadcast_to(sat[0], (T, 3))), c(np.broadcast_to(sat[1], (T, 3))))
-        ids = None if noise_id is None else np.ascontiguousarray(noise_id, dtype=np.int64)
-        Xh = np.zeros((T, n_steps + 1, 7)); Uh = np.zeros((T, n_steps, 3)); Yh = np.full((T, n_steps, 7), np.nan)
-        X = np.zeros((T, N, 7)); U = np.zeros((T, N - 1, 3)); x0a = np.zeros((T, 7))
-        fs = None if fo is None else np.full((T, STATE_W), np.nan)
-        ff = None if fo is None else np.full((T, FINAL_W), np.nan)
-        st = np.zeros(T, dtype=self.abi.STATS_DTYPE)
-        ts = np.zeros(T, dtype=self.abi.TVLQR_STATS_DTYPE)
-        ncl = np.full(T, -1, dtype=np.int32)
-        d = self.abi.as_dp
-        rc = self.lib.emu_mpc_held_model_filtered_batch(
-            C.byref(o), C.byref(po), C.c_int64(T), C.c_int64(batch.Btab.shape[0]), d(batch.x0), d(batch.xf), d(batch.Btab),
-            self.abi.as_ip(batch.btab_idx), d(batch.tau0), d(batch.dtau), d(batch.dt), d(batch.Jmat), d(batch.Qd), d(batch.Qfd),
-            d(batch.Rd), d(batch.ulo), d(batch.uhi), d(batch.U0), C.c_int32(n_steps), C.c_int64(step0), C.c_int32(replan_every),
-            C.c_int32(feedback), d(plant), d(lo), d(hi), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int64)), d(Xh), d(Uh),
-            st.ctypes.data_as(C.c_void_p), ts.ctypes.data_as(C.c_void_p), self.abi.as_ip(ncl), d(X), d(U),
-            None if batch.n_knots is None else self.abi.as_ip(np.ascontiguousarray(batch.n_knots, dtype=np.int32)), d(Rtab),
-            C.c_double(gm), C.byref(so), d(bias), d(Yh), None if fo is None else C.byref(fo), d(filt_init), d(fs), d(ff), d(x0a))
-        if rc != 0:
-            raise RuntimeError(f"emu_mpc_held_model_filtered_batch rc={rc}")
-        return dict(X_hist=Xh, U_hist=Uh, Y_hist=Yh, stats=st, X=X, U=U, tracking_stats=ts, n_clipped=ncl, x0_after=x0a, filt_state=fs,
-                    filt_final=ff)
+        return mf6.filtered_run(self.lib.emu_mpc_held_model_filtered_batch, self.abi, fo, (STATE_W, FINAL_W), filt_init, batch, opts, po,
+                                n_steps, replan_every, feedback, sens, bias, latency, plant, sat, noise_id, step0, Rtab, gm)
 
     def check(self, fo, filt_init, T, filt_state=None, filt_final=None):
         """check_mpc_model_filtered on the arguments tsat_mpc_run_held_model_filtered adds"""

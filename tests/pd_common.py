@@ -15,7 +15,6 @@ Also: the argument list of the entry point as named fields (``Call``), which the
 to the library's own validation function — through the emulator driver (``EmuPd.check``) on the CPU tier, through
 tsat_pd_ensemble itself on the GPU tier —, and the ctypes binding of the emulated kernels (tests/emu/tsat_emu_pd.cpp)."""
 import ctypes as C
-import math
 import os
 import subprocess
 
@@ -56,95 +55,20 @@ def options(ol):
 
 def reference_loop(ol, batch, t, Xr, Ur, kd, kp, x0, opts, gid, Rtab, gm, plant=None, lo=None, hi=None, limit_mode=0, noisy=True,
                    sign_rule=True, k_start=0, k_stop=None):
-    """one closed loop of slew t under the law. Xr (N, 7) or None (regulation: the record of every knot is xf), Ur (N-1, 3) or None
-    (no feed-forward), kd / kp (3,), Rtab (n_btab, n_tab, 3) or None (no gravity-gradient term); ``sign_rule=False`` forces s = +1.
-    Returns X_sim (N, 7) zero-filled beyond the horizon, (n_sure, n_maybe), the commands before the limit (N-1, 3) and the beta of every knot
-    (mode 1)."""
-    NS = batch.N
-    N = NS if batch.n_knots is None else int(batch.n_knots[t])
-    us, h = float(opts.u_scale), float(batch.dt[t])
-    if plant is None:
-        Jp, G, mres = np.asarray(batch.Jmat[t]).reshape(3, 3).T, np.eye(3), np.zeros(3)
-    else:
-        Jp, G, mres = plant[0:9].reshape(3, 3).T, plant[9:18].reshape(3, 3).T, plant[18:21]
-    Xs, Uc = np.zeros((NS, 7)), np.zeros((NS - 1, 3))
-    x = np.array(x0, dtype=np.float64)
-    n_sure = n_maybe = 0
-    betas = []
-    for k in range(k_start, N - 1 if k_stop is None else min(N - 1, k_stop)):      # k_start > 0: x0 is the state at that knot
-        Xs[k] = x
-        xr = batch.xf[t] if Xr is None else Xr[k]
-        b0, b1, b2 = dc._row(batch, t, k, 0.0), dc._row(batch, t, k, 0.5), dc._row(batch, t, k, 1.0)
-        qe = ol.qmult(np.r_[xr[3], -xr[4:7]], x[3:7])
-        dw = x[:3] - xr[:3]
-        s = -1.0 if (sign_rule and qe[0] < 0) else 1.0
-        treq = -(kd * dw + kp * (s * qe[1:4]))
-        bb_ = ol.qrot(x[3:7] / math.sqrt(float(x[3:7] @ x[3:7])), b0)
-        bb = float(bb_ @ bb_)
-        m = np.cross(bb_, treq) / bb if bb != 0.0 else np.zeros(3)
-        u = (Ur[k] if Ur is not None else np.zeros(3)) + m / us
-        Uc[k] = u
-        if limit_mode == 1:
-            r = np.array([u[c] / hi[c] if u[c] > 0 else (u[c] / lo[c] if u[c] < 0 else 0.0) for c in range(3)])
-            beta = float(r.max())
-            betas.append(beta)
-            n_sure += bool(beta - 1.0 > dc.CLIP_BAND)
-            n_maybe += bool(beta - 1.0 > -dc.CLIP_BAND)
-            if beta > 1.0:
-                u = u * (1.0 / beta)
-        elif lo is not None:
-            bl, bh = dc.CLIP_BAND * np.abs(lo), dc.CLIP_BAND * np.abs(hi)
-            n_sure += bool(np.any((lo - u > bl) | (u - hi > bh)))
-            n_maybe += bool(np.any((lo - u > -bl) | (u - hi > -bh)))
-            u = np.minimum(np.maximum(u, lo), hi)
-        ua = G @ u + mres / us
-        nz = [ol.plant_noise(int(opts.noise_seed), int(gid), k, st, opts.sigma_gyro, opts.sigma_att, opts.field_amp) if noisy else None
-              for st in range(4)]
-        rr = [None] * 3 if Rtab is None else [gc._grow(batch, Rtab, t, k, c) for c in (0.0, 0.5, 1.0)]
-
-        def f(xx, bb, n, r):
-            xn, bn = dc._noisy(ol, xx, bb, n)
-            kk = h * ol.dyn7(xn, ua, bn, Jp, us)
-            if r is not None:
-                kk[0:3] = kk[0:3] + gc.gg_increment(ol, xx, r, gm, Jp, h)
-            return kk
-
-        k1 = f(x, b0, nz[0], rr[0])
-        k2 = f(x + k1 / 2, b1, nz[1], rr[1])
-        k3 = f(x + k2 / 2, b1, nz[2], rr[1])
-        k4 = f(x + k3, b2, nz[3], rr[2])
-        x = x + (k1 + 2 * k2 + 2 * k3 + k4) / 6
-    Xs[N - 1 if k_stop is None else min(N - 1, k_stop)] = x
-    return Xs, (n_sure, n_maybe), Uc, betas
+    """one closed loop of slew t under the law, on the true state: ``reference_rollout.ensemble_loop``. Returns X_sim (N, 7)
+    zero-filled beyond the horizon, (n_sure, n_maybe), the commands before the limit (N-1, 3) and the beta of every knot (mode 1)."""
+    import reference_rollout as rr          # here: that module is built on this one's parents
+    return rr.ensemble_loop(ol, "pd", batch, t, Xr, Ur, (kd, kp), x0, opts, gid, Rtab, gm, plant, lo, hi, limit_mode, noisy,
+                            sign_rule=sign_rule, k_start=k_start, k_stop=k_stop)[:4]
 
 
 def reference_pairs(ol, abi, batch, x0_sim, kd, kp, opts, pairs, X=None, U=None, Rtab=None, gm=0.0, plant=None, sat=None, limit_mode=0,
                     x0_nom=None, noise_id0=None, sign_rule=True):
     """the reference on the (t, m) pairs (n, 2); m = -1 is the noise-free MODEL plant from x0_nom[t] (default X[t, 0]). kd / kp
-    (T, 3) or (3,). Returns the dict of ``gg_common.ensemble_pairs`` plus U_cmd (n, N-1, 3) and betas (list per pair)."""
-    T, M = x0_sim.shape[:2]
-    kd, kp = np.broadcast_to(kd, (T, 3)), np.broadcast_to(kp, (T, 3))
-    id0 = np.arange(T, dtype=np.int64) * M if noise_id0 is None else np.asarray(noise_id0, dtype=np.int64)
-    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
-    ol.load()
-    res = []
-    for p in pairs:
-        t, m = int(p[0]), int(p[1])
-        kw = dict(lo=None if lo is None else lo[t], hi=None if hi is None else hi[t], limit_mode=limit_mode, sign_rule=sign_rule)
-        Xr, Ur = None if X is None else X[t], None if U is None else U[t]
-        if m < 0:
-            x0 = x0_nom[t] if x0_nom is not None else X[t, 0]
-            res.append(reference_loop(ol, batch, t, Xr, Ur, kd[t], kp[t], x0, opts, 0, Rtab, gm, None, noisy=False, **kw))
-        else:
-            res.append(reference_loop(ol, batch, t, Xr, Ur, kd[t], kp[t], x0_sim[t, m], opts, id0[t] + m, Rtab, gm,
-                                      None if plant is None else plant[t, m], **kw))
-    pairs = np.asarray(pairs)
-    Xs = np.stack([r[0] for r in res])
-    nk = ec.horizons(batch)[pairs[:, 0]]
-    xf = batch.xf[pairs[:, 0]]
-    st = dc.stats_of(abi, Xs, xf, nk, batch.dt[pairs[:, 0]], opts.min_steps, opts.w_tol, opts.angle_tol)
-    return dict(X_sim=Xs, stats=st, n_sure=np.array([r[1][0] for r in res]), n_maybe=np.array([r[1][1] for r in res]), xf=xf, n_knots=nk,
-                U_cmd=np.stack([r[2] for r in res]), betas=[r[3] for r in res])
+    (T, 3) or (3,). Returns the dict of ``reference_rollout.pairs_of``."""
+    import reference_rollout as rr
+    return rr.pairs_of(ol, abi, "pd", batch, x0_sim, (kd, kp), opts, pairs, X=X, U=U, Rtab=Rtab, gm=gm, plant=plant, sat=sat,
+                       limit_mode=limit_mode, x0_nom=x0_nom, noise_id0=noise_id0, sign_rule=sign_rule)
 
 
 def finals(r):

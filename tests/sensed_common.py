@@ -23,8 +23,6 @@ import subprocess
 import numpy as np
 
 import dispersed_common as dc
-import ensemble_common as ec
-import gg_common as gc
 import pd_common as pc
 from conftest import ROOT
 
@@ -60,111 +58,19 @@ def measure(ol, batch, t, k, x, opts, gid, sens, bias, noisy):
 
 def loop(ol, law, batch, t, Xr, Ur, gains, x0, opts, gid, Rtab, gm, plant=None, lo=None, hi=None, limit_mode=0, noisy=True, sens=None,
          latency=0, bias=None, k_start=0, k_stop=None, x_before=None):
-    """one closed loop of slew t. law "tv": gains = K (N-1, 6, 3), the loop of gg_common.ensemble_loop; law "pd": gains = (kd, kp),
-    Xr None regulates, Ur None flies no feed-forward, the loop of pd_common.reference_loop. ``sens`` None: the parent's own command
-    line from the true state. k_start > 0: x0 is the state at that knot and ``x_before`` the state one knot earlier (latency 1).
-    Returns X_sim (N, 7) zero-filled beyond the horizon, (n_sure, n_maybe), the commands before the limit (N-1, 3)."""
-    NS = batch.N
-    N = NS if batch.n_knots is None else int(batch.n_knots[t])
-    us, h = float(opts.u_scale), float(batch.dt[t])
-    if plant is None:
-        Jp, G, mres = np.asarray(batch.Jmat[t]).reshape(3, 3).T, np.eye(3), np.zeros(3)
-    else:
-        Jp, G, mres = plant[0:9].reshape(3, 3).T, plant[9:18].reshape(3, 3).T, plant[18:21]
-    Xs, Uc = np.zeros((NS, 7)), np.zeros((NS - 1, 3))
-    x = np.array(x0, dtype=np.float64)
-    n_sure = n_maybe = 0
-    held = None
-    if sens is not None and latency and k_start > 0:
-        held = measure(ol, batch, t, k_start - 1, np.asarray(x_before, dtype=np.float64), opts, gid, sens, bias, noisy)
-    last = N - 1 if k_stop is None else min(N - 1, k_stop)
-    for k in range(k_start, last):
-        Xs[k] = x
-        xr = batch.xf[t] if Xr is None else Xr[k]
-        b0, b1, b2 = dc._row(batch, t, k, 0.0), dc._row(batch, t, k, 0.5), dc._row(batch, t, k, 1.0)
-        if sens is None:
-            w_m, q_m = x[:3], x[3:7]
-            b_m = ol.qrot(x[3:7] / math.sqrt(float(x[3:7] @ x[3:7])), b0) if law == "pd" else None
-        else:
-            y = measure(ol, batch, t, k, x, opts, gid, sens, bias, noisy)
-            w_m, q_m, b_m = held if (latency and held is not None) else y       # y_max(k-1, 0)
-            held = y
-        qe = ol.qmult(np.r_[xr[3], -xr[4:7]], q_m)
-        if law == "tv":
-            dX = np.r_[w_m - xr[:3], qe[1:4]]
-            u = Ur[k] - gains[k].T @ dX
-        else:
-            kd, kp = gains
-            dw = w_m - xr[:3]
-            s = -1.0 if qe[0] < 0 else 1.0
-            treq = -(kd * dw + kp * (s * qe[1:4]))
-            bb = float(b_m @ b_m)
-            m = np.cross(b_m, treq) / bb if bb != 0.0 else np.zeros(3)
-            u = (Ur[k] if Ur is not None else np.zeros(3)) + m / us
-        Uc[k] = u
-        if limit_mode == 1:
-            r = np.array([u[c] / hi[c] if u[c] > 0 else (u[c] / lo[c] if u[c] < 0 else 0.0) for c in range(3)])
-            beta = float(r.max())
-            n_sure += bool(beta - 1.0 > dc.CLIP_BAND)
-            n_maybe += bool(beta - 1.0 > -dc.CLIP_BAND)
-            if beta > 1.0:
-                u = u * (1.0 / beta)
-        elif lo is not None:
-            bl, bh = dc.CLIP_BAND * np.abs(lo), dc.CLIP_BAND * np.abs(hi)
-            n_sure += bool(np.any((lo - u > bl) | (u - hi > bh)))
-            n_maybe += bool(np.any((lo - u > -bl) | (u - hi > -bh)))
-            u = np.minimum(np.maximum(u, lo), hi)
-        ua = G @ u + mres / us
-        nz = [ol.plant_noise(int(opts.noise_seed), int(gid), k, st, opts.sigma_gyro, opts.sigma_att, opts.field_amp) if noisy else None
-              for st in range(4)]
-        rr = [None] * 3 if Rtab is None else [gc._grow(batch, Rtab, t, k, c) for c in (0.0, 0.5, 1.0)]
-
-        def f(xx, bb_, n, r):
-            xn, bn = dc._noisy(ol, xx, bb_, n)
-            kk = h * ol.dyn7(xn, ua, bn, Jp, us)
-            if r is not None:
-                kk[0:3] = kk[0:3] + gc.gg_increment(ol, xx, r, gm, Jp, h)
-            return kk
-
-        k1 = f(x, b0, nz[0], rr[0])
-        k2 = f(x + k1 / 2, b1, nz[1], rr[1])
-        k3 = f(x + k2 / 2, b1, nz[2], rr[1])
-        k4 = f(x + k3, b2, nz[3], rr[2])
-        x = x + (k1 + 2 * k2 + 2 * k3 + k4) / 6
-    Xs[last] = x
-    return Xs, (n_sure, n_maybe), Uc
+    """one closed loop of slew t fed measurements: ``reference_rollout.ensemble_loop`` with no filter. Returns X_sim (N, 7)
+    zero-filled beyond the horizon, (n_sure, n_maybe), the commands before the limit (N-1, 3)."""
+    import reference_rollout as rr          # here: that module is built on this one
+    return rr.ensemble_loop(ol, law, batch, t, Xr, Ur, gains, x0, opts, gid, Rtab, gm, plant, lo, hi, limit_mode, noisy, sens, latency,
+                            bias, k_start=k_start, k_stop=k_stop, x_before=x_before)[:3]
 
 
 def pairs_of(ol, abi, law, batch, x0_sim, gains, opts, pairs, X=None, U=None, Rtab=None, gm=0.0, plant=None, sat=None, limit_mode=0,
              x0_nom=None, noise_id0=None, sens=None, latency=0, sensor=None):
-    """the reference on the (t, m) pairs (n, 2); m = -1 is the noise-free MODEL plant with the ideal sensor at the call's latency, from
-    x0_nom[t] (default X[t, 0]). gains: K (T, N-1, 6, 3) for "tv", (kd, kp) each (T, 3) or (3,) for "pd". Returns the dict of
-    ``gg_common.ensemble_pairs`` plus U_cmd (n, N-1, 3)."""
-    T, M = x0_sim.shape[:2]
-    id0 = np.arange(T, dtype=np.int64) * M if noise_id0 is None else np.asarray(noise_id0, dtype=np.int64)
-    lo, hi = (None, None) if sat is None else (np.broadcast_to(sat[0], (T, 3)), np.broadcast_to(sat[1], (T, 3)))
-    if law == "pd":
-        gains = (np.broadcast_to(gains[0], (T, 3)), np.broadcast_to(gains[1], (T, 3)))
-    ol.load()
-    res = []
-    for p in pairs:
-        t, m = int(p[0]), int(p[1])
-        g = gains[t] if law == "tv" else (gains[0][t], gains[1][t])
-        kw = dict(lo=None if lo is None else lo[t], hi=None if hi is None else hi[t], limit_mode=limit_mode, sens=sens, latency=latency)
-        Xr, Ur = None if X is None else X[t], None if U is None else U[t]
-        if m < 0:
-            x0 = x0_nom[t] if x0_nom is not None else X[t, 0]
-            res.append(loop(ol, law, batch, t, Xr, Ur, g, x0, opts, 0, Rtab, gm, None, noisy=False, **kw))
-        else:
-            res.append(loop(ol, law, batch, t, Xr, Ur, g, x0_sim[t, m], opts, id0[t] + m, Rtab, gm, None if plant is None else plant[t, m],
-                            bias=None if sensor is None else sensor[t, m], **kw))
-    pairs = np.asarray(pairs)
-    Xs = np.stack([r[0] for r in res])
-    nk = ec.horizons(batch)[pairs[:, 0]]
-    xf = batch.xf[pairs[:, 0]]
-    st = dc.stats_of(abi, Xs, xf, nk, batch.dt[pairs[:, 0]], opts.min_steps, opts.w_tol, opts.angle_tol)
-    return dict(X_sim=Xs, stats=st, n_sure=np.array([r[1][0] for r in res]), n_maybe=np.array([r[1][1] for r in res]), xf=xf, n_knots=nk,
-                U_cmd=np.stack([r[2] for r in res]))
+    """``reference_rollout.pairs_of`` with no filter"""
+    import reference_rollout as rr
+    return rr.pairs_of(ol, abi, law, batch, x0_sim, gains, opts, pairs, X, U, Rtab, gm, plant, sat, limit_mode, x0_nom, noise_id0, sens,
+                       latency, sensor)
 
 
 def conditions(ref_of, law, sensor):

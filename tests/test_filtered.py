@@ -84,7 +84,7 @@ def _nomp(b):
 
 
 def test_reference_with_the_filter_off_is_the_sensed_reference(pkg, ol, cs):
-    """the anchor: ``filtered_common.loop`` with filt = None is ``sensed_common.loop``, max |d| = 0, both laws and both latencies,
+    """the anchor: ``filtered_common.pairs_of`` with filt = None is ``sensed_common.pairs_of``, max |d| = 0, both laws and both latencies,
     the nominal slot included"""
     b = cs["b"]
     pairs = np.concatenate([dc.all_pairs(b.T, M), _nomp(b)])
@@ -94,7 +94,7 @@ def test_reference_with_the_filter_off_is_the_sensed_reference(pkg, ol, cs):
         old = sc.pairs_of(ol, pkg._abi, "tv", b, cs["x0s"], cs["K"], cs["o"], pairs, X=cs["X"], U=cs["U"], **skw)
         new = _tv_ref(pkg, ol, cs, pairs, kw)
         d = float(np.max(np.abs(old["X_sim"] - new["X_sim"])))
-        print(f"TVLQR reference with the filter off against sensed_common.loop, latency {latency}: max|d| {d:.1e}")
+        print(f"TVLQR reference with the filter off against sensed_common.pairs_of, latency {latency}: max|d| {d:.1e}")
         assert d == 0.0 and np.array_equal(old["stats"], new["stats"]) and np.array_equal(old["U_cmd"], new["U_cmd"])
         assert np.array_equal(old["n_sure"], new["n_sure"]) and np.array_equal(old["n_maybe"], new["n_maybe"])
         assert not new["X_hat"].any() and not new["filt_final"].any()
@@ -104,7 +104,7 @@ def test_reference_with_the_filter_off_is_the_sensed_reference(pkg, ol, cs):
             old = sc.pairs_of(ol, pkg._abi, "pd", b, cs["x0s"], (sc.KD, sc.KP), cs["o"], pairs, **skw)
             new = _pd_ref(pkg, ol, cs, pairs, kw)
             d = float(np.max(np.abs(old["X_sim"] - new["X_sim"])))
-            print(f"PD reference ({kind}, mode {mode}) with the filter off against sensed_common.loop, latency {latency}: max|d| {d:.1e}")
+            print(f"PD reference ({kind}, mode {mode}) with the filter off against sensed_common.pairs_of, latency {latency}: max|d| {d:.1e}")
             assert d == 0.0 and np.array_equal(old["stats"], new["stats"]) and np.array_equal(old["U_cmd"], new["U_cmd"])
             assert np.array_equal(old["n_sure"], new["n_sure"]) and np.array_equal(old["n_maybe"], new["n_maybe"])
 
