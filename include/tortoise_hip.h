@@ -731,6 +731,78 @@ int  tsat_pd_ensemble_mag_filtered(tsat_handle* h, const tsat_tvlqr_options* o, 
                          const tsat_sensor_options* s, const double* sensor,
                          const tsat_mag_filter_options* f, double* X_hat, double* filt_final);
 
+/* The magnetometer-updated filter WITH THE MAGNETOMETER BIAS AS A STATE: the two mag-filtered calls (tsat_mag_filter_options above)
+ * with a nine-state multiplicative EKF — attitude error theta, gyro bias b, magnetometer bias c — between sensor and law. On a
+ * magnetorquer-only satellite the magnetometer sits next to the torquers and a constant bias of several percent of the field is
+ * the normal case; the six-state mag filter lets it enter z unmodelled, this one estimates it (the reference loop of
+ * tests/mag_bias_filtered_common.py, 400 knots, a 3e-6 T bias on a 2.5e-5 T field: rms attitude error over the last half 3.3 deg
+ * against 6.4 deg, |c^ - c| at the end at most 0.28 |c|; the price without a bias at all is 3.0 -> 3.3 deg).
+ * Options (launch-uniform, all standard deviations): those of tsat_mag_filter_options and
+ *   sigma_c   magnetometer-bias random walk per knot              p0_mag    initial magnetometer-bias standard deviation
+ * both in the units of the caller's field table, both >= 0. tsat_mag_bias_filter_default_options fills the figures of
+ * tsat_mag_filter_default_options, sigma_c = p0_mag = 0, and LEAVES sigma_m 0, which the calls reject.
+ * State per realisation, 58 values: q^ 4, b^ 3, w^ 3, c^ 3, and the covariance as 45 values in blocks — the upper triangles of
+ * A (theta theta), D (b b), M (c c) and, row-major 3 x 3, B (theta b), E (theta c), F (b c). Samples m_j = (w_m, q_m, b_m), rows
+ * r_j, h, dq(.), (x), the 3 x 3 inverse by cofactors and the latency rule are the mag filter's, word for word.
+ *   First sample m_0:  as the mag filter — q^ = q_m / |q_m|, b^ = 0, w^ = w_m;  A = p0_att^2 I, B = 0, D = p0_bias^2 I — and
+ *     c^ = 0, M = p0_mag^2 I, E = F = 0. No magnetometer update is made at the first sample.
+ *   Step on sample m_j, j >= 1:
+ *     1. q- and Phi as the mag filter
+ *     2. A-, B-, D- as the mag filter;  E- = Phi E - h F;  F- = F;  M- = M + sigma_c^2 I
+ *     3. n = q- / |q-|;  b^f = qrot(n, r_j);  z = b_m - c^ - b^f;  H = -C(n) [r_j]x;  the measurement matrix is [H 0 I]
+ *     4. Gtheta = A- H^T + E-;  Gb = B-^T H^T + F-;  Gc = E-^T H^T + M-;  S = H Gtheta + Gc + sigma_m^2 I, 3 x 3 (its upper
+ *        triangle, mirrored) and positive definite because sigma_m > 0;  K. = G. S^-1 for each of theta, b and c;
+ *        dtheta, db, dc = K. z
+ *     5. q^, b^ and w^ as the mag filter;  c^ <- c^ + dc
+ *     6. P <- P- - K S K^T by blocks, with W. = K. S: the upper triangles of A, D and M;  B -= Wtheta Kb^T;  E -= Wtheta Kc^T;
+ *        F -= Wb Kc^T
+ *   A ZERO FIELD ROW IS NO LONGER A NO-OP: H = 0 leaves z = b_m - c^ observing c directly. That is correct — the plant's field is
+ *   zero there too, so the reading is bias and noise alone (the last row of a magnetic_simulation table is such a row). Nothing
+ *   asks whether a sigma is zero; with p0_mag = sigma_c = 0 the blocks E, F, M and c^ stay zero and the recursion is the mag
+ *   filter's.
+ *   What the law sees is (w^, q^) by the mag filter's rule, the prediction across the delay and r_{k-1} for the delayed sample
+ *   included. The magnetometer is sampled ONCE per knot; the PD law's b_m is the raw reading the filter used, NOT corrected by c^.
+ *   X_hat       7 x N x M x T or NULL   as the mag-filtered calls'
+ *   filt_final  15 x M x T or NULL      b^ (3), sqrt(diag A) (3), sqrt(diag D) (3), c^ (3), sqrt(diag M) (3) after the last sample
+ *                                       processed (TSAT_MAG_BIAS_FILTER_W)
+ * f == NULL is the sensed call, byte for byte (it is dispatched there); X_hat and filt_final must then be NULL.
+ * Rejected with -1 (text in tsat_ensemble_last_error; nothing is launched and no workspace grows): a non-finite or negative
+ * option; sigma_m == 0; reserved != 0; f NULL with X_hat or filt_final non-NULL; and everything the sensed call rejects. */
+#define TSAT_MAG_BIAS_FILTER_W 15
+struct tsat_mag_bias_filter_options {
+  double  sigma_v;
+  double  sigma_u;
+  double  sigma_m;
+  double  sigma_c;
+  double  p0_att;
+  double  p0_bias;
+  double  p0_mag;
+  int32_t reserved;         /* 0 */
+};
+typedef struct tsat_mag_bias_filter_options tsat_mag_bias_filter_options;
+void tsat_mag_bias_filter_default_options(tsat_mag_bias_filter_options* f);
+int  tsat_tvlqr_ensemble_mag_bias_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                         const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* K_lqr, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor,
+                         const tsat_mag_bias_filter_options* f, double* X_hat, double* filt_final);
+int  tsat_pd_ensemble_mag_bias_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat,
+                         const double* kd, const double* kp, int32_t feedforward, int32_t limit_mode,
+                         const double* x0_sim, const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor,
+                         const tsat_mag_bias_filter_options* f, double* X_hat, double* filt_final);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Receding-horizon re-solve on the RESIDENT batch (BASELINE.json configs[4]). NOT in the reference —
  * it tracks its plan with TVLQR (src/attitude_controller.jl:1-48); defined here as: n_steps times

@@ -633,12 +633,17 @@ end
 # tracking.attitude_ensemble_pd_model_filtered), and so is the held re-planning loop behind that filter
 # (mpc.receding_horizon_held_model_filtered). The mag-filtered ensembles take the sensor struct and a `tsat_mag_filter_options*` (five
 # Float64 — sigma_v, sigma_u, sigma_m, p0_att, p0_bias —, then Int32 reserved: 48 bytes with the tail padding): unbound likewise
-# (tracking.attitude_ensemble_mag_filtered, tracking.attitude_ensemble_pd_mag_filtered).
+# (tracking.attitude_ensemble_mag_filtered, tracking.attitude_ensemble_pd_mag_filtered). The mag-bias-filtered ensembles take the
+# sensor struct and a `tsat_mag_bias_filter_options*` (seven Float64 — sigma_v, sigma_u, sigma_m, sigma_c, p0_att, p0_bias, p0_mag —,
+# then Int32 reserved: 64 bytes with the tail padding): unbound likewise (tracking.attitude_ensemble_mag_bias_filtered,
+# tracking.attitude_ensemble_pd_mag_bias_filtered).
 const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsat_pd_ensemble_sensed, :tsat_mpc_run_held_sensed,
                  :tsat_filter_default_options, :tsat_tvlqr_ensemble_filtered, :tsat_pd_ensemble_filtered,
                  :tsat_mpc_run_held_filtered,
                  :tsat_model_filter_default_options, :tsat_tvlqr_ensemble_model_filtered, :tsat_pd_ensemble_model_filtered,
                  :tsat_mpc_run_held_model_filtered,
-                 :tsat_mag_filter_default_options, :tsat_tvlqr_ensemble_mag_filtered, :tsat_pd_ensemble_mag_filtered]
+                 :tsat_mag_filter_default_options, :tsat_tvlqr_ensemble_mag_filtered, :tsat_pd_ensemble_mag_filtered,
+                 :tsat_mag_bias_filter_default_options, :tsat_tvlqr_ensemble_mag_bias_filtered,
+                 :tsat_pd_ensemble_mag_bias_filtered]
 
 end # module

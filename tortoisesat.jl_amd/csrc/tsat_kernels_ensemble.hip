@@ -1,6 +1,6 @@
-// tsat_kernels_ensemble.hip — the host side of the fourteen ensemble entry points (include/tortoise_hip.h): tsat_tvlqr_ensemble and its
-// _dispersed, _gg, _sensed, _filtered, _model_filtered, _mag_filtered, and tsat_pd_ensemble with its _sensed, _filtered, _model_filtered,
-// _mag_filtered. A
+// tsat_kernels_ensemble.hip — the host side of the sixteen ensemble entry points (include/tortoise_hip.h): tsat_tvlqr_ensemble and its
+// _dispersed, _gg, _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered, and tsat_pd_ensemble with its _sensed,
+// _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered. A
 // translation unit of its own, built on the public ABI: `struct tsat_handle` is private to tsat_kernels.hip, so a call keeps its own
 // buffers and stream. An entry point only describes its call (`Call`: the common arrays, the part of its law, and what it adds —
 // Dispersion, Gravity, Sensing, Filtering); run_call goes through the stages once, all of it synchronous:
@@ -31,6 +31,7 @@
 #include "tsat_filtered.hpp"
 #include "tsat_model_filtered.hpp"
 #include "tsat_mag_filtered.hpp"
+#include "tsat_mag_bias_filtered.hpp"
 #include "tsat_ensemble_launch.hpp"
 
 using namespace tsat;
@@ -140,8 +141,11 @@ struct Filtering {
   double *X_hat, *filt_final;
   const tsat_model_filter_options* mf = nullptr;   // the nine-state filter in place of f
   const tsat_mag_filter_options* gf = nullptr;     // ... or the magnetometer-updated one
-  std::string check() const { return gf ? check_mag_filter(gf) : (mf ? check_model_filter(mf) : check_filter(f)); }
-  size_t final_w() const { return mf ? (size_t)MFFW : (size_t)FFW; }
+  const tsat_mag_bias_filter_options* bf = nullptr;   // ... or the one that estimates the magnetometer bias too
+  std::string check() const {
+    return bf ? check_mag_bias_filter(bf) : (gf ? check_mag_filter(gf) : (mf ? check_model_filter(mf) : check_filter(f)));
+  }
+  size_t final_w() const { return bf ? (size_t)MBFFW : (mf ? (size_t)MFFW : (size_t)FFW); }
 };
 
 // f == NULL is the sensed parent, which has no X_hat and no filt_final to fill
@@ -256,6 +260,7 @@ hipError_t launch_tvlqr(const EnsArgs<double>& a, const DispArgs<double>* d, con
     return hipGetLastError();
   }
   const GgEnsArgs<double> g{*d, GT};
+  if (fl && fl->bf) return tsat_launch_mag_bias_filtered_tv({g, mag_bias_filt_args(*fl->bf, *sa, a, dXH, dFF)}, nw, st);
   if (fl && fl->gf) return tsat_launch_mag_filtered_tv({g, mag_filt_args(*fl->gf, *sa, a, dXH, dFF)}, nw, st);
   if (fl && fl->mf) return tsat_launch_model_filtered_tv({g, model_filt_args(*fl->mf, *sa, a, dXH, dFF)}, nw, st);
   if (fl) return tsat_launch_filtered_tv({g, filt_args(*fl->f, *sa, a, dXH, dFF)}, nw, st);
@@ -267,6 +272,7 @@ hipError_t launch_tvlqr(const EnsArgs<double>& a, const DispArgs<double>* d, con
 
 hipError_t launch_pd(const PdArgs<double>& pa, const SensArgs<double>* sa, const Filtering* fl, double* dXH, double* dFF, int nw,
                      hipStream_t st) {
+  if (fl && fl->bf) return tsat_launch_mag_bias_filtered_pd({pa, mag_bias_filt_args(*fl->bf, *sa, pa.d.e, dXH, dFF)}, nw, st);
   if (fl && fl->gf) return tsat_launch_mag_filtered_pd({pa, mag_filt_args(*fl->gf, *sa, pa.d.e, dXH, dFF)}, nw, st);
   if (fl && fl->mf) return tsat_launch_model_filtered_pd({pa, model_filt_args(*fl->mf, *sa, pa.d.e, dXH, dFF)}, nw, st);
   if (fl) return tsat_launch_filtered_pd({pa, filt_args(*fl->f, *sa, pa.d.e, dXH, dFF)}, nw, st);
@@ -564,6 +570,35 @@ int tsat_pd_ensemble_mag_filtered(tsat_handle* h, const tsat_tvlqr_options* o, i
   return run_call(c);
 }
 
+int tsat_pd_ensemble_mag_bias_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                                       const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                                       const double* dtau, const double* dt, const double* Jmat, const double* kd, const double* kp,
+                                       int32_t feedforward, int32_t limit_mode, const double* x0_sim, const double* x0_nom,
+                                       const int64_t* noise_id0, const int32_t* n_knots, const double* plant, const double* sat_lo,
+                                       const double* sat_hi, tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                                       double* X_sim, int32_t* n_clipped, const double* Rtab, double gm, const tsat_sensor_options* sn,
+                                       const double* sensor, const tsat_mag_bias_filter_options* f, double* X_hat, double* filt_final) {
+  if (!f && unfiltered_outputs(X_hat, filt_final)) return -1;
+  const PdPart law{kd, kp, feedforward, limit_mode, x0_nom};
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  const Sensing se{sn, sensor};
+  const Filtering fl{nullptr, X_hat, filt_final, nullptr, nullptr, f};
+  Call c{f ? "tsat_pd_ensemble_mag_bias_filtered" : "tsat_pd_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt,
+         Jmat, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, X_sim};
+  c.pd = &law; c.disp = &d; c.grav = &g; c.sens = &se; c.filt = f ? &fl : nullptr;
+  return run_call(c);
+}
+
+void tsat_mag_bias_filter_default_options(tsat_mag_bias_filter_options* f) {
+  if (!f) return;
+  tsat_mag_filter_options g;
+  tsat_mag_filter_default_options(&g);                         // the mag filter's figures, sigma_m left 0 and rejected at 0
+  f->sigma_v = g.sigma_v; f->sigma_u = g.sigma_u; f->sigma_m = g.sigma_m; f->p0_att = g.p0_att; f->p0_bias = g.p0_bias;
+  f->sigma_c = 0.0; f->p0_mag = 0.0;                           // in the units of the caller's table: no bias state without them
+  f->reserved = 0;
+}
+
 void tsat_mag_filter_default_options(tsat_mag_filter_options* f) {
   if (!f) return;
   const double pi = 3.14159265358979323846;
@@ -715,6 +750,27 @@ int tsat_tvlqr_ensemble_mag_filtered(tsat_handle* h, const tsat_tvlqr_options* o
   const Filtering fl{nullptr, X_hat, filt_final, nullptr, f};
   Call c{f ? "tsat_tvlqr_ensemble_mag_filtered" : "tsat_tvlqr_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau,
          dt, Jmat, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, X_sim};
+  c.tv = &law; c.disp = &d; c.grav = &g; c.sens = &se; c.filt = f ? &fl : nullptr;
+  return run_call(c);
+}
+
+int tsat_tvlqr_ensemble_mag_bias_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                                          const double* U, const double* xf, const double* Btab, const int32_t* btab_idx,
+                                          const double* tau0, const double* dtau, const double* dt, const double* Jmat, const double* Qd,
+                                          const double* Qfd, const double* Rd, const double* x0_sim, const int64_t* noise_id0,
+                                          const int32_t* n_knots, const double* plant, const double* sat_lo, const double* sat_hi,
+                                          tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr,
+                                          double* X_sim, int32_t* n_clipped, const double* Rtab, double gm, const tsat_sensor_options* sn,
+                                          const double* sensor, const tsat_mag_bias_filter_options* f, double* X_hat,
+                                          double* filt_final) {
+  if (!f && unfiltered_outputs(X_hat, filt_final)) return -1;
+  const TvlqrPart law{Qd, Qfd, Rd, K_lqr};
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  const Sensing se{sn, sensor};
+  const Filtering fl{nullptr, X_hat, filt_final, nullptr, nullptr, f};
+  Call c{f ? "tsat_tvlqr_ensemble_mag_bias_filtered" : "tsat_tvlqr_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0,
+         dtau, dt, Jmat, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, X_sim};
   c.tv = &law; c.disp = &d; c.grav = &g; c.sens = &se; c.filt = f ? &fl : nullptr;
   return run_call(c);
 }

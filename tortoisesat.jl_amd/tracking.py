@@ -375,7 +375,8 @@ def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, s
              sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=None, filtering=None):
     """``tsat_pd_ensemble``, or with ``sensing`` = (SensorOptions, sensor array or None) ``tsat_pd_ensemble_sensed``, or with
     ``filtering`` = (FilterOptions, X_hat or None, filt_final or None) besides ``tsat_pd_ensemble_filtered`` — with ModelFilterOptions
-    in its place ``tsat_pd_ensemble_model_filtered``, with MagFilterOptions ``tsat_pd_ensemble_mag_filtered``"""
+    in its place ``tsat_pd_ensemble_model_filtered``, with MagFilterOptions ``tsat_pd_ensemble_mag_filtered``, with
+    MagBiasFilterOptions ``tsat_pd_ensemble_mag_bias_filtered``"""
     lib = _abi.load()
     T, N = batch.T, batch.N
     c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
@@ -423,8 +424,8 @@ def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, s
     if sensing is None:
         name, rc = "tsat_pd_ensemble", lib.tsat_pd_ensemble(*args)
     elif filtering is not None:
-        name = {_abi.ModelFilterOptions: "tsat_pd_ensemble_model_filtered", _abi.MagFilterOptions: "tsat_pd_ensemble_mag_filtered"}.get(
-            type(filtering[0]), "tsat_pd_ensemble_filtered")
+        name = {_abi.ModelFilterOptions: "tsat_pd_ensemble_model_filtered", _abi.MagFilterOptions: "tsat_pd_ensemble_mag_filtered",
+                _abi.MagBiasFilterOptions: "tsat_pd_ensemble_mag_bias_filtered"}.get(type(filtering[0]), "tsat_pd_ensemble_filtered")
         rc = getattr(lib, name)(*args, C.byref(sensing[0]), d(sensing[1]), C.byref(filtering[0]), d(filtering[1]), d(filtering[2]))
     else:
         name, rc = "tsat_pd_ensemble_sensed", lib.tsat_pd_ensemble_sensed(*args, C.byref(sensing[0]), d(sensing[1]))
@@ -715,6 +716,63 @@ def attitude_ensemble_pd_mag_filtered(solver, batch: SlewBatch, x0_sim, kd, kp, 
     T, M = batch.T, x0.shape[1]
     sensing = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
     fo, Xh, ff = _mag_filtering(T, M, batch.N, filter, want_estimates)
+    out = _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
+                   want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing, filtering=(fo, Xh, ff))
+    return dict(out, X_hat=Xh, filt_final=ff)
+
+
+MAG_BIAS_FILTER_W = 15
+
+
+def mag_bias_filter_options(sigma_v, sigma_m, sigma_u=0.0, sigma_c=0.0, p0_att=None, p0_bias=0.0, p0_mag=0.0):
+    """The ``tsat_mag_bias_filter_options`` of the mag-bias-filtered ensembles: ``mag_filter_options`` and, for the magnetometer-bias
+    state, its random walk per knot ``sigma_c`` and its initial standard deviation ``p0_mag`` (both in the units of the field
+    table). ``p0_mag`` = ``sigma_c`` = 0 estimates no magnetometer bias: the filter is then ``mag_filter_options``'."""
+    fo = _abi.MagBiasFilterOptions()
+    _abi.load().tsat_mag_bias_filter_default_options(C.byref(fo))
+    fo.sigma_v, fo.sigma_m, fo.sigma_u, fo.sigma_c = float(sigma_v), float(sigma_m), float(sigma_u), float(sigma_c)
+    fo.p0_att, fo.p0_bias, fo.p0_mag = float(fo.p0_att if p0_att is None else p0_att), float(p0_bias), float(p0_mag)
+    if min(fo.sigma_v, fo.sigma_u, fo.sigma_c, fo.p0_att, fo.p0_bias, fo.p0_mag) < 0.0 or not fo.sigma_m > 0.0:
+        raise ValueError("filter levels must not be negative, and sigma_m must be positive")
+    if not all(np.isfinite([fo.sigma_v, fo.sigma_m, fo.sigma_u, fo.sigma_c, fo.p0_att, fo.p0_bias, fo.p0_mag])):
+        raise ValueError("filter levels must be finite")
+    return fo
+
+
+def _mag_bias_filtering(T, M, N, filter, want_estimates):
+    """(MagBiasFilterOptions, X_hat (T, M, N, 7) or None, filt_final (T, M, 15)) of a mag-bias-filtered call"""
+    if not isinstance(filter, _abi.MagBiasFilterOptions):
+        raise ValueError("filter must come from mag_bias_filter_options(): sigma_m has no default")
+    return filter, (np.empty((T, M, N, 7)) if want_estimates else None), np.empty((T, M, MAG_BIAS_FILTER_W))
+
+
+def attitude_ensemble_mag_bias_filtered(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant=None, Rtab=None, gm=0.0,
+                                        sat=None, sensor=None, sigma_gyro=0.0, sigma_att=0.0, sigma_mag=0.0, latency=0, noise_id0=None,
+                                        sigma_scale=1.0, want_K=False, want_trajectories=False, linearize_dt_sq=True, u_scale=1e-2,
+                                        min_steps=10, w_tol=0.05, angle_tol=0.08727, filter=None, want_estimates=False):
+    """``attitude_ensemble_mag_filtered`` with the MAGNETOMETER BIAS ESTIMATED (``tsat_tvlqr_ensemble_mag_bias_filtered``): nine
+    error states — attitude error, gyro bias, magnetometer bias —, the measurement z = b_m - c^ - (predicted field); the recursion is
+    in include/tortoise_hip.h. ``filter`` from ``mag_bias_filter_options`` (required: ``sigma_m`` has no default). Returns the dict
+    of ``attitude_ensemble_mag_filtered`` with ``filt_final`` (T, M, 15) = [b^, sqrt(diag A), sqrt(diag D), c^, sqrt(diag M)] after
+    the last sample processed."""
+    return _tv_filtered_call("tsat_tvlqr_ensemble_mag_bias_filtered", _mag_bias_filtering, solver, batch, X, U, x0_sim, Qd, Qfd, Rd,
+                             noise_seed, plant, Rtab, gm, sat, sensor, sigma_gyro, sigma_att, sigma_mag, latency, noise_id0, sigma_scale,
+                             want_K, want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol, filter, want_estimates)
+
+
+def attitude_ensemble_pd_mag_bias_filtered(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X=None, U=None, plant=None, Rtab=None,
+                                           gm=0.0, sat=None, limit_mode=0, x0_nom=None, sensor=None, sigma_gyro=0.0, sigma_att=0.0,
+                                           sigma_mag=0.0, latency=0, noise_id0=None, want_trajectories=False, sigma_scale=1.0,
+                                           u_scale=1e-2, min_steps=10, w_tol=0.05, angle_tol=0.08727, filter=None, want_estimates=False):
+    """``attitude_ensemble_pd_sensed`` with the filter of ``attitude_ensemble_mag_bias_filtered`` between the measurement and the law
+    (``tsat_pd_ensemble_mag_bias_filtered``); the law's field reading is the raw magnetometer sample the filter used, taken once per
+    knot and not corrected by c^. Returns the dict of ``attitude_ensemble_pd_sensed`` plus ``X_hat`` and ``filt_final`` as there."""
+    x0 = np.asarray(x0_sim)
+    if x0.ndim != 3:
+        raise ValueError("x0_sim must be (T, M, 7)")
+    T, M = batch.T, x0.shape[1]
+    sensing = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
+    fo, Xh, ff = _mag_bias_filtering(T, M, batch.N, filter, want_estimates)
     out = _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
                    want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing, filtering=(fo, Xh, ff))
     return dict(out, X_hat=Xh, filt_final=ff)
