@@ -129,9 +129,10 @@ def tvlqr_riccati(Ah, Bh, Q, R, Qf):
     return K.reshape(N - 1, 3, 6)
 
 
-def solve_batch(batch, opts, nthreads=1, want_K=True, trace_rows=0):
-    """Oracle solve of a SlewBatch. Returns dict(X (T,N,7), U (T,N-1,3), K (T,N-1,7,3) ABI order, stats, trace)."""
-    lib = load()
+def solve_batch(batch, opts, nthreads=1, want_K=True, trace_rows=0, lib=None):
+    """Oracle solve of a SlewBatch. Returns dict(X (T,N,7), U (T,N-1,3), K (T,N-1,7,3) ABI order, stats, trace).
+    lib: another build of the oracle, loaded by the caller (oracle/Makefile: _ref/liboracle_nofma.so); None: the shipped one."""
+    lib = lib if lib is not None else load()
     T, N = batch.T, batch.N
     o = opts.copy()
     o.n_knots, o.n_tab = N, batch.n_tab

@@ -1,5 +1,6 @@
 """The field-table chain and the Gramian horizon once more, in mpmath at 80 significant digits, and (second half of the file) the
-closed-loop tracking of tsat_tvlqr_batch at 50: what the reference's text computes when no operation rounds. Transcribed from the same Julia lines as refmath_igrf.py / refmath.py: kep_ECI
+closed-loop tracking of tsat_tvlqr_batch at 50, and (last part) one trajectory of the AL-iLQR solve tsat_solve_batch at 50: what the reference's text
+(for the solve: include/tortoise_hip.h and SURVEY.md Appendix A) computes when no operation rounds. Transcribed from the same Julia lines as refmath_igrf.py / refmath.py: kep_ECI
 (src/kep_ECI.jl:1-49), OrbitPlotter (src/OrbitPlotter.jl:1-52), magnetic_simulation and magnetic_gramian /
 condition_based_time (src/magnetic_toolbox.jl:1-106), igrf12 geocentric (src/igrf.jl:70-274), the Schmidt Legendre
 functions (src/legendre.jl:254-292) and their derivatives (src/dlegendre.jl:221-309). Shares no code with oracle/ or the
@@ -460,3 +461,393 @@ def tracking_reference(X, U, xf, Bt, tau0, dtau, dt, Jcm, Qd, Qfd, Rd, x0_sim, n
         Kabi = [[[K[k][a, j] for a in range(3)] for j in range(6)] for k in range(N - 1)]
         rates = [wn[ji]] * N if rate_as_written else wn
         return dict(K=Kabi, X_sim=Xs, U_sim=Us, stats=stats, rates=rates, ang=ang, gap=gap)
+
+
+# ======================================================================================================================
+# The AL-iLQR solve (tsat_solve_batch, one trajectory) at 50 digits
+# ======================================================================================================================
+# solve_one of the definition (include/tortoise_hip.h): roll-out, AL cost of the control box and the goal,
+# backward sweep, regularisation schedule, backtracking line search, the inner exits, dual and penalty update, final statistics.
+# What it shares with neither the kernel (analytic tangents, cofactor inverses, reductions over lanes) nor the oracle (dual
+# numbers, scalar loops): the dynamics are TrackingPlant.f above, the Jacobians central differences of the RK map in this
+# arithmetic (step FD_STEP), the reductions and the sweep mp.matrix products, Quu^-1 is `** -1`. Every comparison is taken in
+# this arithmetic and recorded with its margin: the relative distance of the compared quantity from the value at which the
+# decision flips. A float64 program whose quantities are accurate to less than the smallest margin takes the same decisions.
+SOLVE_DEFAULTS = dict(integrator=3, max_outer=20, max_inner=50, max_linesearch=20, dj_counter_limit=10, cost_tol=1e-4, grad_tol=1e-5,
+                      constraint_tol=1e-3, penalty_init=1.0, penalty_scale=10.0, penalty_max=1e8, dual_max=1e8, reg_init=0.0,
+                      reg_scale=1.6, reg_min=1e-8, reg_max=1e8, reg_fp=10.0, ls_lower=1e-8, ls_upper=10.0, max_state=1e8,
+                      u_scale=1e-2, terminal_mask=0x7F, error_state=0)
+ST_CONVERGED, ST_MAX_OUTER, ST_REG_FAIL, ST_DIVERGED = 0, 1, 2, 3
+
+
+class Margins:
+    """smallest margin of every kind of decision; `exact` counts the decisions that are ties by construction of the input"""
+
+    def __init__(self):
+        self.kinds, self.exact = {}, {}
+
+    def add(self, kind, m):
+        m = mpf(m)
+        if kind not in self.kinds or m < self.kinds[kind]:
+            self.kinds[kind] = m
+
+    def tie(self, kind):
+        self.exact[kind] = self.exact.get(kind, 0) + 1
+
+    def rel(self, kind, a, b):
+        """a compared with b: |a - b| / max(|a|, |b|)"""
+        s = max(abs(a), abs(b))
+        self.add(kind, mpf(1) if s == 0 else abs(a - b) / s)
+
+    def min(self):
+        return min(self.kinds.values()) if self.kinds else mpf(1)
+
+
+class _Solve:
+    def __init__(self, x0, xf, Bt, tau0, dtau, dt, Jcm, Qd, Qfd, Rd, ulo, uhi, o):
+        self.o = o
+        self.N = None
+        self.plant = TrackingPlant(Jcm, o["u_scale"])
+        self.x0, self.xf = [_f(v) for v in x0], [_f(v) for v in xf]
+        self.Bt, self.tau0, self.dtau, self.h = Bt, _f(tau0), _f(dtau), _f(dt)
+        self.Qd, self.Qfd, self.Rd = [_f(v) for v in Qd], [_f(v) for v in Qfd], [_f(v) for v in Rd]
+        self.ulo, self.uhi = [_f(v) for v in ulo], [_f(v) for v in uhi]
+        self.es, self.mask = int(o["error_state"]), int(o["terminal_mask"])
+        self.max_state = _f(o["max_state"])
+        self.mg = Margins()
+        self.rows_cache = {}
+
+    # ---- dynamics -----------------------------------------------------------------------------------------------------
+    def rows(self, k):
+        if k not in self.rows_cache:
+            r = []
+            for c in (mpf(0), mpf(1) / 2, mpf(1)):
+                row, gap = table_row(self.Bt, k, c, self.dtau, self.tau0)
+                v = (k + c) * self.dtau + self.tau0
+                near = int(mp.floor(v + mpf(1) / 2))                   # the integer next to the argument: rows near - 1 and near
+                if v == mp.floor(v):
+                    self.mg.tie("table_gap")                           # an integer argument: exact in float64 and in fma too
+                elif min(max(near - 1, 0), len(self.Bt) - 1) == min(max(near, 0), len(self.Bt) - 1):
+                    pass                                               # both sides of that integer are clamped to the same row
+                else:
+                    self.mg.add("table_gap", gap)
+                r.append(row)
+            self.rows_cache[k] = r
+        return self.rows_cache[k]
+
+    def step(self, k, x, u):
+        p, h, rows = self.plant, self.h, self.rows(k)
+        if int(self.o["integrator"]) == 4:
+            return p.rk4(x, u, rows, h)
+        k1 = [h * v for v in p.f(x, u, rows[0])]                       # rk3: src/attitude_controller.jl:178-187
+        k2 = [h * v for v in p.f([x[i] + k1[i] / 2 for i in range(7)], u, rows[1])]
+        k3 = [h * v for v in p.f([x[i] - k1[i] + 2 * k2[i] for i in range(7)], u, rows[2])]
+        return [x[i] + (k1[i] + 4 * k2[i] + k3[i]) / 6 for i in range(7)]
+
+    def jacobians(self, k, x, u):
+        eps = mpf(FD_STEP)
+        A, B = mp.matrix(7, 7), mp.matrix(7, 3)
+        for j in range(7):
+            xp, xm = list(x), list(x)
+            xp[j] += eps; xm[j] -= eps
+            fp, fm = self.step(k, xp, u), self.step(k, xm, u)
+            for i in range(7):
+                A[i, j] = (fp[i] - fm[i]) / (2 * eps)
+        for j in range(3):
+            up, um = list(u), list(u)
+            up[j] += eps; um[j] -= eps
+            fp, fm = self.step(k, x, up), self.step(k, x, um)
+            for i in range(7):
+                B[i, j] = (fp[i] - fm[i]) / (2 * eps)
+        return A, B
+
+    # ---- cost ---------------------------------------------------------------------------------------------------------
+    def box(self, u, lam):
+        """the six rows (c, lambda, active) of one knot; the margin of c is relative to max(|u|, |bound|)"""
+        out = []
+        for a in range(3):
+            for c, lm, s in ((u[a] - self.uhi[a], lam[a], max(abs(u[a]), abs(self.uhi[a]))),
+                             (self.ulo[a] - u[a], lam[3 + a], max(abs(u[a]), abs(self.ulo[a])))):
+                if lm > 0:
+                    act = True
+                else:
+                    act = c > 0
+                    if c == 0:
+                        self.mg.tie("active_set")
+                    else:
+                        self.mg.add("active_set", abs(c) / s)
+                out.append((c, lm, act))
+        return out
+
+    def total_cost(self, X, U, al, with_al=True):
+        J = mpf(0)
+        for k in range(self.N - 1):
+            x, u = X[k], U[k]
+            J += sum(self.Qd[i] * (x[i] - self.xf[i]) ** 2 for i in range(7)) / 2 + sum(self.Rd[a] * u[a] ** 2 for a in range(3)) / 2
+            if with_al:
+                for c, lm, act in self.box(u, al["lam"][k]):
+                    J += lm * c + (al["mu"] * c * c / 2 if act else 0)
+        x = X[self.N - 1]
+        J += sum(self.Qfd[i] * (x[i] - self.xf[i]) ** 2 for i in range(7)) / 2
+        if with_al:
+            for i in range(7):
+                if self.mask >> i & 1:
+                    e = x[i] - self.xf[i]
+                    J += al["nu"][i] * e + al["mu"] * e * e / 2
+        return J
+
+    def max_violation(self, X, U):
+        c = mpf(0)
+        for k in range(self.N - 1):
+            for a in range(3):
+                c = max(c, U[k][a] - self.uhi[a], self.ulo[a] - U[k][a])
+        for i in range(7):
+            if self.mask >> i & 1:
+                c = max(c, abs(X[self.N - 1][i] - self.xf[i]))
+        return c
+
+    # ---- roll-out -----------------------------------------------------------------------------------------------------
+    def within(self, v):
+        self.mg.rel("max_state", abs(v), self.max_state)
+        self.largest = max(self.largest, abs(v))
+        return abs(v) <= self.max_state
+
+    def state_diff(self, xn, xb):
+        if not self.es:
+            return [xn[j] - xb[j] for j in range(7)]
+        qe = _qmult([xb[3], -xb[4], -xb[5], -xb[6]], xn[3:7])
+        return [xn[j] - xb[j] for j in range(3)] + [qe[1 + j] / (1 + qe[0]) for j in range(3)]
+
+    def rollout(self, X, U, K, d, alpha, closed):
+        Xc, Uc, ok = [list(self.x0)], [], True
+        self.largest = mpf(0)
+        for k in range(self.N - 1):
+            xc = Xc[k]
+            u = list(U[k])
+            if closed:
+                dx = self.state_diff(xc, X[k])
+                for a in range(3):
+                    u[a] += sum(K[k][a, j] * dx[j] for j in range(len(dx))) + alpha * d[k][a]
+            Uc.append(u)
+            for v in xc + u:
+                ok = self.within(v) and ok
+            Xc.append(self.step(k, xc, u))
+        for v in Xc[self.N - 1]:
+            ok = self.within(v) and ok
+        return ok, Xc, Uc
+
+    # ---- backward sweep -----------------------------------------------------------------------------------------------
+    def emat(self, q):
+        E = mp.matrix(7, 6)
+        G = _gmat(q)
+        for i in range(3):
+            E[i, i] = 1
+        for r in range(4):
+            for c in range(3):
+                E[3 + r, 3 + c] = G[r][c]
+        return E
+
+    def backward(self, X, U, al, rho):
+        N, es, mu = self.N, self.es, al["mu"]
+        xN = X[N - 1]
+        Sd, sf = [], mp.matrix(7, 1)
+        for i in range(7):
+            e = xN[i] - self.xf[i]
+            m = self.mask >> i & 1
+            Sd.append(self.Qfd[i] + (mu if m else 0))
+            sf[i] = self.Qfd[i] * e + ((al["nu"][i] + mu * e) if m else 0)
+        S, s = mp.diag(Sd), sf
+        if es:
+            E = self.emat(xN[3:7])
+            S, s = E.T * S * E, E.T * s
+        Qm = mp.diag(self.Qd)
+        K, d = [None] * (N - 1), [None] * (N - 1)
+        dV = [mpf(0), mpf(0)]
+        for k in range(N - 2, -1, -1):
+            x, u = X[k], U[k]
+            A, B = self.jacobians(k, x, u)
+            lx = mp.matrix([self.Qd[i] * (x[i] - self.xf[i]) for i in range(7)])
+            Q0 = Qm
+            if es:
+                Ek, En = self.emat(x[3:7]), self.emat(X[k + 1][3:7])
+                A, B, lx, Q0 = En.T * A * Ek, En.T * B, Ek.T * lx, Ek.T * Qm * Ek
+            rows = self.box(u, al["lam"][k])
+            lu, luu = mp.matrix(3, 1), [None] * 3
+            for a in range(3):
+                (cu, lmu, au), (cl, lml, alo) = rows[2 * a], rows[2 * a + 1]
+                lu[a] = self.Rd[a] * u[a] + lmu + (mu * cu if au else 0) - lml - (mu * cl if alo else 0)
+                luu[a] = self.Rd[a] + (mu if au else 0) + (mu if alo else 0)
+            Qx, Qu = lx + A.T * s, lu + B.T * s
+            Qxx, Quu, Qux = Q0 + A.T * S * A, mp.diag(luu) + B.T * S * B, B.T * S * A
+            Qr = (Quu + Quu.T) / 2 + rho * mp.eye(3)
+            q00 = Qr[0, 0]
+            t1, t2 = Qr[0, 0] * Qr[1, 1], Qr[1, 0] * Qr[1, 0]
+            c22 = t1 - t2
+            det = mp.det(Qr)
+            c00, c01, c02 = Qr[1, 1] * Qr[2, 2] - Qr[2, 1] ** 2, Qr[2, 0] * Qr[2, 1] - Qr[1, 0] * Qr[2, 2], Qr[1, 0] * Qr[2, 1] - Qr[2, 0] * Qr[1, 1]
+            self.mg.add("pd_q00", abs(q00) / (abs(Quu[0, 0]) + abs(rho)))
+            self.mg.add("pd_c22", abs(c22) / (abs(t1) + abs(t2)))
+            self.mg.add("pd_det", abs(det) / (abs(Qr[0, 0] * c00) + abs(Qr[1, 0] * c01) + abs(Qr[2, 0] * c02)))
+            if not (q00 > 0 and c22 > 0 and det > 0):
+                return False, K, d, dV
+            Qi = Qr ** -1
+            K[k], d[k] = -Qi * Qux, -Qi * Qu
+            QuuK, Quud = Quu * K[k], Quu * d[k]
+            s = Qx + K[k].T * Quud + K[k].T * Qu + Qux.T * d[k]
+            Sn = Qxx + K[k].T * QuuK + K[k].T * Qux + Qux.T * K[k]
+            S = (Sn + Sn.T) / 2
+            dV[0] += (d[k].T * Qu)[0]
+            dV[1] += (d[k].T * Quud)[0] / 2
+        return True, K, d, dV
+
+    # ---- regularisation schedule --------------------------------------------------------------------------------------
+    def reg_increase(self, rho, drho):
+        sc = _f(self.o["reg_scale"])
+        drho = max(drho * sc, sc)
+        return max(rho * drho, _f(self.o["reg_min"])), drho
+
+    def reg_decrease(self, rho, drho):
+        sc = _f(self.o["reg_scale"])
+        drho = min(drho / sc, 1 / sc)
+        r = rho * drho
+        self.mg.rel("reg_min", r, _f(self.o["reg_min"]))
+        return (r if r > _f(self.o["reg_min"]) else mpf(0)), drho
+
+
+def solve_reference(x0, xf, Bt, tau0, dtau, dt, Jcm, Qd, Qfd, Rd, ulo, uhi, U0, trace_rows=64, **options):
+    """One trajectory of tsat_solve_batch over N = len(U0) + 1 knots. options: fields of tsat_options by name (SOLVE_DEFAULTS).
+    Returns dict of mpf: X (N, 7), U (N-1, 3), K (N-1, 7, 3) of the last successful backward sweep in the layout of the ABI (None
+    if there was none; column 6 zero with error_state = 1), d (N-1, 3), stats (dict of the fields of tsat_stats), trace (rows of
+    8), ls_log (outer, inner, candidate, accepted roll-out, largest |x| or |u|) of every candidate, margins (kind -> smallest), exact (kind -> number of ties by construction), min_margin."""
+    o = dict(SOLVE_DEFAULTS)
+    o.update(options)
+    with mp.workdps(TRACK_DPS):
+        sv = _Solve(x0, xf, Bt, tau0, dtau, dt, Jcm, Qd, Qfd, Rd, ulo, uhi, o)
+        N = sv.N = len(U0) + 1
+        mg = sv.mg
+        U = [[_f(v) for v in row] for row in U0]
+        al = dict(lam=[[mpf(0)] * 6 for _ in range(N - 1)], nu=[mpf(0)] * 7, mu=_f(o["penalty_init"]))
+        st = dict(status=ST_MAX_OUTER, outer_iters=0, inner_iters=0, ls_trials=0, n_backward=0, n_forward=1, bp_restarts=0, fp_fails=0,
+                  grad=mpf(0))
+        trace, ls_log, Kl, dl = [], [], None, None
+        ok0, X, _ = sv.rollout(None, U, None, None, mpf(0), False)
+        if not ok0:
+            st["status"] = ST_DIVERGED
+        else:
+            for outer in range(1, int(o["max_outer"]) + 1):
+                Jprev = sv.total_cost(X, U, al)
+                rho, drho, djz, regfail = _f(o["reg_init"]), mpf(0), 0, False
+                for it in range(1, int(o["max_inner"]) + 1):
+                    while True:
+                        st["n_backward"] += 1
+                        good, K, d, dV = sv.backward(X, U, al, rho)
+                        if good:
+                            Kl, dl = K, d
+                            break
+                        st["bp_restarts"] += 1
+                        rho, drho = sv.reg_increase(rho, drho)
+                        mg.rel("reg_max", rho, _f(o["reg_max"]))
+                        if rho > _f(o["reg_max"]):
+                            regfail = True
+                            break
+                    if regfail:
+                        break
+                    rho_used = rho
+                    rho, drho = sv.reg_decrease(rho, drho)
+                    alpha, J, jacc = mpf(1), Jprev, -1
+                    for j in range(int(o["max_linesearch"])):
+                        st["n_forward"] += 1
+                        st["ls_trials"] += 1
+                        ok, Xc, Uc = sv.rollout(X, U, K, d, alpha, True)
+                        ls_log.append((outer, it, j, ok, float(sv.largest)))
+                        if ok:
+                            Jc = sv.total_cost(Xc, Uc, al)
+                            t1, t2 = -alpha * dV[0], -alpha * alpha * dV[1]
+                            expected = t1 + t2
+                            mg.add("expected", abs(expected) / (abs(t1) + abs(t2)) if expected != 0 else 0)
+                            z = (Jprev - Jc) / expected if expected > 0 else mpf(-1)
+                            lo, hi = _f(o["ls_lower"]), _f(o["ls_upper"])
+                            m_lo, m_hi = abs(z - lo) / max(abs(z), lo), abs(z - hi) / max(abs(z), hi)
+                            inr = z > lo and z <= hi
+                            m_rng = min(m_lo, m_hi) if inr else max([m for m, f in ((m_lo, not z > lo), (m_hi, not z <= hi)) if f])
+                            less = Jc < Jprev
+                            m_J = abs(Jc - Jprev) / max(abs(Jc), abs(Jprev))
+                            if inr or less:
+                                mg.add("accept", max([m for m, f in ((m_rng, inr), (m_J, less)) if f]))
+                                jacc, J = j, Jc
+                                break
+                            mg.add("accept", min(m_rng, m_J))
+                        alpha = alpha / 2
+                    if jacc >= 0:
+                        X, U = Xc, Uc
+                    else:
+                        st["fp_fails"] += 1
+                        J = Jprev
+                        rho, drho = sv.reg_increase(rho, drho)
+                        rho += _f(o["reg_fp"])
+                    dJ = abs(J - Jprev)
+                    if len(trace) < trace_rows:
+                        trace.append([mpf(outer), mpf(it), Jprev, J, mpf(jacc), rho_used, dV[0], dV[1]])
+                    if jacc >= 0:
+                        mg.add("dJ_zero", dJ / max(abs(J), abs(Jprev)))
+                    else:
+                        mg.tie("dJ_zero")                               # no candidate accepted: J is Jprev itself
+                    Jprev = J
+                    djz = djz + 1 if dJ == 0 else 0
+                    g = mpf(0)
+                    for k in range(N - 1):
+                        g += max(abs(d[k][a]) / (abs(U[k][a]) + 1) for a in range(3))
+                    st["grad"] = g / (N - 1)
+                    st["inner_iters"] += 1
+                    if dJ > 0:
+                        mg.rel("cost_tol", dJ, _f(o["cost_tol"]))
+                        if dJ < _f(o["cost_tol"]):
+                            break
+                    mg.rel("grad_tol", st["grad"], _f(o["grad_tol"]))
+                    if st["grad"] < _f(o["grad_tol"]):
+                        break
+                    if djz > int(o["dj_counter_limit"]):
+                        break
+                st["outer_iters"] = outer
+                cm = sv.max_violation(X, U)
+                if regfail:
+                    st["status"] = ST_REG_FAIL
+                    break
+                mg.rel("constraint_tol", cm, _f(o["constraint_tol"]))
+                if cm < _f(o["constraint_tol"]):
+                    st["status"] = ST_CONVERGED
+                    break
+                if outer == int(o["max_outer"]):
+                    break
+                mu, dmax = al["mu"], _f(o["dual_max"])
+                for k in range(N - 1):
+                    for a in range(3):
+                        for i, c in ((a, U[k][a] - sv.uhi[a]), (3 + a, sv.ulo[a] - U[k][a])):
+                            v = al["lam"][k][i] + mu * c
+                            if v == 0:
+                                mg.tie("dual_clamp")                    # lambda = 0 and the control on its bound by construction
+                            else:
+                                mg.add("dual_clamp", abs(v) / (abs(al["lam"][k][i]) + abs(mu * c)))
+                            mg.rel("dual_clamp", v, dmax)
+                            al["lam"][k][i] = min(max(v, mpf(0)), dmax)
+                for i in range(7):
+                    if sv.mask >> i & 1:
+                        v = al["nu"][i] + mu * (X[N - 1][i] - sv.xf[i])
+                        mg.rel("dual_clamp", abs(v), dmax)
+                        al["nu"][i] = min(max(v, -dmax), dmax)
+                v = mu * _f(o["penalty_scale"])
+                mg.rel("penalty_clamp", v, _f(o["penalty_max"]))
+                al["mu"] = min(v, _f(o["penalty_max"]))
+        st["c_max"] = sv.max_violation(X, U)
+        st["cost"] = sv.total_cost(X, U, al, False)
+        st["cost_al"] = sv.total_cost(X, U, al, True)
+        for k in range(N - 1):
+            sv.rows(k)                                                  # (a diverged roll-out has looked every row up already)
+        Kabi = None
+        if Kl is not None and all(k is not None for k in Kl):
+            nh = 6 if sv.es else 7
+            Kabi = [[[Kl[k][a, j] if j < nh else mpf(0) for a in range(3)] for j in range(7)] for k in range(N - 1)]
+            dl = [[dl[k][a] for a in range(3)] for k in range(N - 1)]
+        else:
+            dl = None
+        return dict(X=X, U=U, K=Kabi, d=dl, stats=st, trace=trace, ls_log=ls_log, margins=dict(mg.kinds), exact=dict(mg.exact), min_margin=mg.min())

@@ -50,10 +50,8 @@ if __name__ == "__main__":
         sys.exit(0)
     n_pool = int(sys.argv[1]) if len(sys.argv) > 1 else 384
     tmp = tempfile.mkdtemp()
-    flags = "-O2 -std=c++17 -fPIC -fopenmp -march=x86-64-v3 -shared"
-    src = os.path.join(ROOT, "oracle", "tsat_oracle.cpp")
-    nofma = os.path.join(tmp, "liboracle_nofma.so")
-    subprocess.check_call(f"g++ {flags} -ffp-contract=off -o {nofma} {src}", shell=True)
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "_ref/liboracle_nofma.so"], stdout=subprocess.DEVNULL)      # the recipe of oracle/Makefile
+    nofma = os.path.join(ROOT, "oracle", "_ref", "liboracle_nofma.so")
     run = lambda lib, out, pick=None: subprocess.check_call([sys.executable, __file__, "--child", out, str(n_pool)] + ([pick] if pick else []),
                                                             env=dict(os.environ, **({"TSAT_ORACLE_LIB": lib} if lib else {})))
     a_all = os.path.join(tmp, "a_all.npz")
