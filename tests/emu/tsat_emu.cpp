@@ -3,7 +3,10 @@
 // Compiles tortoisesat.jl_amd/csrc/tsat_device.hpp — the very source hipcc compiles for gfx950 — with
 // TSAT_EMU: one wavefront = 64 host threads, __syncthreads() = std::barrier, LDS = a heap block.
 // Lets the CPU-only test tier check the kernel's indexing / lane roles / control flow against the oracle;
-// it is never used by the product and says nothing about performance.
+// it is never used by the product and says nothing about performance. The drivers of the other kernels include this file, some
+// through more than one of their headers: hence the guard.
+#ifndef TSAT_EMU_CPP
+#define TSAT_EMU_CPP
 #define TSAT_EMU
 #include <atomic>
 #include <barrier>
@@ -346,3 +349,4 @@ extern "C" int emu_btable_batch(const tsat_btable_options* o, int64_t T, const d
   return 0;
 }
 #endif  // TSAT_DENSE
+#endif  // TSAT_EMU_CPP

@@ -1,40 +1,41 @@
 // tsat_emu_sensed.cpp — the ensemble controllers fed measurements (tortoisesat.jl_amd/csrc/tsat_sensed.hpp) under the CPU lane
-// emulator (TEST INFRASTRUCTURE). Takes run_wave / for_each_wave and the packing code from tsat_emu.cpp as they are. The two
-// drivers are those of tsat_emu_gg.cpp (its ensemble) and tsat_emu_pd.cpp with the biases packed by the product's own
-// sensed_pack, one call per thread of its grid, and the sensed waves in place of gg_wave / pd_wave; like the entry points they
-// take the model's plant for a NULL plant and the kernels without gravity rows for a NULL Rtab. The sensor arguments are
-// validated by the library's own check_sensor, which emu_sensed_check exposes alone.
-#include <cmath>
-#include "tsat_emu.cpp"
-#include "../../tortoisesat.jl_amd/csrc/tsat_sensed.hpp"
+// emulator (TEST INFRASTRUCTURE). The two drivers are sensed_tv and sensed_pd of tsat_emu_rollout.hpp: like the entry points they
+// take the model's plant for a NULL plant and the kernels without gravity rows for a NULL Rtab. Here are the two calls as EmuCall
+// (the four filter files, which include this one, extend them) and the symbols. The sensor arguments are validated by the library's
+// own check_sensor, which emu_sensed_check exposes alone.
+#include "tsat_emu_rollout.hpp"
 
-namespace {
+// the arguments of emu_tvlqr_ensemble_sensed, in its order, as a call
+static EmuCall sensed_tv_call(const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X, const double* U,
+                              const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                              const double* dt, const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                              const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots, const double* plant,
+                              const double* sat_lo, const double* sat_hi, const double* K_lqr, tsat_tvlqr_stats* stats, double* summary,
+                              tsat_tvlqr_stats* stats_nominal, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                              const tsat_sensor_options* s, const double* sensor) {
+  EmuCall c{o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, X_sim};
+  c.tv = EmuTv{Qd, Qfd, Rd, K_lqr};
+  c.disp = EmuDispersion{plant, sat_lo, sat_hi, n_clipped};
+  c.grav = EmuGravity{Rtab, gm};
+  c.sens = EmuSensing{s, sensor};
+  return c;
+}
 
-// what both drivers share: limits, plants (the model's when null), gravity rows (none when Rtab is null), sensor records
-struct Common {
-  std::vector<double> SAT, PL, GT, SN, model;
-  void fill(const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* P, const double* Jmat, const double* plant,
-            const double* sat_lo, const double* sat_hi, const double* Rtab, double gm, const double* sensor) {
-    const int Mp = ensemble_waves(M) * WAVE;
-    const size_t Tn = (size_t)T;
-    SAT = pack_limits(sat_lo, sat_hi, T);
-    if (!plant) {
-      model = model_plants(Jmat, Tn, M);
-      plant = model.data();
-    }
-    PL.assign(Tn * PLW * Mp, 0.0);
-    for (int64_t e = 0; e < T * (int64_t)(M + 1); ++e) dispersed_pack<double>(plant, P, o->u_scale, PL.data(), T, M, Mp, e);
-    if (Rtab) {
-      const int64_t rows = n_btab * (int64_t)o->n_tab;
-      GT.resize((size_t)rows * 4);
-      for (int64_t e = 0; e < rows; ++e) gg_pack_row<double>(Rtab, gm, GT.data(), rows, e);
-    }
-    SN.assign(Tn * SNW * Mp, -1.0);                            // the pack has to write every slot
-    for (int64_t e = 0; e < T * (int64_t)Mp; ++e) sensed_pack<double>(sensor, SN.data(), T, M, Mp, e);
-  }
-};
-
-}  // namespace
+// ... and of emu_pd_ensemble_sensed
+static EmuCall sensed_pd_call(const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X, const double* U,
+                              const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                              const double* dt, const double* Jmat, const double* kd, const double* kp, int32_t feedforward,
+                              int32_t limit_mode, const double* x0_sim, const double* x0_nom, const int64_t* noise_id0,
+                              const int32_t* n_knots, const double* plant, const double* sat_lo, const double* sat_hi,
+                              tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* X_sim, int32_t* n_clipped,
+                              const double* Rtab, double gm, const tsat_sensor_options* s, const double* sensor) {
+  EmuCall c{o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, X_sim};
+  c.pd = EmuPd{kd, kp, feedforward, limit_mode, x0_nom};
+  c.disp = EmuDispersion{plant, sat_lo, sat_hi, n_clipped};
+  c.grav = EmuGravity{Rtab, gm};
+  c.sens = EmuSensing{s, sensor};
+  return c;
+}
 
 // arguments as tsat_tvlqr_ensemble_sensed (include/tortoise_hip.h) without the handle, with K_lqr 3 x 6 x (N-1) x T as an INPUT
 // (before `stats`, as emu_tvlqr_ensemble_gg); the plants are taken as valid
@@ -46,42 +47,8 @@ extern "C" int emu_tvlqr_ensemble_sensed(const tsat_tvlqr_options* o, int64_t T,
                                          const double* K_lqr, tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
                                          double* X_sim, int32_t* n_clipped, const double* Rtab, double gm, const tsat_sensor_options* s,
                                          const double* sensor) {
-  if (!check_tv_options(*o).empty() || o->noise_mode != 1 || o->rate_as_written != 0 || M < 1 || M > 65535) return -1;
-  if ((sat_lo == nullptr) != (sat_hi == nullptr)) return -1;
-  const int N = o->n_knots, n_tab = o->n_tab;
-  if (Rtab ? !check_gravity(Rtab, gm, n_btab * (int64_t)n_tab).empty() : !(gm == 0.0)) return -1;
-  if (!check_sensor(s, sensor, T, M).empty()) return -1;
-  const int nw = ensemble_waves(M), Mp = nw * WAVE;
-  std::vector<double> P((size_t)T * PSTRIDE), BT((size_t)n_btab * n_tab * 4), XUR((size_t)T * N * XUW), KD((size_t)T * (N - 1) * KDW, 0.0),
-      x0n((size_t)T * 7);
-  std::vector<int> bidx(T);
-  for (int64_t t = 0; t < T; ++t) {
-    bidx[t] = btab_idx ? btab_idx[t] : (int)t;
-    for (int i = 0; i < 7; ++i) x0n[7 * t + i] = X[(size_t)t * N * 7 + i];
-  }
-  pack_tv_params<double>(T, x0n.data(), xf, tau0, dtau, dt, Jmat, Qd, Qfd, Rd, P.data());
-  pack_btab<double>(n_btab, n_tab, Btab, BT.data());
-  pack_xu_records<double>(T, N, X, U, XUR.data());
-  for (size_t ek = 0; ek < (size_t)T * (N - 1); ++ek)        // the inverse of unpack_tv: solver sign, rows of 7
-    for (int j = 0; j < 6; ++j)
-      for (int c = 0; c < 3; ++c) KD[ek * KDW + c * 7 + j] = -K_lqr[ek * 18 + j * 3 + c];
-  Common cm;
-  cm.fill(o, T, n_btab, M, P.data(), Jmat, plant, sat_lo, sat_hi, Rtab, gm, sensor);
-  if (X_sim) std::memset(X_sim, 0, sizeof(double) * (size_t)T * M * N * 7);
-  std::vector<tsat_tvlqr_stats> nom((size_t)T);
-  SensedTvArgs<double> sa;
-  sa.g.d.e = ens_args<EnsArgs<double>>(*o, T, M, P.data(), BT.data(), bidx.data(), n_knots, XUR.data(), KD.data(), x0_sim,
-                                       (const long long*)noise_id0, X_sim, stats, nom.data());
-  sa.g.d.PL = cm.PL.data(); sa.g.d.Mp = Mp; sa.g.d.SAT = cm.SAT.data(); sa.g.d.nclip = n_clipped;
-  sa.g.GT = Rtab ? cm.GT.data() : nullptr;
-  sa.s = sens_args(*s, *o, cm.SN.data(), Mp);
-  tsat_emu::for_each_wave((int)T * nw, [&](int i) {
-    const int t = i / nw, w = i - t * nw;
-    tsat_emu::run_wave(64, [&]() { sa.g.GT ? sensed_tv_gg_wave<double>(sa, t, w) : sensed_tv_wave<double>(sa, t, w); });   // no LDS
-  });
-  if (stats_nominal) std::memcpy(stats_nominal, nom.data(), sizeof(tsat_tvlqr_stats) * (size_t)T);
-  ensemble_summary(T, M, stats, summary);
-  return 0;
+  return sensed_tv(sensed_tv_call(o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, Qd, Qfd, Rd, x0_sim, noise_id0, n_knots,
+                                  plant, sat_lo, sat_hi, K_lqr, stats, summary, stats_nominal, X_sim, n_clipped, Rtab, gm, s, sensor));
 }
 
 // arguments as tsat_pd_ensemble_sensed (include/tortoise_hip.h) without the handle
@@ -93,51 +60,12 @@ extern "C" int emu_pd_ensemble_sensed(const tsat_tvlqr_options* o, int64_t T, in
                                       const double* sat_hi, tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
                                       double* X_sim, int32_t* n_clipped, const double* Rtab, double gm, const tsat_sensor_options* s,
                                       const double* sensor) {
-  if (!check_pd(o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode, x0_sim, x0_nom, n_knots,
-                plant, sat_lo, sat_hi, stats, summary, stats_nominal, Rtab, gm).empty())
-    return -1;
-  if (!check_sensor(s, sensor, T, M).empty()) return -1;
-  const int N = o->n_knots, n_tab = o->n_tab;
-  const int nw = ensemble_waves(M), Mp = nw * WAVE;
-  const size_t Tn = (size_t)T;
-  std::vector<double> P(Tn * PSTRIDE), BT((size_t)n_btab * n_tab * 4), XUR, x0n(Tn * 7), zero(Tn * 6, 0.0), gain(Tn * PDGW);
-  std::vector<int> bidx(Tn);
-  for (size_t t = 0; t < Tn; ++t) {
-    bidx[t] = btab_idx ? btab_idx[t] : (int)t;
-    for (int i = 0; i < 7; ++i) x0n[7 * t + i] = x0_nom ? x0_nom[7 * t + i] : (X ? X[t * N * 7 + i] : xf[7 * t + i]);
-    for (int c = 0; c < 3; ++c) { gain[PDGW * t + c] = kd[3 * t + c]; gain[PDGW * t + 3 + c] = kp[3 * t + c]; }
-  }
-  pack_tv_params<double>(T, x0n.data(), xf, tau0, dtau, dt, Jmat, zero.data(), zero.data(), zero.data(), P.data());
-  pack_btab<double>(n_btab, n_tab, Btab, BT.data());
-  if (X) {
-    std::vector<double> U0;
-    if (!feedforward) { U0.assign(Tn * (size_t)(N - 1) * 3, 0.0); U = U0.data(); }
-    XUR.resize(Tn * N * XUW);
-    pack_xu_records<double>(T, N, X, U, XUR.data());
-  }
-  Common cm;
-  cm.fill(o, T, n_btab, M, P.data(), Jmat, plant, sat_lo, sat_hi, Rtab, gm, sensor);
-  if (X_sim) std::memset(X_sim, 0, sizeof(double) * Tn * M * N * 7);
-  std::vector<tsat_tvlqr_stats> nom(Tn);
-  SensedPdArgs<double> sa;
-  PdArgs<double>& pa = sa.p;
-  pa.d.e = ens_args<EnsArgs<double>>(*o, T, M, P.data(), BT.data(), bidx.data(), n_knots, X ? XUR.data() : nullptr, nullptr, x0_sim,
-                                     (const long long*)noise_id0, X_sim, stats, nom.data());
-  pa.d.PL = cm.PL.data(); pa.d.Mp = Mp; pa.d.SAT = cm.SAT.data(); pa.d.nclip = n_clipped;
-  pa.GT = Rtab ? cm.GT.data() : nullptr; pa.GAIN = gain.data(); pa.X0N = x0n.data(); pa.feedforward = feedforward; pa.limit_mode = limit_mode;
-  sa.s = sens_args(*s, *o, cm.SN.data(), Mp);
-  tsat_emu::for_each_wave((int)T * nw, [&](int i) {
-    const int t = i / nw, w = i - t * nw;
-    tsat_emu::run_wave(64, [&]() { pa.GT ? sensed_pd_gg_wave<double>(sa, t, w) : sensed_pd_wave<double>(sa, t, w); });   // no LDS
-  });
-  if (stats_nominal) std::memcpy(stats_nominal, nom.data(), sizeof(tsat_tvlqr_stats) * Tn);
-  ensemble_summary(T, M, stats, summary);
-  return 0;
+  return sensed_pd(sensed_pd_call(o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward, limit_mode, x0_sim,
+                                  x0_nom, noise_id0, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, X_sim, n_clipped, Rtab, gm,
+                                  s, sensor));
 }
 
 // check_sensor alone: 0 and "" or -1 and the text tsat_ensemble_last_error would hold
 extern "C" int emu_sensed_check(const tsat_sensor_options* s, const double* sensor, int64_t T, int32_t M, char* text, int32_t cap) {
-  const std::string why = check_sensor(s, sensor, T, M);
-  if (cap > 0) { std::strncpy(text, why.c_str(), (size_t)cap - 1); text[cap - 1] = 0; }
-  return why.empty() ? 0 : -1;
+  return check_result(check_sensor(s, sensor, T, M), text, cap);
 }

@@ -4,12 +4,11 @@ index equality meaningful, the bars of ``tests/test_tracking.py::_same_tracking`
 emulated ensemble kernels, nominal and dispersed (tests/emu/tsat_emu_ensemble.cpp)."""
 import ctypes as C
 import dataclasses
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT, oracle_options
+import helpers
+from conftest import ROOT, oracle_options  # noqa: F401  (the tests reach ROOT through this module)
 
 SEED = 2019
 PER_SLEW = ("x0", "xf", "btab_idx", "tau0", "dtau", "dt", "Jmat", "Qd", "Qfd", "Rd", "ulo", "uhi", "U0")
@@ -126,9 +125,7 @@ class EmuEnsemble:
     """ctypes binding of tests/emu/libtsat_emu_ensemble.so (both emulated ensemble kernels), built here by the emulator Makefile"""
 
     def __init__(self, abi):
-        d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "libtsat_emu_ensemble.so"], stdout=subprocess.DEVNULL)
-        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_ensemble.so"))
+        self.lib = helpers.emu_library("libtsat_emu_ensemble.so")
         self.abi = abi
 
     def run(self, batch, X, U, Qd, Qfd, Rd, x0_sim, K, opts, plant=None, sat=None, noise_id0=None, want_trajectories=True):

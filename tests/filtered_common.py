@@ -9,20 +9,22 @@ THE REFERENCE (``pairs_of``) is ``reference_rollout.ensemble_loop`` with the rec
 The case of both tiers is ``sensed_common``'s; the filter's levels are FILT below. Every parity test first asserts its conditions on
 references alone with the bar ``gg_common.MOVED`` (``conditions``).
 
-Also: the argument lists of the two entry points and the ctypes binding of the emulated kernels (tests/emu/tsat_emu_filtered.cpp)."""
+Also, once for the four filter families (``Family``; the other three name theirs in model_filtered_common, mag_filtered_common and
+mag_bias_filtered_common): the argument lists of the two entry points (``TvCall``, ``PdCall``) and the ctypes binding of the emulated
+kernels (``EmuFiltered``; tests/emu/tsat_emu_filtered.cpp and its three siblings)."""
 import ctypes as C
+import dataclasses
+import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 
 import dispersed_common as dc
 import gg_common as gc
+import helpers
 import pd_common as pc
 import reference_rollout as rr
 import sensed_common as sc
-from conftest import ROOT
 
 FILTER_W = 9
 # the filter of the parity tests: it assumes the sensor's own attitude noise (sensed_common.SIGMAS), a bias random walk and an initial
@@ -190,13 +192,28 @@ def filter_options(abi, filt):
                              p0_bias=filt["p0_bias"], reserved=0)
 
 
-def _outputs(v, abi, filt, fo, estimates):
+@dataclasses.dataclass(frozen=True)
+class Family:
+    """what tells the calls of one filter from those of another"""
+    options: object    # (abi, filt) -> the options block of the filter
+    width: int         # FILTER_W: doubles of filt_final per realisation
+    levels: dict       # the filter of the parity tests
+    suffix: str        # tsat_{tvlqr,pd}_ensemble_<suffix>, emu_..._<suffix>, tests/emu/libtsat_emu_<suffix>.so
+    check: str         # the emulator's symbol of the library's check of the options
+
+
+SIX_STATE = Family(filter_options, FILTER_W, FILT, "filtered", "emu_filter_check")
+_LEVELS = object()     # the default of ``filt``: the family's own levels
+
+
+def _outputs(v, abi, family, filt, fo, estimates):
     """the three filter arguments of a call: ``fo`` 0 builds the options from ``filt`` (None: f = NULL and no outputs)"""
     T, M, N = v["T"], v["M"], v["o"].n_knots
-    v["f"] = (None if filt is None else filter_options(abi, filt)) if fo == 0 else fo
+    filt = family.levels if filt is _LEVELS else filt
+    v["f"] = (None if filt is None else family.options(abi, filt)) if fo == 0 else fo
     on = v["f"] is not None
     v["X_hat"] = np.full((T, M, N, 7), np.nan) if (on and estimates) else None
-    v["filt_final"] = np.full((T, M, FILTER_W), np.nan) if (on and estimates) else None
+    v["filt_final"] = np.full((T, M, family.width), np.nan) if (on and estimates) else None
 
 
 def _tail(v, abi):
@@ -204,17 +221,12 @@ def _tail(v, abi):
 
 
 class TvCall(sc.TvCall):
-    """sensed_common.TvCall followed by the three filter arguments: tsat_tvlqr_ensemble_filtered after the handle, or — ``emu=True`` —
-    emu_tvlqr_ensemble_filtered"""
+    """sensed_common.TvCall followed by the three filter arguments of ``family``: tsat_tvlqr_ensemble_<suffix> after the handle, or —
+    ``emu=True`` — emu_tvlqr_ensemble_<suffix>"""
 
-    def __init__(self, abi, *a, filt=FILT, fo=0, estimates=True, **kw):
+    def __init__(self, abi, *a, family=SIX_STATE, filt=_LEVELS, fo=0, estimates=True, **kw):
         super().__init__(abi, *a, **kw)
-        _outputs(self.v, abi, filt, fo, estimates)
-
-    def edit(self, **kw):
-        other = sc.TvCall.edit(self, **kw)
-        other.__class__ = TvCall
-        return other
+        _outputs(self.v, abi, family, filt, fo, estimates)
 
     def c_args(self, emu=False):
         return super().c_args(emu) + _tail(self.v, self.abi)
@@ -224,17 +236,12 @@ class TvCall(sc.TvCall):
 
 
 class PdCall(sc.PdCall):
-    """sensed_common.PdCall followed by the three filter arguments: tsat_pd_ensemble_filtered after the handle, or
-    emu_pd_ensemble_filtered"""
+    """sensed_common.PdCall followed by the three filter arguments of ``family``: tsat_pd_ensemble_<suffix> after the handle, or
+    emu_pd_ensemble_<suffix>"""
 
-    def __init__(self, abi, *a, filt=FILT, fo=0, estimates=True, **kw):
+    def __init__(self, abi, *a, family=SIX_STATE, filt=_LEVELS, fo=0, estimates=True, **kw):
         super().__init__(abi, *a, **kw)
-        _outputs(self.v, abi, filt, fo, estimates)
-
-    def edit(self, **kw):
-        other = sc.PdCall.edit(self, **kw)
-        other.__class__ = PdCall
-        return other
+        _outputs(self.v, abi, family, filt, fo, estimates)
 
     def c_args(self, names=pc.FIELDS):
         return super().c_args(names) + _tail(self.v, self.abi)
@@ -265,33 +272,35 @@ def filter_rejections(call):
 
 
 class EmuFiltered:
-    """ctypes binding of tests/emu/libtsat_emu_filtered.so (the four emulated kernels), built here by the emulator's pattern rule"""
+    """ctypes binding of tests/emu/libtsat_emu_<suffix>.so (the four emulated kernels of a family), built by the emulator's pattern rule"""
 
-    def __init__(self, abi):
-        d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "libtsat_emu_filtered.so"], stdout=subprocess.DEVNULL)
-        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_filtered.so"))
-        self.abi = abi
+    def __init__(self, abi, family=SIX_STATE):
+        self.lib = helpers.emu_library(f"libtsat_emu_{family.suffix}.so")
+        self.abi, self.family = abi, family
+
+    def _run(self, law, call, *a):
+        name = f"emu_{law}_ensemble_{self.family.suffix}"
+        rc = getattr(self.lib, name)(*call.c_args(*a))
+        if rc != 0:
+            raise RuntimeError(f"{name} rc={rc}")
+        return call.result()
 
     def tv(self, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K, **kw):
-        """emu_tvlqr_ensemble_filtered; keyword arguments as ``TvCall``; the result dict of ``tracking.attitude_ensemble_filtered``"""
-        call = TvCall(self.abi, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K=K, **kw)
-        rc = self.lib.emu_tvlqr_ensemble_filtered(*call.c_args(emu=True))
-        if rc != 0:
-            raise RuntimeError(f"emu_tvlqr_ensemble_filtered rc={rc}")
-        return call.result()
+        """emu_tvlqr_ensemble_<suffix>; keyword arguments as ``TvCall``; the result dict of ``tracking.attitude_ensemble_<suffix>``"""
+        return self._run("tvlqr", TvCall(self.abi, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K=K, family=self.family, **kw), True)
 
     def pd(self, batch, opts, x0_sim, kd, kp, **kw):
-        """emu_pd_ensemble_filtered; keyword arguments as ``PdCall``; the result dict of ``tracking.attitude_ensemble_pd_filtered``"""
-        call = PdCall(self.abi, batch, opts, x0_sim, kd, kp, **kw)
-        rc = self.lib.emu_pd_ensemble_filtered(*call.c_args())
-        if rc != 0:
-            raise RuntimeError(f"emu_pd_ensemble_filtered rc={rc}")
-        return call.result()
+        """emu_pd_ensemble_<suffix>; keyword arguments as ``PdCall``; the result dict of ``tracking.attitude_ensemble_pd_<suffix>``"""
+        return self._run("pd", PdCall(self.abi, batch, opts, x0_sim, kd, kp, family=self.family, **kw))
 
     def check(self, call):
-        """check_filter on the filter options of a call"""
+        """the library's check of the family's filter options on those of a call"""
         text = C.create_string_buffer(256)
         f = call.v["f"]
-        rc = self.lib.emu_filter_check(None if f is None else C.byref(f), text, C.c_int32(256))
+        rc = getattr(self.lib, self.family.check)(None if f is None else C.byref(f), text, C.c_int32(256))
         return rc, text.value.decode()
+
+
+def bindings(family):
+    """TvCall, PdCall and EmuFiltered of a family, for the module that names it"""
+    return (functools.partial(TvCall, family=family), functools.partial(PdCall, family=family), functools.partial(EmuFiltered, family=family))

@@ -15,15 +15,13 @@ final state by at least 1e-7, 100 x the X_sim bar.
 Also: the ctypes binding of the emulated kernels (tests/emu/tsat_emu_gg.cpp, built on demand by its own make fragment)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
 import dispersed_common as dc
 import ensemble_common as ec
+import helpers
 import mpc_held_common as hc
-from conftest import ROOT
 
 GM = 3.986004418e5          # km^3 / s^2
 MOVED = 1e-7                # what the term has to change on the references before a kernel is looked at
@@ -100,9 +98,7 @@ class EmuGg:
     """ctypes binding of tests/emu/libtsat_emu_gg.so (both emulated kernels), built here by its own make fragment"""
 
     def __init__(self, abi):
-        d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "libtsat_emu_gg.so"], stdout=subprocess.DEVNULL)
-        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_gg.so"))
+        self.lib = helpers.emu_library("libtsat_emu_gg.so")
         self.abi = abi
 
     def ensemble(self, batch, X, U, Qd, Qfd, Rd, x0_sim, K, opts, plant, Rtab, gm, sat=None, noise_id0=None):

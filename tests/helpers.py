@@ -1,5 +1,7 @@
-"""Helpers shared by the CPU and GPU test tiers: golden-fixture IO and option plumbing."""
+"""Helpers shared by the CPU and GPU test tiers: golden-fixture IO, option plumbing and the emulator libraries."""
+import ctypes as C
 import os
+import subprocess
 
 import numpy as np
 
@@ -8,6 +10,13 @@ BATCH_FIELDS = ("x0", "xf", "Btab", "btab_idx", "tau0", "dtau", "dt", "Jmat", "Q
 OPT_FIELDS = ("integrator", "max_outer", "max_inner", "max_linesearch", "dj_counter_limit", "cost_tol", "grad_tol",
               "constraint_tol", "penalty_init", "penalty_scale", "penalty_max", "dual_max", "reg_init", "reg_scale",
               "reg_min", "reg_max", "reg_fp", "ls_lower", "ls_upper", "max_state", "u_scale", "terminal_mask", "error_state")
+
+
+def emu_library(name):
+    """the library ``name`` of tests/emu as ctypes has it, (re)built first by the emulator's Makefile for the files it includes"""
+    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
+    subprocess.check_call(["make", "-C", d, name], stdout=subprocess.DEVNULL)
+    return C.CDLL(os.path.join(d, name))
 
 
 def save_case(path, batch, opts, res):

@@ -11,12 +11,10 @@ With ``filt=None`` it has to equal ``sensed_common.pairs_of`` with max |d| = 0; 
 The case of both tiers is ``sensed_common``'s; the filter's levels are MBFILT below. Every parity test first asserts its conditions on
 references alone with the bar ``gg_common.MOVED`` (``conditions``).
 
-Also: the argument lists of the two entry points and the ctypes binding of the emulated kernels
-(tests/emu/tsat_emu_mag_bias_filtered.cpp)."""
+Also: the filter as a ``filtered_common.Family``, which gives the argument lists of the two entry points (``TvCall``, ``PdCall``) and
+the ctypes binding of the emulated kernels (``EmuMagBiasFiltered``; tests/emu/tsat_emu_mag_bias_filtered.cpp)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
@@ -27,7 +25,6 @@ import mag_filtered_common as mc
 import pd_common as pc
 import reference_rollout as rr
 import sensed_common as sc
-from conftest import ROOT
 
 FILTER_W = 15
 # the filter of the parity tests: the mag filter's levels, an initial magnetometer-bias spread of the size of sensed_common.BIAS'
@@ -156,53 +153,8 @@ def mag_bias_filter_options(abi, filt):
                                     p0_att=filt["p0_att"], p0_bias=filt["p0_bias"], p0_mag=filt["p0_mag"], reserved=0)
 
 
-def _outputs(v, abi, filt, fo, estimates):
-    """the three filter arguments of a call: ``fo`` 0 builds the options from ``filt`` (None: f = NULL and no outputs)"""
-    T, M, N = v["T"], v["M"], v["o"].n_knots
-    v["f"] = (None if filt is None else mag_bias_filter_options(abi, filt)) if fo == 0 else fo
-    on = v["f"] is not None
-    v["X_hat"] = np.full((T, M, N, 7), np.nan) if (on and estimates) else None
-    v["filt_final"] = np.full((T, M, FILTER_W), np.nan) if (on and estimates) else None
-
-
-class TvCall(sc.TvCall):
-    """sensed_common.TvCall followed by the three filter arguments: tsat_tvlqr_ensemble_mag_bias_filtered after the handle, or —
-    ``emu=True`` — emu_tvlqr_ensemble_mag_bias_filtered"""
-
-    def __init__(self, abi, *a, filt=MBFILT, fo=0, estimates=True, **kw):
-        super().__init__(abi, *a, **kw)
-        _outputs(self.v, abi, filt, fo, estimates)
-
-    def edit(self, **kw):
-        other = sc.TvCall.edit(self, **kw)
-        other.__class__ = TvCall
-        return other
-
-    def c_args(self, emu=False):
-        return super().c_args(emu) + fc._tail(self.v, self.abi)
-
-    def result(self):
-        return dict(super().result(), X_hat=self.v["X_hat"], filt_final=self.v["filt_final"])
-
-
-class PdCall(sc.PdCall):
-    """sensed_common.PdCall followed by the three filter arguments: tsat_pd_ensemble_mag_bias_filtered after the handle, or
-    emu_pd_ensemble_mag_bias_filtered"""
-
-    def __init__(self, abi, *a, filt=MBFILT, fo=0, estimates=True, **kw):
-        super().__init__(abi, *a, **kw)
-        _outputs(self.v, abi, filt, fo, estimates)
-
-    def edit(self, **kw):
-        other = sc.PdCall.edit(self, **kw)
-        other.__class__ = PdCall
-        return other
-
-    def c_args(self, names=pc.FIELDS):
-        return super().c_args(names) + fc._tail(self.v, self.abi)
-
-    def result(self):
-        return dict(super().result(), X_hat=self.v["X_hat"], filt_final=self.v["filt_final"])
+FAMILY = fc.Family(mag_bias_filter_options, FILTER_W, MBFILT, "mag_bias_filtered", "emu_mag_bias_filter_check")
+TvCall, PdCall, EmuMagBiasFiltered = fc.bindings(FAMILY)
 
 
 def filter_rejections(call):
@@ -231,42 +183,6 @@ def filter_rejections(call):
         ("the default options as they are", call.edit(f=default), "sigma_m must be > 0"),
         ("reserved 1", call.edit(f=fo(reserved=1)), "reserved must be 0"),
     ]
-
-
-class EmuMagBiasFiltered:
-    """ctypes binding of tests/emu/libtsat_emu_mag_bias_filtered.so (the four emulated kernels), built here by the emulator's pattern
-    rule"""
-
-    def __init__(self, abi):
-        d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "libtsat_emu_mag_bias_filtered.so"], stdout=subprocess.DEVNULL)
-        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_mag_bias_filtered.so"))
-        self.abi = abi
-
-    def tv(self, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K, **kw):
-        """emu_tvlqr_ensemble_mag_bias_filtered; keyword arguments as ``TvCall``; the result dict of
-        ``tracking.attitude_ensemble_mag_bias_filtered``"""
-        call = TvCall(self.abi, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K=K, **kw)
-        rc = self.lib.emu_tvlqr_ensemble_mag_bias_filtered(*call.c_args(emu=True))
-        if rc != 0:
-            raise RuntimeError(f"emu_tvlqr_ensemble_mag_bias_filtered rc={rc}")
-        return call.result()
-
-    def pd(self, batch, opts, x0_sim, kd, kp, **kw):
-        """emu_pd_ensemble_mag_bias_filtered; keyword arguments as ``PdCall``; the result dict of
-        ``tracking.attitude_ensemble_pd_mag_bias_filtered``"""
-        call = PdCall(self.abi, batch, opts, x0_sim, kd, kp, **kw)
-        rc = self.lib.emu_pd_ensemble_mag_bias_filtered(*call.c_args())
-        if rc != 0:
-            raise RuntimeError(f"emu_pd_ensemble_mag_bias_filtered rc={rc}")
-        return call.result()
-
-    def check(self, call):
-        """check_mag_bias_filter on the filter options of a call"""
-        text = C.create_string_buffer(256)
-        f = call.v["f"]
-        rc = self.lib.emu_mag_bias_filter_check(None if f is None else C.byref(f), text, C.c_int32(256))
-        return rc, text.value.decode()
 
 
 fast_table = mc.fast_table

@@ -11,21 +11,16 @@ The case of both tiers is ``sensed_common``'s; the filter's levels are FILT belo
 references alone with the bar ``gg_common.MOVED`` (``conditions``): terms of the recursion are switched off through ``variant``, which
 is a device of the tests, not a mode of the product.
 
-Also: the argument lists of the two entry points and the ctypes binding of the emulated kernels
-(tests/emu/tsat_emu_model_filtered.cpp)."""
-import ctypes as C
+Also: the filter as a ``filtered_common.Family``, which gives the argument lists of the two entry points (``TvCall``, ``PdCall``) and
+the ctypes binding of the emulated kernels (``EmuModelFiltered``; tests/emu/tsat_emu_model_filtered.cpp)."""
 import math
-import os
-import subprocess
 
 import numpy as np
 
 import filtered_common as fc
 import gg_common as gc
-import pd_common as pc
 import reference_rollout as rr
 import sensed_common as sc
-from conftest import ROOT
 
 FILTER_W = 12
 # the filter of the parity tests: the sensor's own attitude noise (sensed_common.SIGMAS), a gyro noise of 5e-3 rad/s as
@@ -201,57 +196,8 @@ def first_record(filt):
                  np.full(3, filt["p0_bias"])]
 
 
-def _outputs(v, abi, filt, fo, estimates):
-    """the three filter arguments of a call: ``fo`` 0 builds the options from ``filt`` (None: f = NULL and no outputs)"""
-    T, M, N = v["T"], v["M"], v["o"].n_knots
-    v["f"] = (None if filt is None else filter_options(abi, filt)) if fo == 0 else fo
-    on = v["f"] is not None
-    v["X_hat"] = np.full((T, M, N, 7), np.nan) if (on and estimates) else None
-    v["filt_final"] = np.full((T, M, FILTER_W), np.nan) if (on and estimates) else None
-
-
-def _tail(v, abi):
-    return [None if v["f"] is None else C.byref(v["f"]), abi.as_dp(v["X_hat"]), abi.as_dp(v["filt_final"])]
-
-
-class TvCall(sc.TvCall):
-    """sensed_common.TvCall followed by the three filter arguments: tsat_tvlqr_ensemble_model_filtered after the handle, or —
-    ``emu=True`` — emu_tvlqr_ensemble_model_filtered"""
-
-    def __init__(self, abi, *a, filt=FILT, fo=0, estimates=True, **kw):
-        super().__init__(abi, *a, **kw)
-        _outputs(self.v, abi, filt, fo, estimates)
-
-    def edit(self, **kw):
-        other = sc.TvCall.edit(self, **kw)
-        other.__class__ = TvCall
-        return other
-
-    def c_args(self, emu=False):
-        return super().c_args(emu) + _tail(self.v, self.abi)
-
-    def result(self):
-        return dict(super().result(), X_hat=self.v["X_hat"], filt_final=self.v["filt_final"])
-
-
-class PdCall(sc.PdCall):
-    """sensed_common.PdCall followed by the three filter arguments: tsat_pd_ensemble_model_filtered after the handle, or
-    emu_pd_ensemble_model_filtered"""
-
-    def __init__(self, abi, *a, filt=FILT, fo=0, estimates=True, **kw):
-        super().__init__(abi, *a, **kw)
-        _outputs(self.v, abi, filt, fo, estimates)
-
-    def edit(self, **kw):
-        other = sc.PdCall.edit(self, **kw)
-        other.__class__ = PdCall
-        return other
-
-    def c_args(self, names=pc.FIELDS):
-        return super().c_args(names) + _tail(self.v, self.abi)
-
-    def result(self):
-        return dict(super().result(), X_hat=self.v["X_hat"], filt_final=self.v["filt_final"])
+FAMILY = fc.Family(filter_options, FILTER_W, FILT, "model_filtered", "emu_model_filter_check")
+TvCall, PdCall, EmuModelFiltered = fc.bindings(FAMILY)
 
 
 def filter_rejections(call):
@@ -318,35 +264,3 @@ def assert_filter_works(c):
     db = np.abs(ref["filt_final"][:, 0:3] - c["sensor"][pr[:, 0], pr[:, 1], 0:3])
     print(f"|b^ - bw| / sqrt(diag P_bb) at the end: max {float(np.max(db / ref['filt_final'][:, 9:12])):.2f}")
     assert np.all(db < 3.0 * ref["filt_final"][:, 9:12]), "the bias estimate is outside 3 sigma of its own covariance"
-
-
-class EmuModelFiltered:
-    """ctypes binding of tests/emu/libtsat_emu_model_filtered.so (the four emulated kernels), built here by the emulator's pattern
-    rule"""
-
-    def __init__(self, abi):
-        d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "libtsat_emu_model_filtered.so"], stdout=subprocess.DEVNULL)
-        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_model_filtered.so"))
-        self.abi = abi
-
-    def tv(self, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K, **kw):
-        call = TvCall(self.abi, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K=K, **kw)
-        rc = self.lib.emu_tvlqr_ensemble_model_filtered(*call.c_args(emu=True))
-        if rc != 0:
-            raise RuntimeError(f"emu_tvlqr_ensemble_model_filtered rc={rc}")
-        return call.result()
-
-    def pd(self, batch, opts, x0_sim, kd, kp, **kw):
-        call = PdCall(self.abi, batch, opts, x0_sim, kd, kp, **kw)
-        rc = self.lib.emu_pd_ensemble_model_filtered(*call.c_args())
-        if rc != 0:
-            raise RuntimeError(f"emu_pd_ensemble_model_filtered rc={rc}")
-        return call.result()
-
-    def check(self, call):
-        """check_model_filter on the filter options of a call"""
-        text = C.create_string_buffer(256)
-        f = call.v["f"]
-        rc = self.lib.emu_model_filter_check(None if f is None else C.byref(f), text, C.c_int32(256))
-        return rc, text.value.decode()

@@ -15,16 +15,14 @@ Also: the argument list of the entry point as named fields (``Call``), which the
 to the library's own validation function — through the emulator driver (``EmuPd.check``) on the CPU tier, through
 tsat_pd_ensemble itself on the GPU tier —, and the ctypes binding of the emulated kernels (tests/emu/tsat_emu_pd.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import dispersed_common as dc
 import ensemble_common as ec
 import gg_common as gc
+import helpers
 import mpc_held_common as hc
-from conftest import ROOT
 
 KD = np.array([2e-5, 3e-5, 1e-5])        # N m s / rad
 KP = np.array([4e-7, 2e-7, 6e-7])        # N m
@@ -132,7 +130,7 @@ class Call:
 
     def edit(self, **kw):
         """a copy with the named fields replaced (float arrays made contiguous); ``o_<field>=value`` edits the options block"""
-        other = Call.__new__(Call)
+        other = type(self).__new__(type(self))
         other.abi, other.v = self.abi, dict(self.v)
         for k, val in kw.items():
             if k.startswith("o_"):
@@ -217,9 +215,7 @@ class EmuPd:
     """ctypes binding of tests/emu/libtsat_emu_pd.so, built here by its own make fragment"""
 
     def __init__(self, abi):
-        d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "libtsat_emu_pd.so"], stdout=subprocess.DEVNULL)
-        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_pd.so"))
+        self.lib = helpers.emu_library("libtsat_emu_pd.so")
         self.abi = abi
 
     def run(self, batch, opts, x0_sim, kd, kp, **kw):

@@ -17,14 +17,12 @@ Also: the ctypes binding of the emulated kernels (tests/emu/tsat_emu_sensed.cpp,
 argument lists of the two entry points for the GPU tier."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
 import dispersed_common as dc
+import helpers
 import pd_common as pc
-from conftest import ROOT
 
 R_LQR = 0.5e-6
 KD, KP = 10.0 * pc.KD, 10.0 * pc.KP
@@ -118,7 +116,7 @@ class TvCall:
                       s=sensor_options(abi, sens, latency) if so == 0 else so, sensor=_dc(sensor))
 
     def edit(self, **kw):
-        other = TvCall.__new__(TvCall)
+        other = type(self).__new__(type(self))
         other.abi, other.v = self.abi, dict(self.v)
         for k, val in kw.items():
             assert k in other.v, k
@@ -136,9 +134,25 @@ class TvCall:
               [vp(v["stats"]), d(v["summary"]), vp(v["stats_nominal"]), None, d(v["X_sim"])]
         return head + mid + [ip(v["n_clipped"]), d(v["Rtab"]), C.c_double(v["gm"]), None if v["s"] is None else C.byref(v["s"]), d(v["sensor"])]
 
+    def parent_args(self, gravity):
+        """the arguments of the emulated parents out of the call's own: emu_tvlqr_ensemble_dispersed, or — ``gravity`` —
+        emu_tvlqr_ensemble_gg, which end before the sensor's"""
+        return self.c_args(emu=True)[:30 if gravity else 28]
+
     def result(self):
         v = self.v
         return dict(stats=v["stats"], summary=v["summary"], nominal=v["stats_nominal"], X_sim=v["X_sim"], n_clipped=v["n_clipped"])
+
+
+def smallest_tv_call(pkg, opts):
+    """the smallest valid TVLQR call — T = 1, N = 4, M = 1, zero gains, with a plant, limits and an orbit table — for the tests of
+    what the emulated drivers reject"""
+    import gg_common as gc
+    import mpc_held_common as hc
+    b = hc.mpc_batch(pkg, T=1, N=4, rows=4)
+    X, U, K = np.repeat(b.x0[:, None], 4, axis=1), np.zeros((1, 3, 3)), np.zeros((1, 3, 6, 3))
+    return TvCall(pkg._abi, b, opts, X, U, *pkg.tracking.tvlqr_weights(1, r=0.5e3), b.x0[:, None], K=K, plant=hc.plants(pkg, b, 1),
+                  Rtab=gc.orbit(pkg, 4, 0.2)[None], gm=gc.GM, sat=hc.SAT)
 
 
 class PdCall(pc.Call):
@@ -148,11 +162,6 @@ class PdCall(pc.Call):
         super().__init__(abi, batch, opts, x0_sim, kd, kp, **kw)
         self.v["s"] = sensor_options(abi, sens, latency) if so == 0 else so
         self.v["sensor"] = _dc(sensor)
-
-    def edit(self, **kw):
-        other = pc.Call.edit(self, **kw)
-        other.__class__ = PdCall
-        return other
 
     def c_args(self, names=pc.FIELDS):
         s = self.v["s"]
@@ -193,9 +202,7 @@ class EmuSensed:
     """ctypes binding of tests/emu/libtsat_emu_sensed.so (the four emulated kernels), built here by its own make fragment"""
 
     def __init__(self, abi):
-        d = os.path.join(ROOT, "tests", "emu")
-        subprocess.check_call(["make", "-C", d, "libtsat_emu_sensed.so"], stdout=subprocess.DEVNULL)
-        self.lib = C.CDLL(os.path.join(d, "libtsat_emu_sensed.so"))
+        self.lib = helpers.emu_library("libtsat_emu_sensed.so")
         self.abi = abi
 
     def tv(self, batch, opts, X, U, Qd, Qfd, Rd, x0_sim, K, **kw):

@@ -12,6 +12,7 @@ import pytest
 
 import dispersed_common as dc
 import ensemble_common as ec
+import sensed_common as sc
 
 
 @pytest.fixture(scope="module")
@@ -42,6 +43,15 @@ def ragged_case(pkg, ol):
 
 def _box(b):
     return b.ulo, b.uhi
+
+
+def test_emulated_driver_rejects_a_null_plant_and_half_a_limit(pkg, ol, emu_disp):
+    """what tsat_tvlqr_ensemble_dispersed rejects of its own three arguments, through the emulator driver: -1 and nothing run"""
+    good = sc.smallest_tv_call(pkg, ec.tv_options(ol))
+    fn = emu_disp.lib.emu_tvlqr_ensemble_dispersed
+    assert fn(*good.parent_args(False)) == 0 and fn(*good.edit(sat_lo=None, sat_hi=None).parent_args(False)) == 0
+    for label, call in (("plant NULL", good.edit(plant=None)), ("sat_hi NULL", good.edit(sat_hi=None)), ("sat_lo NULL", good.edit(sat_lo=None))):
+        assert fn(*call.parent_args(False)) == -1, label
 
 
 def test_reference_is_pinned_to_the_oracle(pkg, ol, mc_case):

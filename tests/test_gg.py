@@ -12,6 +12,7 @@ import dispersed_common as dc
 import ensemble_common as ec
 import gg_common as gc
 import mpc_held_common as hc
+import sensed_common as sc
 
 IDS = np.array([7, 2 ** 33 + 1], dtype=np.int64)
 
@@ -137,7 +138,7 @@ def test_emulated_hold_at_r1_does_not_see_the_feedback_switch(pkg, ol, emu):
     assert np.max(np.abs(off["X_hist"] - a["X_hist"])) >= gc.MOVED
 
 
-def test_rejected_arguments(pkg, emu):
+def test_rejected_arguments(pkg, ol, emu):
     """check_gravity, which both entry points call after their parents' checks"""
     good = gc.orbit(pkg, 12, 0.2)
     assert emu.check(good, gc.GM) == (0, "") and emu.check(good, 0.0) == (0, "")
@@ -153,6 +154,13 @@ def test_rejected_arguments(pkg, emu):
                         (good, -1.0, "gm must be finite and >= 0"), (good, np.nan, "gm must"), (good, np.inf, "gm must")):
         rc, text = emu.check(R, gm)
         assert rc == -1 and word in text, (word, text)
+    # the emulated ensemble refuses a null plant, half a limit and — unlike the sensed calls — a null table whatever gm is
+    call = sc.smallest_tv_call(pkg, ec.tv_options(ol))
+    fn = emu.lib.emu_tvlqr_ensemble_gg
+    assert fn(*call.parent_args(True)) == 0 and fn(*call.edit(sat_lo=None, sat_hi=None).parent_args(True)) == 0
+    for label, bad in (("plant NULL", call.edit(plant=None)), ("sat_hi NULL", call.edit(sat_hi=None)), ("sat_lo NULL", call.edit(sat_lo=None)),
+                       ("Rtab NULL", call.edit(Rtab=None)), ("Rtab NULL, gm 0", call.edit(Rtab=None, gm=0.0)), ("gm negative", call.edit(gm=-1.0))):
+        assert fn(*bad.parent_args(True)) == -1, label
     # without a handle the entry points themselves are codes, not crashes
     lib = pkg._abi.load()
     assert lib.tsat_mpc_run_held_gg(None, None, None, 1, 0, 1, 1, None, None, None, None, None, None, None, None, None, None, None, 0.0) == -1
