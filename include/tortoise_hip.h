@@ -803,6 +803,82 @@ int  tsat_pd_ensemble_mag_bias_filtered(tsat_handle* h, const tsat_tvlqr_options
                          const tsat_sensor_options* s, const double* sensor,
                          const tsat_mag_bias_filter_options* f, double* X_hat, double* filt_final);
 
+/* The MODEL-BASED rate filter UPDATED BY THE MAGNETOMETER: the two model-filtered calls (tsat_model_filter_options above) with
+ * update a. (attitude) replaced by the magnetometer update of the mag-filtered calls. It is the filter a magnetorquer-only satellite
+ * can fly — a gyro, a magnetometer and ONE attitude fix at acquisition — and it still smooths the gyro: the law reads a rate that
+ * was propagated on the model, not w_m - b^ (the reference loop of tests/model_mag_filtered_common.py, 400 knots at dt = 0.2 s,
+ * 0.38 deg/s gyro noise, 5e-7 T magnetometer noise, a 2e-3 rad/s gyro bias: rms rate error over the last half 9.2e-4 rad/s against
+ * the raw sample's 1.17e-2, rms attitude error 2.8 deg against the mag filter's 3.0 deg).
+ * Options (launch-uniform, all standard deviations): sigma_v, sigma_w, sigma_u, sigma_g, p0_att, p0_bias of tsat_model_filter_options
+ * and
+ *   sigma_m   magnetometer noise the filter assumes, in units of Btab, > 0
+ * tsat_model_mag_filter_default_options fills sigma_g = 0.38 pi / 180, p0_att = pi / 180 and the rest 0. sigma_w and sigma_m have
+ * no default: sigma_w is the caller's choice, sigma_m is in the units of the caller's table and is rejected at 0.
+ * State per realisation: the model filter's, in the same 58-value record (TSAT_MODEL_FILTER_STATE_W) — q^ 4, w^ 3, b^ 3, the last
+ * command 3, and P over (dtheta, dw, db) as the upper triangles of A (theta theta), W (w w), D (b b) and, row-major 3 x 3,
+ * X (theta w), B (theta b), Y (w b). The recursion of tsat_model_filter_options applies unchanged except as stated here. The filter
+ * runs over the samples m_j = (w_m, q_m, b_m) of the measurement of the sensed calls; r_j is the stage-0 field row of knot j, the
+ * row b_m of knot j was formed with.
+ *   first(m_0):  the model filter's: the one attitude fix comes from q_m of sample 0, w^ = w_m, the consistent start with the
+ *     -p0_bias^2 cross block included. q_m of every later sample is ignored. No magnetometer update is made at sample 0.
+ *   predict(u):  the model filter's, with the rows of the knot being crossed.
+ *   update(m_j), j >= 1:  two 3-vector updates in this order, each applying its whole 9-vector delta = K z:
+ *     a. magnetometer  n = q^ / |q^|;  z = b_m - qrot(n, r_j), as the true body field is formed;  Hm = -C(n) [r_j]x, the mag
+ *                      filter's H;  P H^T = [A Hm^T; X^T Hm^T; B^T Hm^T];  S = Hm A Hm^T + sigma_m^2 I (its upper triangle,
+ *                      mirrored; positive definite because sigma_m > 0);  K = P H^T S^-1
+ *     b. gyro          the model filter's b., operation for operation
+ *     both: q^ <- normalise(q^ (x) [1; dtheta / 2]), w^ += dw, b^ += db;  P <- P - K S K^T.
+ *   A zero field row gives Hm = 0 and K = 0 in a.: an update that changes nothing, without a branch. Nothing asks whether a sigma
+ *   is zero.
+ *   What the law sees at knot k is the model filter's rule — latency 0: k = 0 first; k >= 1 predict(u_{k-1}), then update(m_k)
+ *   against r_k. Latency 1: y_0 from first(m_0); k = 1: m_0 arrives a second time and makes no update, then predict(u_0); k >= 2:
+ *   update(m_{k-1}) against r_{k-1} — the delayed sample's own row, not r_k — then predict(u_{k-1}); for k >= 1, y_k is the model
+ *   prediction across the delay, rate included.
+ * The magnetometer is sampled ONCE per knot: the PD law's b_m is the very reading the filter used (not filtered). Under the TVLQR
+ * law the reading is drawn too (the sensed and model-filtered TVLQR calls draw none). stats_nominal flies the ideal sensor through
+ * the same filter. The magnetometer bias of `sensor` is not estimated: it enters z unmodelled.
+ *   X_hat       7 x N x M x T or NULL   row k holds y_k for k < n_knots[t] - 1, the rest is zero (the layout of X_sim)
+ *   filt_final  12 x M x T or NULL      b^ (3), sqrt(diag A) (3), sqrt(diag W) (3), sqrt(diag D) (3), taken directly after the last
+ *                                       update made up to and including the call at k = n_knots[t] - 2; the record of first when
+ *                                       none was made (TSAT_MODEL_FILTER_W)
+ * f == NULL is the sensed call, byte for byte (it is dispatched there); X_hat and filt_final must then be NULL.
+ * Rejected with -1 (text in tsat_ensemble_last_error; nothing is launched and no workspace grows): a non-finite or negative
+ * option; sigma_g == 0; sigma_m == 0; reserved != 0; f NULL with X_hat or filt_final non-NULL; and everything the sensed call
+ * rejects. */
+struct tsat_model_mag_filter_options {
+  double  sigma_v;
+  double  sigma_w;
+  double  sigma_u;
+  double  sigma_g;
+  double  sigma_m;
+  double  p0_att;
+  double  p0_bias;
+  int32_t reserved;         /* 0 */
+};
+typedef struct tsat_model_mag_filter_options tsat_model_mag_filter_options;
+void tsat_model_mag_filter_default_options(tsat_model_mag_filter_options* f);
+int  tsat_tvlqr_ensemble_model_mag_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                         const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* K_lqr, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor,
+                         const tsat_model_mag_filter_options* f, double* X_hat, double* filt_final);
+int  tsat_pd_ensemble_model_mag_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat,
+                         const double* kd, const double* kp, int32_t feedforward, int32_t limit_mode,
+                         const double* x0_sim, const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor,
+                         const tsat_model_mag_filter_options* f, double* X_hat, double* filt_final);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Receding-horizon re-solve on the RESIDENT batch (BASELINE.json configs[4]). NOT in the reference —
  * it tracks its plan with TVLQR (src/attitude_controller.jl:1-48); defined here as: n_steps times

@@ -122,6 +122,17 @@ class MagBiasFilterOptions(C.Structure):
 
 assert C.sizeof(MagBiasFilterOptions) == 64
 
+
+class ModelMagFilterOptions(C.Structure):
+    """``tsat_model_mag_filter_options`` — what the nine-state model-based EKF updated by the magnetometer assumes (standard
+    deviations; ``sigma_m`` in the units of the field table)."""
+
+    _fields_ = [("sigma_v", C.c_double), ("sigma_w", C.c_double), ("sigma_u", C.c_double), ("sigma_g", C.c_double),
+                ("sigma_m", C.c_double), ("p0_att", C.c_double), ("p0_bias", C.c_double), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(ModelMagFilterOptions) == 64
+
 TVLQR_STATS_DTYPE = np.dtype([("slew_index", "<i4"), ("failed", "<i4"), ("slew_time", "<f8"), ("final_w_norm", "<f8"),
                               ("final_angle", "<f8")])
 assert TVLQR_STATS_DTYPE.itemsize == 32
@@ -235,6 +246,15 @@ PROTOTYPES = {
                                                      _ip, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64),
                                                      _ip, _dp, _dp, _dp, C.c_void_p, _dp, C.c_void_p, _dp, _ip, _dp, C.c_double,
                                                      C.POINTER(SensorOptions), _dp, C.POINTER(MagBiasFilterOptions), _dp, _dp]),
+    "tsat_model_mag_filter_default_options": (None, [C.POINTER(ModelMagFilterOptions)]),
+    "tsat_tvlqr_ensemble_model_mag_filtered": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp,
+                                                         _dp, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp,
+                                                         _dp, C.c_void_p, _dp, C.c_void_p, _dp, _dp, _ip, _dp, C.c_double,
+                                                         C.POINTER(SensorOptions), _dp, C.POINTER(ModelMagFilterOptions), _dp, _dp]),
+    "tsat_pd_ensemble_model_mag_filtered": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp,
+                                                      _ip, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64),
+                                                      _ip, _dp, _dp, _dp, C.c_void_p, _dp, C.c_void_p, _dp, _ip, _dp, C.c_double,
+                                                      C.POINTER(SensorOptions), _dp, C.POINTER(ModelMagFilterOptions), _dp, _dp]),
     "tsat_mpc_run_held_sensed": (C.c_int, [C.c_void_p, C.POINTER(Options), C.POINTER(TvlqrOptions), C.c_int32, C.c_int64, C.c_int32,
                                            C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_int64), _dp, _dp, C.c_void_p, C.c_void_p, _ip,
                                            C.POINTER(C.c_float), _dp, C.c_double, C.POINTER(SensorOptions), _dp, _dp]),

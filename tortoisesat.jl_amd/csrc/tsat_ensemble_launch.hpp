@@ -6,6 +6,7 @@
 #include "tsat_model_filtered.hpp"
 #include "tsat_mag_filtered.hpp"
 #include "tsat_mag_bias_filtered.hpp"
+#include "tsat_model_mag_filtered.hpp"
 
 // pack and roll-out of tsat_tvlqr_ensemble_gg (tsat_kernels_gg.hip)
 hipError_t tsat_launch_gg_pack(const double* R, double gm, double* GT, int64_t rows, hipStream_t stream);
@@ -28,3 +29,6 @@ hipError_t tsat_launch_mag_filtered_pd(const tsat::MagFilteredPdArgs<double>& a,
 // roll-outs of the mag-bias-filtered calls (tsat_kernels_mag_bias_filtered.hip)
 hipError_t tsat_launch_mag_bias_filtered_tv(const tsat::MagBiasFilteredTvArgs<double>& a, int waves, hipStream_t stream);
 hipError_t tsat_launch_mag_bias_filtered_pd(const tsat::MagBiasFilteredPdArgs<double>& a, int waves, hipStream_t stream);
+// roll-outs of the model-mag-filtered calls (tsat_kernels_model_mag_filtered.hip)
+hipError_t tsat_launch_model_mag_filtered_tv(const tsat::ModelMagFilteredTvArgs<double>& a, int waves, hipStream_t stream);
+hipError_t tsat_launch_model_mag_filtered_pd(const tsat::ModelMagFilteredPdArgs<double>& a, int waves, hipStream_t stream);

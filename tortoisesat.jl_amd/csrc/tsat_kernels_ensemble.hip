@@ -1,6 +1,6 @@
-// tsat_kernels_ensemble.hip — the host side of the sixteen ensemble entry points (include/tortoise_hip.h): tsat_tvlqr_ensemble and its
-// _dispersed, _gg, _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered, and tsat_pd_ensemble with its _sensed,
-// _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered. A
+// tsat_kernels_ensemble.hip — the host side of the eighteen ensemble entry points (include/tortoise_hip.h): tsat_tvlqr_ensemble and its
+// _dispersed, _gg, _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered, _model_mag_filtered, and tsat_pd_ensemble
+// with its _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered, _model_mag_filtered. A
 // translation unit of its own, built on the public ABI: `struct tsat_handle` is private to tsat_kernels.hip, so a call keeps its own
 // buffers and stream. An entry point only describes its call (`Call`: the common arrays, the part of its law, and what it adds —
 // Dispersion, Gravity, Sensing, Filtering); run_call goes through the stages once, all of it synchronous:
@@ -32,6 +32,7 @@
 #include "tsat_model_filtered.hpp"
 #include "tsat_mag_filtered.hpp"
 #include "tsat_mag_bias_filtered.hpp"
+#include "tsat_model_mag_filtered.hpp"
 #include "tsat_ensemble_launch.hpp"
 
 using namespace tsat;
@@ -142,10 +143,12 @@ struct Filtering {
   const tsat_model_filter_options* mf = nullptr;   // the nine-state filter in place of f
   const tsat_mag_filter_options* gf = nullptr;     // ... or the magnetometer-updated one
   const tsat_mag_bias_filter_options* bf = nullptr;   // ... or the one that estimates the magnetometer bias too
+  const tsat_model_mag_filter_options* mg = nullptr;  // ... or the nine-state filter updated by the magnetometer
   std::string check() const {
+    if (mg) return check_model_mag_filter(mg);
     return bf ? check_mag_bias_filter(bf) : (gf ? check_mag_filter(gf) : (mf ? check_model_filter(mf) : check_filter(f)));
   }
-  size_t final_w() const { return bf ? (size_t)MBFFW : (mf ? (size_t)MFFW : (size_t)FFW); }
+  size_t final_w() const { return bf ? (size_t)MBFFW : ((mf || mg) ? (size_t)MFFW : (size_t)FFW); }
 };
 
 // f == NULL is the sensed parent, which has no X_hat and no filt_final to fill
@@ -260,6 +263,7 @@ hipError_t launch_tvlqr(const EnsArgs<double>& a, const DispArgs<double>* d, con
     return hipGetLastError();
   }
   const GgEnsArgs<double> g{*d, GT};
+  if (fl && fl->mg) return tsat_launch_model_mag_filtered_tv({g, model_mag_filt_args(*fl->mg, *sa, a, dXH, dFF)}, nw, st);
   if (fl && fl->bf) return tsat_launch_mag_bias_filtered_tv({g, mag_bias_filt_args(*fl->bf, *sa, a, dXH, dFF)}, nw, st);
   if (fl && fl->gf) return tsat_launch_mag_filtered_tv({g, mag_filt_args(*fl->gf, *sa, a, dXH, dFF)}, nw, st);
   if (fl && fl->mf) return tsat_launch_model_filtered_tv({g, model_filt_args(*fl->mf, *sa, a, dXH, dFF)}, nw, st);
@@ -272,6 +276,7 @@ hipError_t launch_tvlqr(const EnsArgs<double>& a, const DispArgs<double>* d, con
 
 hipError_t launch_pd(const PdArgs<double>& pa, const SensArgs<double>* sa, const Filtering* fl, double* dXH, double* dFF, int nw,
                      hipStream_t st) {
+  if (fl && fl->mg) return tsat_launch_model_mag_filtered_pd({pa, model_mag_filt_args(*fl->mg, *sa, pa.d.e, dXH, dFF)}, nw, st);
   if (fl && fl->bf) return tsat_launch_mag_bias_filtered_pd({pa, mag_bias_filt_args(*fl->bf, *sa, pa.d.e, dXH, dFF)}, nw, st);
   if (fl && fl->gf) return tsat_launch_mag_filtered_pd({pa, mag_filt_args(*fl->gf, *sa, pa.d.e, dXH, dFF)}, nw, st);
   if (fl && fl->mf) return tsat_launch_model_filtered_pd({pa, model_filt_args(*fl->mf, *sa, pa.d.e, dXH, dFF)}, nw, st);
@@ -590,6 +595,36 @@ int tsat_pd_ensemble_mag_bias_filtered(tsat_handle* h, const tsat_tvlqr_options*
   return run_call(c);
 }
 
+int tsat_pd_ensemble_model_mag_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                                        const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                                        const double* dtau, const double* dt, const double* Jmat, const double* kd, const double* kp,
+                                        int32_t feedforward, int32_t limit_mode, const double* x0_sim, const double* x0_nom,
+                                        const int64_t* noise_id0, const int32_t* n_knots, const double* plant, const double* sat_lo,
+                                        const double* sat_hi, tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                                        double* X_sim, int32_t* n_clipped, const double* Rtab, double gm, const tsat_sensor_options* sn,
+                                        const double* sensor, const tsat_model_mag_filter_options* f, double* X_hat, double* filt_final) {
+  if (!f && unfiltered_outputs(X_hat, filt_final)) return -1;
+  const PdPart law{kd, kp, feedforward, limit_mode, x0_nom};
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  const Sensing se{sn, sensor};
+  const Filtering fl{nullptr, X_hat, filt_final, nullptr, nullptr, nullptr, f};
+  Call c{f ? "tsat_pd_ensemble_model_mag_filtered" : "tsat_pd_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt,
+         Jmat, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, X_sim};
+  c.pd = &law; c.disp = &d; c.grav = &g; c.sens = &se; c.filt = f ? &fl : nullptr;
+  return run_call(c);
+}
+
+void tsat_model_mag_filter_default_options(tsat_model_mag_filter_options* f) {
+  if (!f) return;
+  const double pi = 3.14159265358979323846;
+  f->sigma_v = 0.0; f->sigma_w = 0.0; f->sigma_u = 0.0;       // sigma_w: the caller's choice, as for the model filter
+  f->sigma_g = 0.38 * pi / 180.0;
+  f->sigma_m = 0.0;                                            // in the units of the caller's table: no default, and 0 is rejected
+  f->p0_att = pi / 180.0; f->p0_bias = 0.0;
+  f->reserved = 0;
+}
+
 void tsat_mag_bias_filter_default_options(tsat_mag_bias_filter_options* f) {
   if (!f) return;
   tsat_mag_filter_options g;
@@ -770,6 +805,27 @@ int tsat_tvlqr_ensemble_mag_bias_filtered(tsat_handle* h, const tsat_tvlqr_optio
   const Sensing se{sn, sensor};
   const Filtering fl{nullptr, X_hat, filt_final, nullptr, nullptr, f};
   Call c{f ? "tsat_tvlqr_ensemble_mag_bias_filtered" : "tsat_tvlqr_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0,
+         dtau, dt, Jmat, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, X_sim};
+  c.tv = &law; c.disp = &d; c.grav = &g; c.sens = &se; c.filt = f ? &fl : nullptr;
+  return run_call(c);
+}
+
+int tsat_tvlqr_ensemble_model_mag_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                                           const double* U, const double* xf, const double* Btab, const int32_t* btab_idx,
+                                           const double* tau0, const double* dtau, const double* dt, const double* Jmat, const double* Qd,
+                                           const double* Qfd, const double* Rd, const double* x0_sim, const int64_t* noise_id0,
+                                           const int32_t* n_knots, const double* plant, const double* sat_lo, const double* sat_hi,
+                                           tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal, double* K_lqr,
+                                           double* X_sim, int32_t* n_clipped, const double* Rtab, double gm, const tsat_sensor_options* sn,
+                                           const double* sensor, const tsat_model_mag_filter_options* f, double* X_hat,
+                                           double* filt_final) {
+  if (!f && unfiltered_outputs(X_hat, filt_final)) return -1;
+  const TvlqrPart law{Qd, Qfd, Rd, K_lqr};
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  const Sensing se{sn, sensor};
+  const Filtering fl{nullptr, X_hat, filt_final, nullptr, nullptr, nullptr, f};
+  Call c{f ? "tsat_tvlqr_ensemble_model_mag_filtered" : "tsat_tvlqr_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0,
          dtau, dt, Jmat, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, X_sim};
   c.tv = &law; c.disp = &d; c.grav = &g; c.sens = &se; c.filt = f ? &fl : nullptr;
   return run_call(c);

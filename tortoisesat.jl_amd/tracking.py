@@ -376,7 +376,7 @@ def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, s
     """``tsat_pd_ensemble``, or with ``sensing`` = (SensorOptions, sensor array or None) ``tsat_pd_ensemble_sensed``, or with
     ``filtering`` = (FilterOptions, X_hat or None, filt_final or None) besides ``tsat_pd_ensemble_filtered`` — with ModelFilterOptions
     in its place ``tsat_pd_ensemble_model_filtered``, with MagFilterOptions ``tsat_pd_ensemble_mag_filtered``, with
-    MagBiasFilterOptions ``tsat_pd_ensemble_mag_bias_filtered``"""
+    MagBiasFilterOptions ``tsat_pd_ensemble_mag_bias_filtered``, with ModelMagFilterOptions ``tsat_pd_ensemble_model_mag_filtered``"""
     lib = _abi.load()
     T, N = batch.T, batch.N
     c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
@@ -425,7 +425,8 @@ def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, s
         name, rc = "tsat_pd_ensemble", lib.tsat_pd_ensemble(*args)
     elif filtering is not None:
         name = {_abi.ModelFilterOptions: "tsat_pd_ensemble_model_filtered", _abi.MagFilterOptions: "tsat_pd_ensemble_mag_filtered",
-                _abi.MagBiasFilterOptions: "tsat_pd_ensemble_mag_bias_filtered"}.get(type(filtering[0]), "tsat_pd_ensemble_filtered")
+                _abi.MagBiasFilterOptions: "tsat_pd_ensemble_mag_bias_filtered",
+                _abi.ModelMagFilterOptions: "tsat_pd_ensemble_model_mag_filtered"}.get(type(filtering[0]), "tsat_pd_ensemble_filtered")
         rc = getattr(lib, name)(*args, C.byref(sensing[0]), d(sensing[1]), C.byref(filtering[0]), d(filtering[1]), d(filtering[2]))
     else:
         name, rc = "tsat_pd_ensemble_sensed", lib.tsat_pd_ensemble_sensed(*args, C.byref(sensing[0]), d(sensing[1]))
@@ -773,6 +774,64 @@ def attitude_ensemble_pd_mag_bias_filtered(solver, batch: SlewBatch, x0_sim, kd,
     T, M = batch.T, x0.shape[1]
     sensing = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
     fo, Xh, ff = _mag_bias_filtering(T, M, batch.N, filter, want_estimates)
+    out = _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
+                   want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing, filtering=(fo, Xh, ff))
+    return dict(out, X_hat=Xh, filt_final=ff)
+
+
+MODEL_MAG_FILTER_W = 12
+
+
+def model_mag_filter_options(sigma_w, sigma_g, sigma_m, sigma_v=0.0, sigma_u=0.0, p0_att=None, p0_bias=0.0):
+    """The ``tsat_model_mag_filter_options`` of the model-mag-filtered ensembles: ``model_filter_options`` without the attitude
+    sensor's ``sigma_a`` and with the magnetometer noise the filter assumes, ``sigma_m`` (units of the field table, > 0; it has no
+    default, and neither has ``sigma_w``). ``p0_att`` (rad; None: the default options' 1 deg) is the accuracy of the one attitude
+    fix."""
+    fo = _abi.ModelMagFilterOptions()
+    _abi.load().tsat_model_mag_filter_default_options(C.byref(fo))
+    fo.sigma_w, fo.sigma_g, fo.sigma_m, fo.sigma_v, fo.sigma_u = float(sigma_w), float(sigma_g), float(sigma_m), float(sigma_v), float(sigma_u)
+    fo.p0_att, fo.p0_bias = float(fo.p0_att if p0_att is None else p0_att), float(p0_bias)
+    if min(fo.sigma_w, fo.sigma_v, fo.sigma_u, fo.p0_att, fo.p0_bias) < 0.0 or not fo.sigma_g > 0.0 or not fo.sigma_m > 0.0:
+        raise ValueError("filter levels must not be negative, and sigma_g and sigma_m must be positive")
+    if not all(np.isfinite([fo.sigma_w, fo.sigma_v, fo.sigma_u, fo.sigma_g, fo.sigma_m, fo.p0_att, fo.p0_bias])):
+        raise ValueError("filter levels must be finite")
+    return fo
+
+
+def _model_mag_filtering(T, M, N, filter, want_estimates):
+    """(ModelMagFilterOptions, X_hat (T, M, N, 7) or None, filt_final (T, M, 12)) of a model-mag-filtered call"""
+    if not isinstance(filter, _abi.ModelMagFilterOptions):
+        raise ValueError("filter must come from model_mag_filter_options(): sigma_w and sigma_m have no default")
+    return filter, (np.empty((T, M, N, 7)) if want_estimates else None), np.empty((T, M, MODEL_MAG_FILTER_W))
+
+
+def attitude_ensemble_model_mag_filtered(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant=None, Rtab=None, gm=0.0,
+                                         sat=None, sensor=None, sigma_gyro=0.0, sigma_att=0.0, sigma_mag=0.0, latency=0, noise_id0=None,
+                                         sigma_scale=1.0, want_K=False, want_trajectories=False, linearize_dt_sq=True, u_scale=1e-2,
+                                         min_steps=10, w_tol=0.05, angle_tol=0.08727, filter=None, want_estimates=False):
+    """``attitude_ensemble_model_filtered`` with the attitude update replaced by a MAGNETOMETER update
+    (``tsat_tvlqr_ensemble_model_mag_filtered``): the attitude measurement is used once, at knot 0; rate and attitude are propagated
+    on the model under the command just issued, the attitude is corrected by the magnetometer reading b_m against the slew's field
+    table and the gyro is a measurement of w^ + b^; the recursion is in include/tortoise_hip.h. ``filter`` from
+    ``model_mag_filter_options`` (required). Returns the dict of ``attitude_ensemble_model_filtered``."""
+    return _tv_filtered_call("tsat_tvlqr_ensemble_model_mag_filtered", _model_mag_filtering, solver, batch, X, U, x0_sim, Qd, Qfd, Rd,
+                             noise_seed, plant, Rtab, gm, sat, sensor, sigma_gyro, sigma_att, sigma_mag, latency, noise_id0, sigma_scale,
+                             want_K, want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol, filter, want_estimates)
+
+
+def attitude_ensemble_pd_model_mag_filtered(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X=None, U=None, plant=None, Rtab=None,
+                                            gm=0.0, sat=None, limit_mode=0, x0_nom=None, sensor=None, sigma_gyro=0.0, sigma_att=0.0,
+                                            sigma_mag=0.0, latency=0, noise_id0=None, want_trajectories=False, sigma_scale=1.0,
+                                            u_scale=1e-2, min_steps=10, w_tol=0.05, angle_tol=0.08727, filter=None, want_estimates=False):
+    """``attitude_ensemble_pd_sensed`` with the filter of ``attitude_ensemble_model_mag_filtered`` between the measurement and the
+    law (``tsat_pd_ensemble_model_mag_filtered``); the law's field reading is the very magnetometer sample the filter used, taken
+    once per knot. Returns the dict of ``attitude_ensemble_pd_sensed`` plus ``X_hat`` and ``filt_final`` as there."""
+    x0 = np.asarray(x0_sim)
+    if x0.ndim != 3:
+        raise ValueError("x0_sim must be (T, M, 7)")
+    T, M = batch.T, x0.shape[1]
+    sensing = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
+    fo, Xh, ff = _model_mag_filtering(T, M, batch.N, filter, want_estimates)
     out = _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
                    want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing, filtering=(fo, Xh, ff))
     return dict(out, X_hat=Xh, filt_final=ff)
