@@ -1080,6 +1080,41 @@ int  tsat_mpc_run_held_model_filtered(tsat_handle* h, const tsat_options* o, con
                        const tsat_sensor_options* s, const double* sensor, double* Y_hist,
                        const tsat_model_filter_options* f, const double* filt_init, double* filt_state, double* filt_final);
 
+/* tsat_mpc_run_held_model_filtered WITH ITS ATTITUDE UPDATE REPLACED BY THE MAGNETOMETER'S — the filter of
+ * tsat_tvlqr_ensemble_model_mag_filtered in the held re-planning loop: the filter a satellite with a gyro, a magnetometer and one
+ * attitude fix could fly. It is the parent with one change: update(m) becomes the `update` written out at
+ * tsat_model_mag_filter_options — a. the magnetometer block against a row of the slew's field table, then b. the gyro block. The
+ * blocks and the j = 0 rule, the clip, the dispersed RK4 step, the gravity rows, the table clock, the shift, the tally, the statistic
+ * on the TRUE state, the true state written back, the model (Jmat, u_scale, the limited command, the three rows the plant's step
+ * read), `first`, `predict`, the one closing predict, the 58-value record and the 12-value filt_final are the parent's. s counted
+ * FROM THE CALL:
+ *   the magnetometer sample: one reading per control step, b_m,s = qrot(x_s / |x_s|, r_s) + bm + n_m(step0 + s) on the TRUE state
+ *     x_s, n_m the draw the ensembles make for that generator id and knot (a tiled held run sees the ensemble's magnetometer noise at
+ *     the same ids). r_s is the stage-0 row of the table clock at step s: the row the plant's step s reads at c = 0.
+ *   latency 0: s = 0: first(m_0) — THE ONE ATTITUDE FIX: no magnetometer update, and q_m of every later sample is ignored;
+ *              s >= 1: predict(u_{s-1}, rows_{s-1}), then update(w_m,s, b_m,s, r_s); y_s = (w^, q^)
+ *   latency 1: y_0 from first(m_0); s = 1: m_0 arrives a second time and makes no update, then predict(u_0) — the field is still
+ *              sampled, so the one-knot memory holds b_m,1; s >= 2: update(w_m,s-1, b_m,s-1, r_{s-1}), then predict(u_{s-1}): the
+ *              delayed sample is paired with the row it was formed with; for s >= 1, y_s = (w-, q-)
+ *   NO NEW TABLE READ IN THE HOLD: the hold hands the filter the three rows of each step it flies. The row at c = 1 of step s - 1 is
+ *     bit for bit the row at c = 0 of step s (fma(1, dtau, tau0) is the clock's own rounded addition tau0 + dtau), and the row at
+ *     c = 0 of step s - 1 is r_{s-1}: r_s and r_{s-1} are taken from the rows of the step just flown.
+ *   filt_init given: sample 0 makes update(w_m,0, b_m,0, r_0) on the record in place of first, r_0 the stage-0 row of the clock as the
+ *     call finds it. At latency 0 a continuation is the longer run BIT FOR BIT under the parent's conditions (step0 = the steps made,
+ *     no upload, the first call's n_steps a multiple of R). At latency 1 the sensor's memory — now the field's too — restarts with
+ *     every call.
+ * filt_init, filt_state (TSAT_MODEL_FILTER_STATE_W x T) and filt_final (TSAT_MODEL_FILTER_W x T) are the parent's; no new width.
+ * f == NULL is tsat_mpc_run_held_sensed, byte for byte (it is dispatched there); the three filter arrays must then be NULL.
+ * Rejected with -1 (text in tsat_last_error; nothing is launched and no workspace grows): a non-finite or negative filter option,
+ * sigma_g == 0, sigma_m == 0, reserved != 0; f NULL with a filter array non-NULL; a non-finite entry of filt_init; a q^ of zero norm
+ * in filt_init (reported with its t); and everything tsat_mpc_run_held_sensed rejects. */
+int  tsat_mpc_run_held_model_mag_filtered(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps,
+                       int64_t step0, int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo,
+                       const double* sat_hi, const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last,
+                       tsat_tvlqr_stats* stats, int32_t* n_clipped, float* solve_ms, const double* Rtab, double gm,
+                       const tsat_sensor_options* s, const double* sensor, double* Y_hist,
+                       const tsat_model_mag_filter_options* f, const double* filt_init, double* filt_state, double* filt_final);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Sweep exchange across GPUs. The reference's Monte-Carlo is a serial loop whose iterations share nothing but the result
  * lists they append to (src/monte_carlo.jl:52-66, 199-235; src/paper_images/heatmap.jl:114-243). Here each rank — one

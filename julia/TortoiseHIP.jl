@@ -639,7 +639,8 @@ end
 # tracking.attitude_ensemble_pd_mag_bias_filtered). The model-mag-filtered ensembles take the sensor struct and a
 # `tsat_model_mag_filter_options*` (seven Float64 — sigma_v, sigma_w, sigma_u, sigma_g, sigma_m, p0_att, p0_bias —, then Int32
 # reserved: 64 bytes with the tail padding): unbound likewise (tracking.attitude_ensemble_model_mag_filtered,
-# tracking.attitude_ensemble_pd_model_mag_filtered).
+# tracking.attitude_ensemble_pd_model_mag_filtered), and so is the held re-planning loop behind that filter
+# (mpc.receding_horizon_held_model_mag_filtered).
 const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsat_pd_ensemble_sensed, :tsat_mpc_run_held_sensed,
                  :tsat_filter_default_options, :tsat_tvlqr_ensemble_filtered, :tsat_pd_ensemble_filtered,
                  :tsat_mpc_run_held_filtered,
@@ -649,6 +650,6 @@ const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsa
                  :tsat_mag_bias_filter_default_options, :tsat_tvlqr_ensemble_mag_bias_filtered,
                  :tsat_pd_ensemble_mag_bias_filtered,
                  :tsat_model_mag_filter_default_options, :tsat_tvlqr_ensemble_model_mag_filtered,
-                 :tsat_pd_ensemble_model_mag_filtered]
+                 :tsat_pd_ensemble_model_mag_filtered, :tsat_mpc_run_held_model_mag_filtered]
 
 end # module

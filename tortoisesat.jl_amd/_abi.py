@@ -266,6 +266,10 @@ PROTOTYPES = {
                                                    C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_int64), _dp, _dp, C.c_void_p, C.c_void_p, _ip,
                                                    C.POINTER(C.c_float), _dp, C.c_double, C.POINTER(SensorOptions), _dp, _dp,
                                                    C.POINTER(ModelFilterOptions), _dp, _dp, _dp]),
+    "tsat_mpc_run_held_model_mag_filtered": (C.c_int, [C.c_void_p, C.POINTER(Options), C.POINTER(TvlqrOptions), C.c_int32, C.c_int64,
+                                                       C.c_int32, C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_int64), _dp, _dp, C.c_void_p,
+                                                       C.c_void_p, _ip, C.POINTER(C.c_float), _dp, C.c_double, C.POINTER(SensorOptions),
+                                                       _dp, _dp, C.POINTER(ModelMagFilterOptions), _dp, _dp, _dp]),
 }
 
 LIB_NAME = "libtortoise_hip.so"

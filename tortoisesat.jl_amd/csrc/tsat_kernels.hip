@@ -20,6 +20,7 @@
 #include "tsat_mpc_sensed.hpp"
 #include "tsat_mpc_filtered.hpp"
 #include "tsat_mpc_model_filtered.hpp"
+#include "tsat_mpc_model_mag_filtered.hpp"
 
 using namespace tsat;
 
@@ -52,6 +53,9 @@ hipError_t tsat_launch_mpc_filtered(const MpcFilteredArgs<double>& a, int error_
 // tsat_mpc_run_held_model_filtered (tsat_kernels_mpc_model_filtered.hip)
 hipError_t tsat_launch_mpc_model_filtered_pack(const MpcModelFilteredArgs<double>& a, const double* sensor, int given, hipStream_t stream);
 hipError_t tsat_launch_mpc_model_filtered(const MpcModelFilteredArgs<double>& a, int error_state, hipStream_t stream);
+// tsat_mpc_run_held_model_mag_filtered (tsat_kernels_mpc_model_mag_filtered.hip)
+hipError_t tsat_launch_mpc_model_mag_filtered_pack(const MpcModelMagFilteredArgs<double>& a, const double* sensor, int given, hipStream_t stream);
+hipError_t tsat_launch_mpc_model_mag_filtered(const MpcModelMagFilteredArgs<double>& a, int error_state, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -149,7 +153,8 @@ struct tsat_handle {
          WS_MPCS_XT, WS_MPCS_SN, WS_MPCS_IN, WS_MPCS_Y,   // tsat_mpc_run_held_sensed: true state + last measurement [14][T], biases
                                // [9][T], the uploaded sensor array, Y_hist
          WS_MPCF_FL,           // tsat_mpc_run_held_filtered: the filter's records [31][T]
-         WS_MPCMF_FL,          // tsat_mpc_run_held_model_filtered: the nine-state filter's records [58][T]
+         WS_MPCMF_FL,          // tsat_mpc_run_held_model_filtered and _model_mag_filtered: the nine-state filter's records [58][T]
+         WS_MPCMM_HB,          // tsat_mpc_run_held_model_mag_filtered: the last field sample [3][T]
          WS_COUNT };
   void* ws[WS_COUNT] = {};
   size_t ws_bytes[WS_COUNT] = {};
@@ -628,7 +633,9 @@ namespace {
 // `gravity` the hold is the one of tsat_mpc_run_held_gg (Rtab [n_btab][n_tab][3] of the resident batch, gm); with `sc` the hold of
 // tsat_mpc_run_held_sensed, which reads measurements (tsat_mpc_sensed.hpp) — through the gravity rows when `gravity`; with `fc`
 // besides, the hold of tsat_mpc_run_held_filtered, which reads the filter's estimates (tsat_mpc_filtered.hpp); with `mc` besides
-// `sc`, the hold of tsat_mpc_run_held_model_filtered, which reads the nine-state filter's (tsat_mpc_model_filtered.hpp)
+// `sc`, the hold of tsat_mpc_run_held_model_filtered, which reads the nine-state filter's (tsat_mpc_model_filtered.hpp); with `gc`
+// besides `sc`, the hold of tsat_mpc_run_held_model_mag_filtered, which reads that filter's updated by the magnetometer
+// (tsat_mpc_model_mag_filtered.hpp): the parent's record, and the field's one-sample memory beside it
 struct SensedCall {
   const tsat_sensor_options* s;
   const double* sensor;      // 9 x T or null
@@ -646,12 +653,18 @@ struct ModelFilteredCall {
   double* filt_state;        // 58 x T or null
   double* filt_final;        // 12 x T or null
 };
+struct ModelMagFilteredCall {
+  const tsat_model_mag_filter_options* f;
+  const double* filt_init;   // 58 x T or null
+  double* filt_state;        // 58 x T or null
+  double* filt_final;        // 12 x T or null
+};
 int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps,
                    int64_t step0, int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo,
                    const double* sat_hi, const int64_t* noise_id, double* X_hist, double* U_hist, tsat_stats* stats_last,
                    tsat_tvlqr_stats* stats, int32_t* n_clipped, float* solve_ms, bool gravity = false, const double* Rtab = nullptr,
                    double gm = 0.0, const SensedCall* sc = nullptr, const FilteredCall* fc = nullptr,
-                   const ModelFilteredCall* mc = nullptr) {
+                   const ModelFilteredCall* mc = nullptr, const ModelMagFilteredCall* gc = nullptr) {
   if (!h || !o || !po) return -1;
   const bool held = replan_every != 0;
   if (!h->uploaded) return fail(h, -1, "tsat_batch_upload has not been called");
@@ -677,6 +690,14 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
     const std::string badm = check_mpc_model_filtered(mc->f, mc->filt_init, mc->filt_state, mc->filt_final, h->T);
     if (!badm.empty()) return fail(h, -1, badm);
   }
+  if (gc) {
+    const std::string badg = check_mpc_model_mag_filtered(gc->f, gc->filt_init, gc->filt_state, gc->filt_final, h->T);
+    if (!badg.empty()) return fail(h, -1, badg);
+  }
+  // the nine-state record is one: whichever of the two filters the call flies
+  const double* nine_init = mc ? mc->filt_init : (gc ? gc->filt_init : nullptr);
+  double* nine_state = mc ? mc->filt_state : (gc ? gc->filt_state : nullptr);
+  double* nine_final = mc ? mc->filt_final : (gc ? gc->filt_final : nullptr);
   if (!X_hist || !U_hist) return fail(h, -1, "null array");
   TSAT_HIP(h, hipSetDevice(h->dev));
   if (held) {
@@ -710,8 +731,10 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
   }
   double* dFL = fc ? (double*)ws_get(h, tsat_handle::WS_MPCF_FL, T * FLW * 8) : nullptr;
   if (fc && !dFL) return fail(h, -10, std::string("device allocation failed in ") + name);
-  double* dMFL = mc ? (double*)ws_get(h, tsat_handle::WS_MPCMF_FL, T * MFLW * 8) : nullptr;
-  if (mc && !dMFL) return fail(h, -10, std::string("device allocation failed in ") + name);
+  double* dMFL = (mc || gc) ? (double*)ws_get(h, tsat_handle::WS_MPCMF_FL, T * MFLW * 8) : nullptr;
+  if ((mc || gc) && !dMFL) return fail(h, -10, std::string("device allocation failed in ") + name);
+  double* dHB = gc ? (double*)ws_get(h, tsat_handle::WS_MPCMM_HB, T * 3 * 8) : nullptr;
+  if (gc && !dHB) return fail(h, -10, std::string("device allocation failed in ") + name);
   // the gravity call: the packed rows are the handle's, the raw orbit table lives until the pack has run
   double* dGT = gravity ? tsat_ws_gravity(h, n_rows * 4 * 8) : nullptr;
   struct Raw {
@@ -733,9 +756,9 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
     filt_records_pack(fc->filt_init, flh.data(), (int64_t)T);
     TSAT_HIP(h, hipMemcpy(dFL, flh.data(), flh.size() * 8, hipMemcpyHostToDevice));
   }
-  std::vector<double> mflh(mc ? T * MFLW : 0);   // the nine-state filter's records, likewise
-  if (mc && mc->filt_init) {
-    model_filt_records_pack(mc->filt_init, mflh.data(), (int64_t)T);
+  std::vector<double> mflh((mc || gc) ? T * MFLW : 0);   // the nine-state filter's records, likewise
+  if (nine_init) {
+    model_filt_records_pack(nine_init, mflh.data(), (int64_t)T);
     TSAT_HIP(h, hipMemcpy(dMFL, mflh.data(), mflh.size() * 8, hipMemcpyHostToDevice));
   }
   TSAT_HIP(h, hipMemsetAsync(dTally, 0, T * 4 * sizeof(long long), h->stream));
@@ -775,6 +798,14 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
     mm.f.sv = mc->f->sigma_v; mm.f.sw = mc->f->sigma_w; mm.f.su = mc->f->sigma_u; mm.f.sa = mc->f->sigma_a; mm.f.sg = mc->f->sigma_g;
     mm.f.p0a = mc->f->p0_att; mm.f.p0b = mc->f->p0_bias;
   }
+  MpcModelMagFilteredArgs<double> mg9 = {};
+  if (gc) {
+    ModelFiltArgs<double>& g = mg9.f.m;
+    mg9.FL = dMFL; mg9.HB = dHB; mg9.f.sm = gc->f->sigma_m;
+    g.s = ms.s; g.P = h->P; g.M = 1; g.N = h->N; g.n_tab = h->n_tab; g.us = o->u_scale;
+    g.sv = gc->f->sigma_v; g.sw = gc->f->sigma_w; g.su = gc->f->sigma_u; g.sa = 0.0; g.sg = gc->f->sigma_g;
+    g.p0a = gc->f->p0_att; g.p0b = gc->f->p0_bias;
+  }
   int rc = 0;
   if (hipEventRecord(h->ev0, h->stream) != hipSuccess) rc = -10;
   if (held) {   // the pack, then solve, hold and shift per block queued back to back; the stream orders them
@@ -788,6 +819,9 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
       } else if (mc) {
         mm.ms = ms;
         if (!rc && tsat_launch_mpc_model_filtered_pack(mm, dSIn, mc->filt_init != nullptr, h->stream) != hipSuccess) rc = -10;
+      } else if (gc) {
+        mg9.ms = ms;
+        if (!rc && tsat_launch_mpc_model_mag_filtered_pack(mg9, dSIn, gc->filt_init != nullptr, h->stream) != hipSuccess) rc = -10;
       } else {
         if (!rc && tsat_launch_mpc_sensed_pack(ms, dSIn, h->stream) != hipSuccess) rc = -10;
       }
@@ -802,6 +836,9 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
       } else if (mc) { // the hold on the nine-state filter's estimates (with or without the gravity rows)
         ms.h = mh; mm.ms = ms;
         if (!rc && tsat_launch_mpc_model_filtered(mm, o->error_state, h->stream) != hipSuccess) rc = -10;
+      } else if (gc) { // the hold on the magnetometer-updated nine-state filter's estimates (likewise)
+        ms.h = mh; mg9.ms = ms;
+        if (!rc && tsat_launch_mpc_model_mag_filtered(mg9, o->error_state, h->stream) != hipSuccess) rc = -10;
       } else if (sc) {        // the hold on measurements (with or without the gravity rows)
         ms.h = mh;
         if (!rc && tsat_launch_mpc_sensed(ms, o->error_state, h->stream) != hipSuccess) rc = -10;
@@ -829,9 +866,9 @@ int mpc_plant_loop(tsat_handle* h, const char* name, const tsat_options* o, cons
     TSAT_HIP(h, hipMemcpy(flh.data(), dFL, flh.size() * 8, hipMemcpyDeviceToHost));
     filt_records_unpack(flh.data(), (int64_t)T, fc->filt_state, fc->filt_final);
   }
-  if (mc && (mc->filt_state || mc->filt_final)) {
+  if (nine_state || nine_final) {
     TSAT_HIP(h, hipMemcpy(mflh.data(), dMFL, mflh.size() * 8, hipMemcpyDeviceToHost));
-    model_filt_records_unpack(mflh.data(), (int64_t)T, mc->filt_state, mc->filt_final);
+    model_filt_records_unpack(mflh.data(), (int64_t)T, nine_state, nine_final);
   }
   return 0;
 }
@@ -911,6 +948,27 @@ int tsat_mpc_run_held_model_filtered(tsat_handle* h, const tsat_options* o, cons
   const ModelFilteredCall mc = {f, filt_init, filt_state, filt_final};
   return mpc_plant_loop(h, "tsat_mpc_run_held_model_filtered", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi,
                         noise_id, X_hist, U_hist, stats_last, stats, n_clipped, solve_ms, Rtab != nullptr, Rtab, gm, &sc, nullptr, &mc);
+}
+
+int tsat_mpc_run_held_model_mag_filtered(tsat_handle* h, const tsat_options* o, const tsat_tvlqr_options* po, int32_t n_steps,
+                                         int64_t step0, int32_t replan_every, int32_t feedback, const double* plant, const double* sat_lo,
+                                         const double* sat_hi, const int64_t* noise_id, double* X_hist, double* U_hist,
+                                         tsat_stats* stats_last, tsat_tvlqr_stats* stats, int32_t* n_clipped, float* solve_ms,
+                                         const double* Rtab, double gm, const tsat_sensor_options* s, const double* sensor,
+                                         double* Y_hist, const tsat_model_mag_filter_options* f, const double* filt_init,
+                                         double* filt_state, double* filt_final) {
+  if (!f) {   // the sensed call itself
+    const std::string bad = check_mpc_model_mag_filtered(f, filt_init, filt_state, filt_final, 0);
+    if (!bad.empty()) return fail(h, -1, bad);
+    return tsat_mpc_run_held_sensed(h, o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi, noise_id, X_hist, U_hist,
+                                    stats_last, stats, n_clipped, solve_ms, Rtab, gm, s, sensor, Y_hist);
+  }
+  if (replan_every < 1) return fail(h, -1, check_mpc_held(replan_every, feedback, 2));
+  const SensedCall sc = {s, sensor, Y_hist};
+  const ModelMagFilteredCall gc = {f, filt_init, filt_state, filt_final};
+  return mpc_plant_loop(h, "tsat_mpc_run_held_model_mag_filtered", o, po, n_steps, step0, replan_every, feedback, plant, sat_lo, sat_hi,
+                        noise_id, X_hist, U_hist, stats_last, stats, n_clipped, solve_ms, Rtab != nullptr, Rtab, gm, &sc, nullptr, nullptr,
+                        &gc);
 }
 
 int tsat_batch_export_device(tsat_handle* h, void* X_dev, void* U_dev, void* K_dev, void* stats_dev) {

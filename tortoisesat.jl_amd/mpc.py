@@ -52,12 +52,13 @@ def _noise_options(lib, noise_opts):
 
 
 def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
-                gravity=None, sensed=None, filtered=None, model_filtered=None):
+                gravity=None, sensed=None, filtered=None, model_filtered=None, model_mag_filtered=None):
     """``tsat_mpc_run_dispersed`` (``replan_every`` None), ``tsat_mpc_run_held``, — with ``gravity`` = (Rtab, gm) —
     ``tsat_mpc_run_held_gg`` or — with ``sensed`` = (SensorOptions, sensor (T, 9) or None) and ``gravity`` (Rtab may be None) —
     ``tsat_mpc_run_held_sensed`` or — with ``filtered`` = (FilterOptions or None, filt_init (T, 31) or None) besides —
     ``tsat_mpc_run_held_filtered`` or — with ``model_filtered`` = (ModelFilterOptions or None, filt_init (T, 58) or None) instead —
-    ``tsat_mpc_run_held_model_filtered`` on ``prob``: marshalling of all six"""
+    ``tsat_mpc_run_held_model_filtered`` or — with ``model_mag_filtered`` = (ModelMagFilterOptions or None, filt_init (T, 58) or None)
+    instead — ``tsat_mpc_run_held_model_mag_filtered`` on ``prob``: marshalling of all seven"""
     lib = _abi.load()
     b = prob.arrays
     o = solver.opts.to_abi(b.N, b.n_tab, prob.integrator, prob.terminal_mask, error_state=prob.error_state)
@@ -101,15 +102,15 @@ def _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise
         Yh = np.empty((T, n_steps, 7))
         args = (*head, int(replan_every), int(feedback), *tail, d(Rtab), float(gravity[1]), C.byref(so), d(sensor), d(Yh))
         res = dict(X_hist=Xh, U_hist=Uh, stats=st, tracking_stats=ts, n_clipped=ncl, Y_hist=Yh)
-        if model_filtered is not None:
-            fo, init = model_filtered
+        if model_filtered is not None or model_mag_filtered is not None:      # the two nine-state filters: one record, two entry points
+            name = "tsat_mpc_run_held_model_filtered" if model_filtered is not None else "tsat_mpc_run_held_model_mag_filtered"
+            fo, init = model_filtered if model_filtered is not None else model_mag_filtered
             if init is not None:
                 init = c(init)
                 if init.shape != (T, MODEL_FILTER_STATE_W):
                     raise ValueError("filt_init must be (T, 58)")
             fs, ff = (None, None) if fo is None else (np.empty((T, MODEL_FILTER_STATE_W)), np.empty((T, 12)))
-            solver._check(lib.tsat_mpc_run_held_model_filtered(*args, None if fo is None else C.byref(fo), d(init), d(fs), d(ff)),
-                          "tsat_mpc_run_held_model_filtered")
+            solver._check(getattr(lib, name)(*args, None if fo is None else C.byref(fo), d(init), d(fs), d(ff)), name)
             res.update(filt_state=fs, filt_final=ff)
         elif filtered is None:
             solver._check(lib.tsat_mpc_run_held_sensed(*args), "tsat_mpc_run_held_sensed")
@@ -264,6 +265,31 @@ def receding_horizon_held_model_filtered(prob, solver, n_steps, replan_every, fi
     so = _sensor_options(sensor_opts, latency)
     r = _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
                     gravity=(Rtab, gm), sensed=(so, sensor), model_filtered=(filter, filt_init))
+    r["n_solves"] = -(-int(n_steps) // int(replan_every))
+    return r
+
+
+def receding_horizon_held_model_mag_filtered(prob, solver, n_steps, replan_every, filter=None, filt_init=None, sensor_opts=None,
+                                             sensor=None, latency=0, Rtab=None, gm=0.0, feedback=True, plant=None, sat=None,
+                                             noise_opts=None, noise_id=None, step0=0, max_outer=1, max_inner=3, upload=True):
+    """``receding_horizon_held_model_filtered`` WITH THE ATTITUDE UPDATE REPLACED BY THE MAGNETOMETER'S
+    (``tsat_mpc_run_held_model_mag_filtered``): the filter of ``tracking.attitude_ensemble_model_mag_filtered`` in the held loop. The
+    attitude sensor is read once — sample 0 of a call without ``filt_init`` —; after that the nine-state filter is corrected by one
+    magnetometer reading per control step (the true body field of the row the plant's step reads, bias ``sensor[:, 6:9]``, noise
+    ``sigma_mag`` of ``sensor_opts``) against the slew's own field table, and by the gyro. Model, predict, the closing predict, the
+    record and every other argument are the parent's. ``filter``: a ``tracking.model_mag_filter_options`` result, or a dict of that
+    function's arguments; None passes f = NULL, which is ``receding_horizon_held_sensed`` itself (``filt_state`` and ``filt_final``
+    are then None, and ``filt_init`` must be None). ``filt_init`` (T, 58): sample 0 then makes an update — magnetometer and gyro — on
+    the record instead of starting the filter. At latency 0 a continuation equals one longer run bit for bit under the parent's
+    conditions; latency 1 restarts the sensor's memory, the field's included, with every call. Returns the parent's dict."""
+    if isinstance(filter, dict):
+        from .tracking import model_mag_filter_options
+        filter = model_mag_filter_options(**filter)
+    if filter is not None and not isinstance(filter, _abi.ModelMagFilterOptions):
+        raise ValueError("filter must be None, a tracking.model_mag_filter_options() result or a dict of its arguments")
+    so = _sensor_options(sensor_opts, latency)
+    r = _plant_loop(prob, solver, n_steps, replan_every, feedback, plant, sat, noise_opts, noise_id, step0, max_outer, max_inner, upload,
+                    gravity=(Rtab, gm), sensed=(so, sensor), model_mag_filtered=(filter, filt_init))
     r["n_solves"] = -(-int(n_steps) // int(replan_every))
     return r
 
