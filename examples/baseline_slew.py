@@ -35,15 +35,15 @@ GRID_WN, GRID_ZETA = np.geomspace(1e-3, 3e-2, 16), np.linspace(0.3, 3.0, 16)
 GM = tracking.GM_EARTH
 
 
-def orbit_batch(solver, b, T):
-    """the slew of `b` T times over one orbit: N_ORBIT knots on the orbit's own table (2 N_ORBIT rows, two per knot, the last one
+def orbit_batch(solver, b, T, n=N_ORBIT):
+    """the slew of `b` T times over n knots (default one orbit, N_ORBIT) on the orbit's own table (2 n rows, two per knot, the last one
     zero — the law commands no dipole there), field and position; no plan"""
     kep = np.array([[0.0, 400.0 + 6371.0, 51.6, 0.0, 0.0, 90.0]])
-    B, pos = magnetic.magnetic_simulation(solver, kep, 0.0, N_ORBIT * float(b.dt[0]), N_ORBIT)
+    B, pos = magnetic.magnetic_simulation(solver, kep, 0.0, n * float(b.dt[0]), n)
     rows = B.shape[1]
     rep = lambda a: np.ascontiguousarray(np.repeat(a[:1], T, axis=0))
-    ob = dataclasses.replace(b, N=N_ORBIT, n_tab=rows, Btab=np.ascontiguousarray(B), btab_idx=np.zeros(T, dtype=np.int32),
-                             tau0=np.zeros(T), dtau=np.full(T, rows / float(N_ORBIT)), U0=np.zeros((T, 1, 3)), n_knots=None,
+    ob = dataclasses.replace(b, N=n, n_tab=rows, Btab=np.ascontiguousarray(B), btab_idx=np.zeros(T, dtype=np.int32),
+                             tau0=np.zeros(T), dtau=np.full(T, rows / float(n)), U0=np.zeros((T, 1, 3)), n_knots=None,
                              **{k: rep(getattr(b, k)) for k in ("x0", "xf", "dt", "Jmat", "Qd", "Qfd", "Rd", "ulo", "uhi")})
     return ob, magnetic.orbit_rows(pos, rows)
 

@@ -452,6 +452,71 @@ int  tsat_pd_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, in
                          tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
                          double* X_sim, int32_t* n_clipped, const double* Rtab, double gm);
 
+/* The ASYMPTOTIC PERIODIC LQR on the plants of tsat_pd_ensemble: the model-based constant-P regulator that the reference's
+ * comparison figure plots against the tracked plans ("APLQR", src/comparison/psiaki2001_Period_LQR.jl). Two calls: the gain
+ * synthesis on the device (tsat_aplqr_gains) and the roll-out (tsat_aplqr_ensemble), which flies whatever gain it is handed.
+ * Restated from magnetic_control_effectiveness (src/comparison/psiaki_dynamics.jl:75-98), Pss_psiaki (:101-125) and
+ * nominal_input_psiaki (:127-143); this is the law as defined HERE. Deviations:
+ *   frame             the reference's goal is fixed in the local-level frame and its A carries orbit-rate and gravity-gradient
+ *                     terms; every goal of this ABI is inertial (xf), so A is the double integrator [[0, I], [0, 0]] and the field
+ *                     is averaged in the goal's body frame
+ *   no square root    the reference forms B~ = sqrt(alpha) and hands it to care; only B~ B~' = Gamma enters the equation
+ *   attitude error    quaternion_euler(q) there; here the rotation vector to first order, 2 s e[1:4], with the PD law's sign s
+ *   general inertia   inv(J) is the full inverse of Jmat, not 1 / J_ii row scalings
+ *   limits            the reference scales the command back against U_max; here limit_mode 0 or 1 is tsat_pd_ensemble's
+ * SYNTHESIS, per slew t (one wavefront each; state z = [theta (3); dw (3)]):
+ *   beta_j = qrot(xf[3:7,t] / |xf[3:7,t]|, row j of the slew's table)
+ *   B_j    = -inv(J) hat(beta_j)                                           3 x 3
+ *   Gamma  = (1/n) sum_{j = avg_lo .. avg_hi-1} B_j diag(1/rd) B_j'        n = avg_hi - avg_lo
+ *   G = blockdiag(0, Gamma),  Q = diag(qd)
+ *   P      : A'P + P A - P G P + Q = 0,  P symmetric, A - G P stable
+ *   Kg     = alpha inv(J) P[3:6, 0:6]                                      3 x 6
+ * P by the matrix sign function of the Hamiltonian [[A, -G], [-Q, -A']]: Z <- (c Z + inv(Z) / c) / 2, c = |det Z|^(-1/12), the
+ * inverse by Gauss-Jordan with partial pivoting, until |dZ|_1 <= 1e-14 |Z|_1 or 32 iterations; then [W12; W22 + I] P =
+ * -[W11 + I; W21] in the least-squares sense by a Gram-Schmidt QR (the normal equations would square its condition), symmetrised.
+ *   avg_lo, avg_hi  int32 x T, or both NULL for the whole table [0, n_tab)
+ *   qd 6 x T, rd 3 x T   finite and > 0          alpha T   finite and >= 0          res_tol > 0
+ *   Kg 3 x 6 x T         P_ss 6 x 6 x T or NULL          Gamma 3 x 3 x T or NULL
+ *   info   T records of tsat_aplqr_info: status 0 ok; 1 not converged in 32 iterations; 2 a zero or non-finite pivot;
+ *          3 residual > res_tol, with residual = |A'P + P A - P G P + Q|_F / (2 |A|_F |P|_F + |G|_F |P|_F^2 + |Q|_F). pivot_min is
+ *          the smallest |pivot| of all eliminations of the slew and of the diagonal of the QR's triangular factor. On any status other than 0 the slew's Kg and P_ss are zero-filled,
+ *          never non-finite, and the call still returns 0.
+ * Rejected with -1 (text in tsat_ensemble_last_error; nothing is launched and no workspace grows): a null handle or array; exactly
+ * one of avg_lo / avg_hi NULL; a window without 0 <= avg_lo < avg_hi <= n_tab; btab_idx out of range, or NULL with n_btab != T;
+ * qd or rd non-finite or <= 0; alpha non-finite or negative; res_tol not > 0; a non-finite or singular Jmat; a zero or non-finite
+ * goal quaternion. */
+struct tsat_aplqr_info {
+  int32_t status;
+  int32_t iterations;       /* of the sign iteration, the one a failed elimination stopped included */
+  double  residual;         /* 0 unless the iteration converged and the QR that P is solved from went through */
+  double  pivot_min;
+};
+typedef struct tsat_aplqr_info tsat_aplqr_info;
+int  tsat_aplqr_gains(tsat_handle* h, int64_t T, int64_t n_btab, int32_t n_tab, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const int32_t* avg_lo, const int32_t* avg_hi,
+                         const double* Jmat, const double* qd, const double* rd, const double* alpha, double res_tol,
+                         double* Kg, double* P_ss, double* Gamma, void* info);
+
+/* ROLL-OUT: tsat_pd_ensemble with the command of knot k replaced. y and B are what the law sees of the realisation's state and of
+ * the stage-0 field row, exactly as the PD law takes them; xr the record X[:,k,t], or xf[:,t] when regulating:
+ *   dw    = y[0:3] - xr[0:3];   e = conj(xr[3:7]) (x) y[3:7];   s = (e0 < 0) ? -1 : 1;   theta = 2 s e[1:4]
+ *   v     = Kg [theta; dw]
+ *   m[c]  = -(1 / rd[c]) (B x v)[c]                 A m^2; a zero field row gives m = 0 by itself
+ *   u_cmd = (feedforward ? U_k : 0) + m / o->u_scale
+ * Everything after u_cmd, and every argument not named here, is tsat_pd_ensemble's, unchanged in meaning, shape and validation.
+ *   Kg 3 x 6 x T   from tsat_aplqr_gains or the caller's own, finite          rd 3 x T   finite and > 0
+ * Rejected with -1: everything tsat_pd_ensemble rejects (its kd / kp rules apart); Kg or rd NULL; Kg non-finite; rd non-finite
+ * or <= 0. */
+int  tsat_aplqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat,
+                         const double* Kg, const double* rd, int32_t feedforward, int32_t limit_mode,
+                         const double* x0_sim, const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* X_sim, int32_t* n_clipped, const double* Rtab, double gm);
+
 /* The ensemble controllers fed MEASUREMENTS: every closed loop above commands from the realisation's TRUE state — a perfect
  * attitude solution, a perfect gyro, a perfect magnetometer. The two calls below are tsat_tvlqr_ensemble_gg and tsat_pd_ensemble
  * with the feedback reading a biased, noisy, optionally one-knot-old measurement instead. The reference's noise figures ARE

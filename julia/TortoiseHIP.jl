@@ -443,6 +443,73 @@ function attitude_ensemble_pd(s::HIPSolver, p::BatchProblem, x0_lqr::Array{Float
     return st, summary, nominal, Xs, n_clipped
 end
 
+"tsat_aplqr_info: one record per slew of `aplqr_gains`"
+struct AplqrInfo
+    status::Int32
+    iterations::Int32
+    residual::Float64
+    pivot_min::Float64
+end
+
+"""
+aplqr_gains(s, p, qd, rd, alpha; avg_lo, avg_hi, res_tol) — `tsat_aplqr_gains`: the gains of the asymptotic periodic LQR (the
+reference's src/comparison/psiaki_dynamics.jl:75-125, as include/tortoise_hip.h defines it), one wavefront per slew: the
+control-effectiveness Gramian averaged over the rows avg_lo[t] .. avg_hi[t]-1 (0-based; empty: the whole table) of the slew's
+table in the goal's body frame, the 6 x 6 Riccati equation on the double integrator, Kg = alpha inv(J) P[4:6, :].
+qd 6 x T, rd 3 x T, alpha T. Returns (Kg 3 x 6 x T, P 6 x 6 x T, Gamma 3 x 3 x T, info T); a slew whose info.status is not 0
+has Kg = P = 0.
+"""
+function aplqr_gains(s::HIPSolver, p::BatchProblem, qd::Matrix{Float64}, rd::Matrix{Float64}, alpha::Vector{Float64};
+                     avg_lo::Vector{Int32} = Int32[], avg_hi::Vector{Int32} = Int32[], res_tol::Float64 = 3.3e-12)
+    T = size(p.x0, 2)
+    size(qd) == (6, T) && size(rd) == (3, T) && length(alpha) == T || error("qd 6 x T, rd 3 x T, alpha T")
+    Kg = zeros(3, 6, T); P = zeros(6, 6, T); Gamma = zeros(3, 3, T); info = Vector{AplqrInfo}(undef, T)
+    rc = ccall((:tsat_aplqr_gains, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{AplqrInfo}),
+        s.handle, T, size(p.B_ECI, 3), size(p.B_ECI, 2), p.xf, p.B_ECI, p.btab_idx, isempty(avg_lo) ? C_NULL : avg_lo,
+        isempty(avg_hi) ? C_NULL : avg_hi, p.J, qd, rd, alpha, res_tol, Kg, P, Gamma, info)
+    rc == 0 || error("tsat_aplqr_gains failed ($rc): " * unsafe_string(ccall((:tsat_ensemble_last_error, LIB), Cstring, ())))
+    return Kg, P, Gamma, info
+end
+
+"""
+attitude_ensemble_aplqr(s, p, x0_lqr, Kg, rd; X, U, plant, Rtab, gm, sat_lo, sat_hi, limit_mode, x0_nom, noise_id0, opts,
+want_trajectories) — `tsat_aplqr_ensemble`: `attitude_ensemble_pd` with the law m = -diag(1/rd) (b x Kg [theta; dw]), theta the
+rotation-vector error. Kg 3 x 6 x T (from `aplqr_gains` or the caller's own), rd 3 x T; every other argument and the returned
+tuple are those of `attitude_ensemble_pd`.
+"""
+function attitude_ensemble_aplqr(s::HIPSolver, p::BatchProblem, x0_lqr::Array{Float64,3}, Kg::Array{Float64,3}, rd::Matrix{Float64};
+                                 X::Array{Float64,3} = zeros(7, 0, 0), U::Array{Float64,3} = zeros(3, 0, 0),
+                                 plant::Array{Float64,3} = zeros(21, 0, 0), Rtab::Array{Float64,3} = zeros(3, 0, 0), gm::Float64 = 0.0,
+                                 sat_lo::Matrix{Float64} = zeros(3, 0), sat_hi::Matrix{Float64} = zeros(3, 0), limit_mode::Integer = 0,
+                                 x0_nom::Matrix{Float64} = zeros(7, 0), noise_id0::Vector{Int64} = Int64[],
+                                 opts::TvlqrOptions = TvlqrOptions(noise_mode = 1), want_trajectories::Bool = false)
+    T = size(p.x0, 2); N = p.N; M = size(x0_lqr, 2)
+    size(Kg) == (3, 6, T) && size(rd) == (3, T) || error("Kg must be 3 x 6 x T and rd 3 x T")
+    isempty(X) || size(X) == (7, N, T) || error("X must be 7 x N x T")
+    isempty(U) || size(U) == (3, N - 1, T) || error("U must be 3 x (N-1) x T")
+    isempty(plant) || size(plant) == (21, M, T) || error("plant must be 21 x M x T")
+    isempty(Rtab) || size(Rtab) == size(p.B_ECI) || error("Rtab must have the shape of B_ECI: 3 x n_tab x n_btab")
+    opts.n_knots = N; opts.n_tab = size(p.B_ECI, 2)
+    st = Matrix{TvlqrStats}(undef, M, T); nominal = Vector{TvlqrStats}(undef, T); summary = zeros(8, T)
+    n_clipped = zeros(Int32, M, T)
+    Xs = want_trajectories ? zeros(7, N, M, T) : nothing
+    rc = ccall((:tsat_aplqr_ensemble, LIB), Cint,
+        (Ptr{Cvoid}, Ref{TvlqrOptions}, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64},
+         Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{TvlqrStats}, Ptr{Float64}, Ptr{TvlqrStats},
+         Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Float64),
+        s.handle, opts, T, size(p.B_ECI, 3), M, isempty(X) ? C_NULL : X, isempty(U) ? C_NULL : U, p.xf, p.B_ECI, p.btab_idx,
+        p.tau0, p.dtau, p.dt, p.J, Kg, rd, isempty(U) ? 0 : 1, limit_mode, x0_lqr, isempty(x0_nom) ? C_NULL : x0_nom,
+        isempty(noise_id0) ? C_NULL : noise_id0, isempty(p.n_knots) ? C_NULL : p.n_knots,
+        isempty(plant) ? C_NULL : plant, isempty(sat_lo) ? C_NULL : sat_lo, isempty(sat_hi) ? C_NULL : sat_hi,
+        st, summary, isempty(X) && isempty(x0_nom) ? C_NULL : nominal, Xs === nothing ? C_NULL : Xs, n_clipped,
+        isempty(Rtab) ? C_NULL : Rtab, gm)
+    rc == 0 || error("tsat_aplqr_ensemble failed ($rc): " * unsafe_string(ccall((:tsat_ensemble_last_error, LIB), Cstring, ())))
+    return st, summary, nominal, Xs, n_clipped
+end
+
 """
 receding_horizon!(s, p, n_steps; plant_integrator = 4) — `tsat_mpc_run` on the batch `p` (uploaded here): re-solve the
 horizon every control step with the budget of `s.opts`, apply U[:,1] to the noise-free plant, shift the plan.

@@ -137,6 +137,10 @@ TVLQR_STATS_DTYPE = np.dtype([("slew_index", "<i4"), ("failed", "<i4"), ("slew_t
                               ("final_angle", "<f8")])
 assert TVLQR_STATS_DTYPE.itemsize == 32
 
+#: tsat_aplqr_info, one record per slew of tsat_aplqr_gains
+APLQR_INFO_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("residual", "<f8"), ("pivot_min", "<f8")])
+assert APLQR_INFO_DTYPE.itemsize == 24
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 
@@ -203,6 +207,11 @@ PROTOTYPES = {
     "tsat_pd_ensemble": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp, _ip,
                                    _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp,
                                    C.c_void_p, _dp, C.c_void_p, _dp, _ip, _dp, C.c_double]),
+    "tsat_aplqr_gains": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, C.c_double,
+                                   _dp, _dp, _dp, C.c_void_p]),
+    "tsat_aplqr_ensemble": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp, _ip,
+                                      _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp,
+                                      C.c_void_p, _dp, C.c_void_p, _dp, _ip, _dp, C.c_double]),
     "tsat_sensor_default_options": (None, [C.POINTER(SensorOptions)]),
     "tsat_tvlqr_ensemble_sensed": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp,
                                              _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp,

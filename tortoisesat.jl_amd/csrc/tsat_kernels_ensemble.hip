@@ -1,6 +1,7 @@
-// tsat_kernels_ensemble.hip — the host side of the eighteen ensemble entry points (include/tortoise_hip.h): tsat_tvlqr_ensemble and its
+// tsat_kernels_ensemble.hip — the host side of the twenty ensemble entry points (include/tortoise_hip.h): tsat_tvlqr_ensemble and its
 // _dispersed, _gg, _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered, _model_mag_filtered, and tsat_pd_ensemble
-// with its _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered, _model_mag_filtered. A
+// with its _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered, _model_mag_filtered, and tsat_aplqr_ensemble (a PD
+// call with another law) with its synthesis tsat_aplqr_gains (run_aplqr_gains: no roll-out, a call of its own). A
 // translation unit of its own, built on the public ABI: `struct tsat_handle` is private to tsat_kernels.hip, so a call keeps its own
 // buffers and stream. An entry point only describes its call (`Call`: the common arrays, the part of its law, and what it adds —
 // Dispersion, Gravity, Sensing, Filtering); run_call goes through the stages once, all of it synchronous:
@@ -34,6 +35,7 @@
 #include "tsat_mag_bias_filtered.hpp"
 #include "tsat_model_mag_filtered.hpp"
 #include "tsat_ensemble_launch.hpp"
+#include "tsat_aplqr.hpp"
 
 using namespace tsat;
 
@@ -179,11 +181,13 @@ struct TvlqrPart {
   double* K_lqr;
 };
 
-// ... and only the PD ones
+// ... and only the PD ones; with Kg the law is the asymptotic periodic LQR of tsat_aplqr_ensemble (Kg, rd) and kd, kp are null
 struct PdPart {
   const double *kd, *kp;
   int32_t feedforward, limit_mode;
   const double* x0_nom;
+  const double *Kg = nullptr, *rd = nullptr;
+  bool aplqr = false;
 };
 
 // One call of any entry point: the arrays every one of them takes, the part of its law (exactly one of `tv` / `pd`), and what the
@@ -248,6 +252,10 @@ std::string check_tvlqr(const Call& c) {
 // ... and of a PD call: check_pd is the authority
 std::string check_pd_call(const Call& c) {
   if (!c.h) return "null handle or options";
+  if (c.pd->aplqr)
+    return check_aplqr(c.o, c.T, c.n_btab, c.M, c.X, c.U, c.xf, c.Btab, c.btab_idx, c.tau0, c.dtau, c.dt, c.Jmat, c.pd->Kg, c.pd->rd,
+                       c.pd->feedforward, c.pd->limit_mode, c.x0_sim, c.pd->x0_nom, c.n_knots, c.disp->plant, c.disp->sat_lo,
+                       c.disp->sat_hi, c.stats, c.summary, c.stats_nominal, c.grav->Rtab, c.grav->gm);
   return check_pd(c.o, c.T, c.n_btab, c.M, c.X, c.U, c.xf, c.Btab, c.btab_idx, c.tau0, c.dtau, c.dt, c.Jmat, c.pd->kd, c.pd->kp,
                   c.pd->feedforward, c.pd->limit_mode, c.x0_sim, c.pd->x0_nom, c.n_knots, c.disp->plant, c.disp->sat_lo, c.disp->sat_hi,
                   c.stats, c.summary, c.stats_nominal, c.grav->Rtab, c.grav->gm);
@@ -275,7 +283,8 @@ hipError_t launch_tvlqr(const EnsArgs<double>& a, const DispArgs<double>* d, con
 }
 
 hipError_t launch_pd(const PdArgs<double>& pa, const SensArgs<double>* sa, const Filtering* fl, double* dXH, double* dFF, int nw,
-                     hipStream_t st) {
+                     hipStream_t st, bool aplqr) {
+  if (aplqr) return tsat_launch_aplqr(pa, nw, st);             // GAIN holds [T][AQGW]; no sensed or filtered variant
   if (fl && fl->mg) return tsat_launch_model_mag_filtered_pd({pa, model_mag_filt_args(*fl->mg, *sa, pa.d.e, dXH, dFF)}, nw, st);
   if (fl && fl->bf) return tsat_launch_mag_bias_filtered_pd({pa, mag_bias_filt_args(*fl->bf, *sa, pa.d.e, dXH, dFF)}, nw, st);
   if (fl && fl->gf) return tsat_launch_mag_filtered_pd({pa, mag_filt_args(*fl->gf, *sa, pa.d.e, dXH, dFF)}, nw, st);
@@ -328,15 +337,17 @@ int run_call(const Call& c) {
   const int nw = ensemble_waves(M), Mp = nw * WAVE;
   const size_t nX = Tn * N * 7, nU = Tn * (size_t)(N - 1) * 3, nB = (size_t)c.n_btab * n_tab, nXU = Tn * N * XUW,
                nKD = Tn * (size_t)(N - 1) * KDW, nS = Tn * (size_t)M, nXS = c.X_sim ? nS * N * 7 : 0;
-  std::vector<double> P(Tn * PSTRIDE), x0n(Tn * 7), zero(c.pd ? Tn * 6 : 0, 0.0), gain(c.pd ? Tn * PDGW : 0), model;
+  const bool aplqr = c.pd && c.pd->aplqr;
+  std::vector<double> P(Tn * PSTRIDE), x0n(Tn * 7), zero(c.pd ? Tn * 6 : 0, 0.0), gain((c.pd && !aplqr) ? Tn * PDGW : 0), model;
   for (size_t t = 0; t < Tn; ++t) {
     for (int i = 0; i < 7; ++i)
       x0n[7 * t + i] = (c.pd && c.pd->x0_nom) ? c.pd->x0_nom[7 * t + i] : (c.X ? c.X[t * N * 7 + i] : c.xf[7 * t + i]);
-    for (int k = 0; c.pd && k < 3; ++k) {
+    for (int k = 0; c.pd && !aplqr && k < 3; ++k) {
       gain[PDGW * t + k] = c.pd->kd[3 * t + k];
       gain[PDGW * t + 3 + k] = c.pd->kp[3 * t + k];
     }
   }
+  if (aplqr) gain = pack_aplqr_law(T, c.pd->Kg, c.pd->rd);
   if (c.tv) pack_tv_params<double>(T, x0n.data(), c.xf, c.tau0, c.dtau, c.dt, c.Jmat, c.tv->Qd, c.tv->Qfd, c.tv->Rd, P.data());
   else pack_tv_params<double>(T, x0n.data(), c.xf, c.tau0, c.dtau, c.dt, c.Jmat, zero.data(), zero.data(), zero.data(), P.data());
   const int cls = inertia_class(T, c.Jmat);
@@ -377,7 +388,7 @@ int run_call(const Call& c) {
   double *dXH = nullptr, *dFF = nullptr;
   if (ok && filt && filt->X_hat) ok = s.alloc(&dXH, nS * N * 7);
   if (ok && filt && filt->filt_final) ok = s.alloc(&dFF, nS * filt->final_w());
-  if (!ok) return efail(-10, std::string("device allocation failed in ") + (c.pd ? "tsat_pd_ensemble" : c.name));
+  if (!ok) return efail(-10, std::string("device allocation failed in ") + ((c.pd && !aplqr) ? "tsat_pd_ensemble" : c.name));
   ENS_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
   for (hipEvent_t& e : s.ev) ENS_HIP(hipEventCreate(&e));
   ENS_HIP(hipMemcpy(dP, P.data(), P.size() * 8, hipMemcpyHostToDevice));
@@ -439,7 +450,8 @@ int run_call(const Call& c) {
     SensArgs<double> sa;
     if (sens) sa = sens_args(*sens->s, *o, dSN, Mp);
     if (c.tv) ENS_HIP(launch_tvlqr(a, disp ? &d : nullptr, dGT, sens ? &sa : nullptr, filt, dXH, dFF, cls, nw, s.stream));
-    else ENS_HIP(launch_pd({d, dGT, dGain, dX0N, c.pd->feedforward, c.pd->limit_mode}, sens ? &sa : nullptr, filt, dXH, dFF, nw, s.stream));
+    else ENS_HIP(launch_pd({d, dGT, dGain, dX0N, c.pd->feedforward, c.pd->limit_mode}, sens ? &sa : nullptr, filt, dXH, dFF, nw, s.stream,
+                         aplqr));
   }
   ENS_HIP(hipEventRecord(s.ev[c.tv ? 2 : 1], s.stream));
   if (K_lqr) {
@@ -477,6 +489,45 @@ int run_call(const Call& c) {
   }
   return 0;
 }
+
+// tsat_aplqr_gains: checks, the handle's GPU, the parameter records and the tables up, one wavefront per slew, the results down
+int run_aplqr_gains(tsat_handle* h, int64_t T, int64_t n_btab, int32_t n_tab, const double* xf, const double* Btab, const int32_t* btab_idx,
+                    const int32_t* avg_lo, const int32_t* avg_hi, const double* Jmat, const double* qd, const double* rd,
+                    const double* alpha, double res_tol, double* Kg, double* P_ss, double* Gamma, void* info) {
+  g_err.clear();
+  if (!h) return efail(-1, "null handle");
+  const std::string bad = check_aplqr_gains(T, n_btab, n_tab, xf, Btab, btab_idx, avg_lo, avg_hi, Jmat, qd, rd, alpha, res_tol, Kg, info);
+  if (!bad.empty()) return efail(-1, bad);
+  ENS_HIP(hipSetDevice(tsat_handle_device(h)));
+  const std::vector<double> gp = pack_aplqr_gains(T, n_tab, xf, btab_idx, avg_lo, avg_hi, Jmat, qd, rd, alpha);
+  const size_t Tn = (size_t)T, nB = (size_t)n_btab * n_tab * 3;
+  EnsScope s;
+  double *dGP = nullptr, *dB = nullptr, *dKg = nullptr, *dP = nullptr, *dGam = nullptr;
+  tsat_aplqr_info* dInfo = nullptr;
+  if (!(s.alloc(&dGP, gp.size()) && s.alloc(&dB, nB) && s.alloc(&dKg, Tn * 18) && s.alloc(&dP, Tn * 36) && s.alloc(&dGam, Tn * 9) &&
+        s.alloc(&dInfo, Tn)))
+    return efail(-10, "device allocation failed in tsat_aplqr_gains");
+  ENS_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) ENS_HIP(hipEventCreate(&s.ev[i]));
+  ENS_HIP(hipMemcpy(dGP, gp.data(), gp.size() * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipMemcpy(dB, Btab, nB * 8, hipMemcpyHostToDevice));
+  ENS_HIP(hipEventRecord(s.ev[0], s.stream));
+  ENS_HIP(tsat_launch_aplqr_gains({dGP, dB, n_tab, res_tol, dKg, dP, dGam, dInfo}, T, s.stream));
+  ENS_HIP(hipEventRecord(s.ev[1], s.stream));
+  ENS_HIP(hipStreamSynchronize(s.stream));
+  ENS_HIP(hipMemcpy(Kg, dKg, Tn * 18 * 8, hipMemcpyDeviceToHost));
+  if (P_ss) ENS_HIP(hipMemcpy(P_ss, dP, Tn * 36 * 8, hipMemcpyDeviceToHost));
+  if (Gamma) ENS_HIP(hipMemcpy(Gamma, dGam, Tn * 9 * 8, hipMemcpyDeviceToHost));
+  ENS_HIP(hipMemcpy(info, dInfo, Tn * sizeof(tsat_aplqr_info), hipMemcpyDeviceToHost));
+  if (const char* v = std::getenv("TSAT_ENSEMBLE_TIMING")) {   // diagnostic (tools/aplqr_timing.py)
+    if (v[0] == '1') {
+      float e = 0;
+      (void)hipEventElapsedTime(&e, s.ev[0], s.ev[1]);
+      std::fprintf(stderr, "tsat_aplqr_gains: gains_kernel_ms %.4f\n", e);
+    }
+  }
+  return 0;
+}
 #undef ENS_HIP
 
 }  // namespace
@@ -496,6 +547,27 @@ int tsat_pd_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int
          summary, stats_nominal, X_sim};
   c.pd = &law; c.disp = &d; c.grav = &g;
   return run_call(c);
+}
+
+int tsat_aplqr_ensemble(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,
+                        const double* U, const double* xf, const double* Btab, const int32_t* btab_idx, const double* tau0,
+                        const double* dtau, const double* dt, const double* Jmat, const double* Kg, const double* rd, int32_t feedforward,
+                        int32_t limit_mode, const double* x0_sim, const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots,
+                        const double* plant, const double* sat_lo, const double* sat_hi, tsat_tvlqr_stats* stats, double* summary,
+                        tsat_tvlqr_stats* stats_nominal, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm) {
+  const PdPart law{nullptr, nullptr, feedforward, limit_mode, x0_nom, Kg, rd, true};
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  Call c{"tsat_aplqr_ensemble", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, x0_sim, noise_id0, n_knots, stats,
+         summary, stats_nominal, X_sim};
+  c.pd = &law; c.disp = &d; c.grav = &g;
+  return run_call(c);
+}
+
+int tsat_aplqr_gains(tsat_handle* h, int64_t T, int64_t n_btab, int32_t n_tab, const double* xf, const double* Btab,
+                     const int32_t* btab_idx, const int32_t* avg_lo, const int32_t* avg_hi, const double* Jmat, const double* qd,
+                     const double* rd, const double* alpha, double res_tol, double* Kg, double* P_ss, double* Gamma, void* info) {
+  return run_aplqr_gains(h, T, n_btab, n_tab, xf, Btab, btab_idx, avg_lo, avg_hi, Jmat, qd, rd, alpha, res_tol, Kg, P_ss, Gamma, info);
 }
 
 int tsat_pd_ensemble_sensed(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M, const double* X,

@@ -372,8 +372,8 @@ def attitude_ensemble_pd(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X
 
 
 def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0, want_trajectories,
-             sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=None, filtering=None):
-    """``tsat_pd_ensemble``, or with ``sensing`` = (SensorOptions, sensor array or None) ``tsat_pd_ensemble_sensed``, or with
+             sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=None, filtering=None, aplqr=False):
+    """``tsat_pd_ensemble`` — with ``aplqr`` ``tsat_aplqr_ensemble``, ``kd`` being Kg (T, 6, 3) and ``kp`` rd —, or with ``sensing`` = (SensorOptions, sensor array or None) ``tsat_pd_ensemble_sensed``, or with
     ``filtering`` = (FilterOptions, X_hat or None, filt_final or None) besides ``tsat_pd_ensemble_filtered`` — with ModelFilterOptions
     in its place ``tsat_pd_ensemble_model_filtered``, with MagFilterOptions ``tsat_pd_ensemble_mag_filtered``, with
     MagBiasFilterOptions ``tsat_pd_ensemble_mag_bias_filtered``, with ModelMagFilterOptions ``tsat_pd_ensemble_model_mag_filtered``"""
@@ -384,7 +384,14 @@ def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, s
     if x0_sim.ndim != 3 or x0_sim.shape[0] != T or x0_sim.shape[2] != 7:
         raise ValueError("x0_sim must be (T, M, 7)")
     M = x0_sim.shape[1]
-    kd, kp = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in (kd, kp))
+    if aplqr:
+        if kd is None or kp is None:
+            raise ValueError("Kg and rd must be given")
+        kd, kp = c(kd), c(np.broadcast_to(np.asarray(kp, dtype=np.float64), (T, 3)))
+        if kd.shape != (T, 6, 3):
+            raise ValueError("Kg must be (T, 6, 3)")
+    else:
+        kd, kp = (c(np.broadcast_to(np.asarray(v, dtype=np.float64), (T, 3))) for v in (kd, kp))
     X, U, plant, x0_nom = c(X), c(U), c(plant), c(x0_nom)
     if U is not None and X is None:
         raise ValueError("the feed-forward U needs the trajectory X it belongs to")
@@ -421,7 +428,9 @@ def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, s
             None if id0 is None else id0.ctypes.data_as(C.POINTER(C.c_int64)), _abi.as_ip(nk), d(plant), d(lo), d(hi),
             st.ctypes.data_as(C.c_void_p), d(summary), None if nom is None else nom.ctypes.data_as(C.c_void_p), d(Xs),
             _abi.as_ip(ncl), d(Rtab), float(gm))
-    if sensing is None:
+    if aplqr:
+        name, rc = "tsat_aplqr_ensemble", lib.tsat_aplqr_ensemble(*args)
+    elif sensing is None:
         name, rc = "tsat_pd_ensemble", lib.tsat_pd_ensemble(*args)
     elif filtering is not None:
         name = {_abi.ModelFilterOptions: "tsat_pd_ensemble_model_filtered", _abi.MagFilterOptions: "tsat_pd_ensemble_mag_filtered",
@@ -433,6 +442,54 @@ def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, s
     if rc != 0:
         raise RuntimeError(f"{name} failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
     return dict(stats=st, summary=summary, nominal=nom, X_sim=Xs, n_clipped=ncl)
+
+
+#: default ``res_tol`` of ``aplqr_gains``: 100 x the largest relative residual a numpy-double restatement of the sign iteration
+#: leaves on the cases of tests/test_aplqr.py, 3.26e-14 (profiles/aplqr/care_e_ref.txt)
+APLQR_RES_TOL = 3.3e-12
+
+
+def aplqr_gains(solver, batch: SlewBatch, qd, rd, alpha=1.0, rows=None, res_tol=APLQR_RES_TOL, allow_failed=False):
+    """Gains of the asymptotic periodic LQR (``tsat_aplqr_gains``), one wavefront per slew on the device: the control-effectiveness
+    Gramian Gamma = mean_j B_j diag(1/rd) B_j', B_j = -inv(J) hat(beta_j), beta_j the field rows ``rows`` = (lo, hi) — ints or
+    (T,) arrays, default the whole table — rotated into the goal's body frame; P of A'P + P A - P G P + diag(qd) = 0 on the
+    double integrator with G = blockdiag(0, Gamma); Kg = alpha inv(J) P[3:6, :] (include/tortoise_hip.h; the reference's
+    src/comparison/psiaki_dynamics.jl:75-125). ``qd`` (T, 6) or (6,) weights [theta (3); dw (3)], ``rd`` (T, 3) or (3,), ``alpha``
+    scalar or (T,). Returns (Kg (T, 6, 3), info) with info = dict(status, iterations, residual, pivot_min (T,) each, P (T, 6, 6),
+    Gamma (T, 3, 3)). A non-zero status (1 not converged, 2 singular elimination, 3 residual > res_tol) raises unless
+    ``allow_failed``; the Kg and P of such a slew are zero."""
+    lib = _abi.load()
+    T = batch.T
+    c = lambda a, shape: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape))
+    qd, rd, alpha = c(qd, (T, 6)), c(rd, (T, 3)), c(alpha, (T,))
+    lo = hi = None
+    if rows is not None:
+        lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v), (T,)), dtype=np.int32) for v in rows)
+    Kg, P, Gm = np.zeros((T, 6, 3)), np.zeros((T, 6, 6)), np.zeros((T, 3, 3))
+    info = np.zeros(T, dtype=_abi.APLQR_INFO_DTYPE)
+    d = _abi.as_dp
+    rc = lib.tsat_aplqr_gains(solver._h, T, batch.Btab.shape[0], batch.n_tab, d(batch.xf), d(batch.Btab), _abi.as_ip(batch.btab_idx),
+                              _abi.as_ip(lo), _abi.as_ip(hi), d(batch.Jmat), d(qd), d(rd), d(alpha), float(res_tol), d(Kg), d(P), d(Gm),
+                              info.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise RuntimeError(f"tsat_aplqr_gains failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
+    if info["status"].any() and not allow_failed:
+        t = int(np.flatnonzero(info["status"])[0])
+        raise RuntimeError(f"tsat_aplqr_gains: slew {t} has status {int(info['status'][t])} after {int(info['iterations'][t])} iterations "
+                           f"(residual {float(info['residual'][t]):.2e}, smallest pivot {float(info['pivot_min'][t]):.2e})")
+    return Kg, dict(status=info["status"].copy(), iterations=info["iterations"].copy(), residual=info["residual"].copy(),
+                    pivot_min=info["pivot_min"].copy(), P=P, Gamma=Gm)
+
+
+def attitude_ensemble_aplqr(solver, batch: SlewBatch, x0_sim, Kg, rd, noise_seed, X=None, U=None, plant=None, Rtab=None, gm=0.0, sat=None,
+                            limit_mode=0, x0_nom=None, noise_id0=None, want_trajectories=False, sigma_scale=1.0, u_scale=1e-2,
+                            min_steps=10, w_tol=0.05, angle_tol=0.08727):
+    """The asymptotic periodic LQR on the plants of ``attitude_ensemble_pd`` (``tsat_aplqr_ensemble``): per knot
+    m = -diag(1/rd) (b x Kg [theta; dw]) with theta = 2 s e the rotation-vector error, dw the rate error and b the body-frame field.
+    ``Kg`` (T, 6, 3) from ``aplqr_gains`` or the caller's own, ``rd`` (T, 3) or (3,). Every other keyword and the returned dict are
+    those of ``attitude_ensemble_pd``."""
+    return _pd_call(solver, batch, x0_sim, Kg, rd, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
+                    want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, aplqr=True)
 
 
 SENSOR_W = 9
