@@ -944,6 +944,77 @@ int  tsat_pd_ensemble_model_mag_filtered(tsat_handle* h, const tsat_tvlqr_option
                          const tsat_sensor_options* s, const double* sensor,
                          const tsat_model_mag_filter_options* f, double* X_hat, double* filt_final);
 
+/* The magnetometer-updated model filter WITH A SUN SENSOR THAT ECLIPSE BLINDS: the two model-mag-filtered calls above with a second
+ * body vector. One field vector does not observe the rotation about itself; a coarse sun sensor closes that gap while the satellite
+ * is lit and hands over nothing in the Earth's shadow (the reference loop of tests/model_mag_sun_filtered_common.py, the 400-knot
+ * case of the model-mag filter with a 0.5 deg sun sensor 35 deg from the field: rms attitude error over the last half 0.26 deg lit
+ * throughout and 0.66 deg when dark from knot 100 on, against 2.8 deg without the sun sensor).
+ * Stab (n_btab x n_tab x 3) is the sun table: the shape and the indexing of Btab — the same btab_idx, the same table clock; the row
+ * of knot j is s_j, the stage-0 row of that knot. A row is the sun direction in ECI where the satellite is lit (a unit vector in the
+ * intended use; the filter does not normalise it) and EXACTLY (0, 0, 0) where it is in shadow.
+ * The sensor: one sun sample per knot, s_m = qrot(x[3:7] / |x[3:7]|, s_k) + sigma_sun n_s, formed as the true body field is; n_s
+ * is the gyro triple of stage index 6 of the documented draw layout (Philox counter 24 of (gid, k)). sigma_sun >= 0 is
+ * launch-uniform and dimensionless (radians for small angles); it is an argument of the calls because tsat_sensor_options keeps its
+ * layout. There is NO per-realisation sun-sensor bias. Where the row is zero nothing is drawn and no sample exists. At latency 1 the
+ * delayed sample is paired with its own row s_{k-1}, not s_k. stats_nominal flies the ideal sensor (no draw) through the same filter.
+ * Options: those of tsat_model_mag_filter_options and
+ *   sigma_s   sun-sensor noise the filter assumes, dimensionless, > 0 when Stab is given; it has no default
+ * tsat_model_mag_sun_filter_default_options fills the parent's defaults and sigma_s = 0.
+ * The recursion of tsat_model_mag_filter_options applies unchanged — first, predict, the 58-value record, the latency rule —
+ * except that update(m_j), j >= 1, is three 3-vector updates in this order, each applying its whole 9-vector delta = K z:
+ *     a. magnetometer, b. gyro   the parent's, operation for operation
+ *     c. sun, ONLY IF s_j != 0   n = q^ / |q^|;  z = s_m - qrot(n, s_j);  Hs = -C(n) [s_j]x;
+ *                                P H^T = [A Hs^T; X^T Hs^T; B^T Hs^T];  S = Hs A Hs^T + sigma_s^2 I (its upper triangle,
+ *                                mirrored; positive definite because sigma_s > 0);  K = P H^T S^-1
+ *     then q^ <- normalise(q^ (x) [1; dtheta / 2]), w^ += dw, b^ += db;  P <- P - K S K^T, as after a. and b.
+ *   A dark knot SKIPS c. by a branch (uniform over the wavefront: the row is read by scalar loads), not by K = 0: the correction
+ *   renormalises q^, and a table dark throughout is the model-mag-filtered call bit for bit.
+ *   No sun update is made at sample 0 and none at k = 1 of latency 1, as for the magnetometer.
+ *   X_hat, filt_final (12, TSAT_MODEL_FILTER_W): the parent's.
+ * f == NULL is the sensed call, byte for byte (it is dispatched there); X_hat, filt_final and Stab must then be NULL and sigma_sun 0.
+ * Stab == NULL with f given is the model-mag-filtered call on the seven shared options, byte for byte (it is dispatched there);
+ * sigma_sun must then be 0 and sigma_s is not looked at.
+ * Rejected with -1 (text in tsat_ensemble_last_error; nothing is launched and no workspace grows): a non-finite or negative
+ * option; sigma_g == 0; sigma_m == 0; sigma_s == 0 with Stab given; a negative or non-finite sigma_sun; a non-finite Stab entry;
+ * reserved != 0; and everything the model-mag-filtered call rejects. The packed sun rows live in a grow-only workspace of the handle
+ * (tsat_workspace_bytes counts them, tsat_workspace_trim(h, 1) frees them). */
+struct tsat_model_mag_sun_filter_options {
+  double  sigma_v;
+  double  sigma_w;
+  double  sigma_u;
+  double  sigma_g;
+  double  sigma_m;
+  double  sigma_s;
+  double  p0_att;
+  double  p0_bias;
+  int32_t reserved;         /* 0 */
+};
+typedef struct tsat_model_mag_sun_filter_options tsat_model_mag_sun_filter_options;
+void tsat_model_mag_sun_filter_default_options(tsat_model_mag_sun_filter_options* f);
+int  tsat_tvlqr_ensemble_model_mag_sun_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                         const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* K_lqr, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor,
+                         const tsat_model_mag_sun_filter_options* f, double* X_hat, double* filt_final,
+                         const double* Stab, double sigma_sun);
+int  tsat_pd_ensemble_model_mag_sun_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                         const double* X, const double* U, const double* xf,
+                         const double* Btab, const int32_t* btab_idx, const double* tau0, const double* dtau,
+                         const double* dt, const double* Jmat,
+                         const double* kd, const double* kp, int32_t feedforward, int32_t limit_mode,
+                         const double* x0_sim, const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots,
+                         const double* plant, const double* sat_lo, const double* sat_hi,
+                         tsat_tvlqr_stats* stats, double* summary, tsat_tvlqr_stats* stats_nominal,
+                         double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                         const tsat_sensor_options* s, const double* sensor,
+                         const tsat_model_mag_sun_filter_options* f, double* X_hat, double* filt_final,
+                         const double* Stab, double sigma_sun);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Receding-horizon re-solve on the RESIDENT batch (BASELINE.json configs[4]). NOT in the reference —
  * it tracks its plan with TVLQR (src/attitude_controller.jl:1-48); defined here as: n_steps times

@@ -707,7 +707,11 @@ end
 # `tsat_model_mag_filter_options*` (seven Float64 — sigma_v, sigma_w, sigma_u, sigma_g, sigma_m, p0_att, p0_bias —, then Int32
 # reserved: 64 bytes with the tail padding): unbound likewise (tracking.attitude_ensemble_model_mag_filtered,
 # tracking.attitude_ensemble_pd_model_mag_filtered), and so is the held re-planning loop behind that filter
-# (mpc.receding_horizon_held_model_mag_filtered).
+# (mpc.receding_horizon_held_model_mag_filtered). The model-mag-sun-filtered ensembles take the sensor struct, a
+# `tsat_model_mag_sun_filter_options*` (eight Float64 — sigma_v, sigma_w, sigma_u, sigma_g, sigma_m, sigma_s, p0_att, p0_bias —,
+# then Int32 reserved: 72 bytes with the tail padding), and after filt_final the sun table `Stab` (3 x n_tab x n_btab, zero rows
+# in eclipse) and a Float64 sigma_sun: unbound likewise (tracking.attitude_ensemble_model_mag_sun_filtered,
+# tracking.attitude_ensemble_pd_model_mag_sun_filtered).
 const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsat_pd_ensemble_sensed, :tsat_mpc_run_held_sensed,
                  :tsat_filter_default_options, :tsat_tvlqr_ensemble_filtered, :tsat_pd_ensemble_filtered,
                  :tsat_mpc_run_held_filtered,
@@ -717,6 +721,8 @@ const UNBOUND = [:tsat_sensor_default_options, :tsat_tvlqr_ensemble_sensed, :tsa
                  :tsat_mag_bias_filter_default_options, :tsat_tvlqr_ensemble_mag_bias_filtered,
                  :tsat_pd_ensemble_mag_bias_filtered,
                  :tsat_model_mag_filter_default_options, :tsat_tvlqr_ensemble_model_mag_filtered,
-                 :tsat_pd_ensemble_model_mag_filtered, :tsat_mpc_run_held_model_mag_filtered]
+                 :tsat_pd_ensemble_model_mag_filtered, :tsat_mpc_run_held_model_mag_filtered,
+                 :tsat_model_mag_sun_filter_default_options, :tsat_tvlqr_ensemble_model_mag_sun_filtered,
+                 :tsat_pd_ensemble_model_mag_sun_filtered]
 
 end # module

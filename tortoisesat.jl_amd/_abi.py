@@ -133,6 +133,18 @@ class ModelMagFilterOptions(C.Structure):
 
 assert C.sizeof(ModelMagFilterOptions) == 64
 
+
+class ModelMagSunFilterOptions(C.Structure):
+    """``tsat_model_mag_sun_filter_options`` — ``ModelMagFilterOptions`` and ``sigma_s``, the sun-sensor noise the filter assumes
+    (dimensionless)."""
+
+    _fields_ = [("sigma_v", C.c_double), ("sigma_w", C.c_double), ("sigma_u", C.c_double), ("sigma_g", C.c_double),
+                ("sigma_m", C.c_double), ("sigma_s", C.c_double), ("p0_att", C.c_double), ("p0_bias", C.c_double),
+                ("reserved", C.c_int32)]
+
+
+assert C.sizeof(ModelMagSunFilterOptions) == 72
+
 TVLQR_STATS_DTYPE = np.dtype([("slew_index", "<i4"), ("failed", "<i4"), ("slew_time", "<f8"), ("final_w_norm", "<f8"),
                               ("final_angle", "<f8")])
 assert TVLQR_STATS_DTYPE.itemsize == 32
@@ -264,6 +276,17 @@ PROTOTYPES = {
                                                       _ip, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64),
                                                       _ip, _dp, _dp, _dp, C.c_void_p, _dp, C.c_void_p, _dp, _ip, _dp, C.c_double,
                                                       C.POINTER(SensorOptions), _dp, C.POINTER(ModelMagFilterOptions), _dp, _dp]),
+    "tsat_model_mag_sun_filter_default_options": (None, [C.POINTER(ModelMagSunFilterOptions)]),
+    "tsat_tvlqr_ensemble_model_mag_sun_filtered": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp,
+                                                             _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip,
+                                                             _dp, _dp, _dp, C.c_void_p, _dp, C.c_void_p, _dp, _dp, _ip, _dp, C.c_double,
+                                                             C.POINTER(SensorOptions), _dp, C.POINTER(ModelMagSunFilterOptions), _dp, _dp,
+                                                             _dp, C.c_double]),
+    "tsat_pd_ensemble_model_mag_sun_filtered": (C.c_int, [C.c_void_p, C.POINTER(TvlqrOptions), C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp,
+                                                          _dp, _ip, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp,
+                                                          C.POINTER(C.c_int64), _ip, _dp, _dp, _dp, C.c_void_p, _dp, C.c_void_p, _dp, _ip, _dp,
+                                                          C.c_double, C.POINTER(SensorOptions), _dp, C.POINTER(ModelMagSunFilterOptions), _dp,
+                                                          _dp, _dp, C.c_double]),
     "tsat_mpc_run_held_sensed": (C.c_int, [C.c_void_p, C.POINTER(Options), C.POINTER(TvlqrOptions), C.c_int32, C.c_int64, C.c_int32,
                                            C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_int64), _dp, _dp, C.c_void_p, C.c_void_p, _ip,
                                            C.POINTER(C.c_float), _dp, C.c_double, C.POINTER(SensorOptions), _dp, _dp]),

@@ -7,6 +7,7 @@
 #include "tsat_mag_filtered.hpp"
 #include "tsat_mag_bias_filtered.hpp"
 #include "tsat_model_mag_filtered.hpp"
+#include "tsat_model_mag_sun_filtered.hpp"
 
 // pack and roll-out of tsat_tvlqr_ensemble_gg (tsat_kernels_gg.hip)
 hipError_t tsat_launch_gg_pack(const double* R, double gm, double* GT, int64_t rows, hipStream_t stream);
@@ -32,3 +33,6 @@ hipError_t tsat_launch_mag_bias_filtered_pd(const tsat::MagBiasFilteredPdArgs<do
 // roll-outs of the model-mag-filtered calls (tsat_kernels_model_mag_filtered.hip)
 hipError_t tsat_launch_model_mag_filtered_tv(const tsat::ModelMagFilteredTvArgs<double>& a, int waves, hipStream_t stream);
 hipError_t tsat_launch_model_mag_filtered_pd(const tsat::ModelMagFilteredPdArgs<double>& a, int waves, hipStream_t stream);
+// roll-outs of the model-mag-sun-filtered calls (tsat_kernels_model_mag_sun_filtered.hip)
+hipError_t tsat_launch_model_mag_sun_filtered_tv(const tsat::ModelMagSunFilteredTvArgs<double>& a, int waves, hipStream_t stream);
+hipError_t tsat_launch_model_mag_sun_filtered_pd(const tsat::ModelMagSunFilteredPdArgs<double>& a, int waves, hipStream_t stream);

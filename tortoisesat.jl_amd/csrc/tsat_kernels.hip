@@ -155,6 +155,7 @@ struct tsat_handle {
          WS_MPCF_FL,           // tsat_mpc_run_held_filtered: the filter's records [31][T]
          WS_MPCMF_FL,          // tsat_mpc_run_held_model_filtered and _model_mag_filtered: the nine-state filter's records [58][T]
          WS_MPCMM_HB,          // tsat_mpc_run_held_model_mag_filtered: the last field sample [3][T]
+         WS_SUN_ST,            // packed sun rows of the model-mag-sun-filtered ensembles
          WS_COUNT };
   void* ws[WS_COUNT] = {};
   size_t ws_bytes[WS_COUNT] = {};
@@ -216,6 +217,8 @@ int dev_alloc(tsat_handle* h, Tp** p, size_t n) {
 // the packed gravity rows of the gravity-gradient entry points: the handle's grow-only slot, for the ensemble's translation
 // unit too (to which `struct tsat_handle` is opaque); nullptr on failure
 double* tsat_ws_gravity(tsat_handle* h, size_t bytes) { return (double*)ws_get(h, tsat_handle::WS_GG_GT, bytes); }
+// ... and the packed sun rows of the model-mag-sun-filtered ensembles, likewise
+double* tsat_ws_sun(tsat_handle* h, size_t bytes) { return (double*)ws_get(h, tsat_handle::WS_SUN_ST, bytes); }
 // the handle's GPU, for an entry point of that unit which makes no call into this one before it allocates (tsat_pd_ensemble)
 int tsat_handle_device(const tsat_handle* h) { return h->dev; }
 

@@ -1,6 +1,7 @@
-// tsat_kernels_ensemble.hip — the host side of the twenty ensemble entry points (include/tortoise_hip.h): tsat_tvlqr_ensemble and its
-// _dispersed, _gg, _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered, _model_mag_filtered, and tsat_pd_ensemble
-// with its _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered, _model_mag_filtered, and tsat_aplqr_ensemble (a PD
+// tsat_kernels_ensemble.hip — the host side of the twenty-two ensemble entry points (include/tortoise_hip.h): tsat_tvlqr_ensemble and its
+// _dispersed, _gg, _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered, _model_mag_filtered,
+// _model_mag_sun_filtered, and tsat_pd_ensemble with its _sensed, _filtered, _model_filtered, _mag_filtered, _mag_bias_filtered,
+// _model_mag_filtered, _model_mag_sun_filtered, and tsat_aplqr_ensemble (a PD
 // call with another law) with its synthesis tsat_aplqr_gains (run_aplqr_gains: no roll-out, a call of its own). A
 // translation unit of its own, built on the public ABI: `struct tsat_handle` is private to tsat_kernels.hip, so a call keeps its own
 // buffers and stream. An entry point only describes its call (`Call`: the common arrays, the part of its law, and what it adds —
@@ -34,6 +35,7 @@
 #include "tsat_mag_filtered.hpp"
 #include "tsat_mag_bias_filtered.hpp"
 #include "tsat_model_mag_filtered.hpp"
+#include "tsat_model_mag_sun_filtered.hpp"
 #include "tsat_ensemble_launch.hpp"
 #include "tsat_aplqr.hpp"
 
@@ -41,6 +43,7 @@ using namespace tsat;
 
 // the handle's workspace for the packed gravity rows, counted by tsat_workspace_bytes, and its GPU (tsat_kernels.hip)
 double* tsat_ws_gravity(tsat_handle* h, size_t bytes);
+double* tsat_ws_sun(tsat_handle* h, size_t bytes);             // ... and for the packed sun rows
 int tsat_handle_device(const tsat_handle* h);
 
 template <typename real, int DIAGJ>
@@ -146,17 +149,30 @@ struct Filtering {
   const tsat_mag_filter_options* gf = nullptr;     // ... or the magnetometer-updated one
   const tsat_mag_bias_filter_options* bf = nullptr;   // ... or the one that estimates the magnetometer bias too
   const tsat_model_mag_filter_options* mg = nullptr;  // ... or the nine-state filter updated by the magnetometer
+  const tsat_model_mag_sun_filter_options* ms = nullptr;   // ... or that one with the sun-vector update, against Stab
+  const double* Stab = nullptr;                       // n_btab x n_tab x 3, sun_rows rows
+  double sigma_sun = 0.0;
+  int64_t sun_rows = 0;
   std::string check() const {
+    if (ms) return check_model_mag_sun_filter(ms, Stab, sigma_sun, sun_rows);
     if (mg) return check_model_mag_filter(mg);
     return bf ? check_mag_bias_filter(bf) : (gf ? check_mag_filter(gf) : (mf ? check_model_filter(mf) : check_filter(f)));
   }
-  size_t final_w() const { return bf ? (size_t)MBFFW : ((mf || mg) ? (size_t)MFFW : (size_t)FFW); }
+  size_t final_w() const { return bf ? (size_t)MBFFW : ((mf || mg || ms) ? (size_t)MFFW : (size_t)FFW); }
 };
 
 // f == NULL is the sensed parent, which has no X_hat and no filt_final to fill
 bool unfiltered_outputs(const double* X_hat, const double* filt_final) {
   if (!X_hat && !filt_final) return false;
   g_err = "f is NULL (the sensed call): X_hat and filt_final must be NULL";
+  return true;
+}
+
+// ... and no sun table; without a sun table (the model-mag-filtered parent) there is no sun sensor to draw for
+bool no_sun_arguments(bool has_f, const double* Stab, double sigma_sun) {
+  const std::string bad = check_sun_arguments(has_f, Stab, sigma_sun);
+  if (bad.empty()) return false;
+  g_err = bad;
   return true;
 }
 
@@ -264,13 +280,15 @@ std::string check_pd_call(const Call& c) {
 // stage 6, one dispatch per law: the nested argument block inside-out, then the unit that holds its kernel.
 // d == null: tsat_tvlqr_ensemble (the kernel of the model's inertia class `cls`); GT == null: the plants without the gravity rows
 hipError_t launch_tvlqr(const EnsArgs<double>& a, const DispArgs<double>* d, const double* GT, const SensArgs<double>* sa,
-                        const Filtering* fl, double* dXH, double* dFF, int cls, int nw, hipStream_t st) {
+                        const Filtering* fl, double* dXH, double* dFF, const double* dST, int cls, int nw, hipStream_t st) {
   if (!d) {
     auto kern = cls == 2 ? tsat_ensemble_kernel<double, 2> : (cls == 1 ? tsat_ensemble_kernel<double, 1> : tsat_ensemble_kernel<double, 0>);
     hipLaunchKernelGGL(kern, dim3((unsigned)a.T, (unsigned)nw), dim3(64), 0, st, a);
     return hipGetLastError();
   }
   const GgEnsArgs<double> g{*d, GT};
+  if (fl && fl->ms)
+    return tsat_launch_model_mag_sun_filtered_tv({g, model_mag_sun_filt_args(*fl->ms, *sa, a, dXH, dFF, dST, fl->sigma_sun)}, nw, st);
   if (fl && fl->mg) return tsat_launch_model_mag_filtered_tv({g, model_mag_filt_args(*fl->mg, *sa, a, dXH, dFF)}, nw, st);
   if (fl && fl->bf) return tsat_launch_mag_bias_filtered_tv({g, mag_bias_filt_args(*fl->bf, *sa, a, dXH, dFF)}, nw, st);
   if (fl && fl->gf) return tsat_launch_mag_filtered_tv({g, mag_filt_args(*fl->gf, *sa, a, dXH, dFF)}, nw, st);
@@ -282,9 +300,11 @@ hipError_t launch_tvlqr(const EnsArgs<double>& a, const DispArgs<double>* d, con
   return hipGetLastError();
 }
 
-hipError_t launch_pd(const PdArgs<double>& pa, const SensArgs<double>* sa, const Filtering* fl, double* dXH, double* dFF, int nw,
-                     hipStream_t st, bool aplqr) {
+hipError_t launch_pd(const PdArgs<double>& pa, const SensArgs<double>* sa, const Filtering* fl, double* dXH, double* dFF,
+                     const double* dST, int nw, hipStream_t st, bool aplqr) {
   if (aplqr) return tsat_launch_aplqr(pa, nw, st);             // GAIN holds [T][AQGW]; no sensed or filtered variant
+  if (fl && fl->ms)
+    return tsat_launch_model_mag_sun_filtered_pd({pa, model_mag_sun_filt_args(*fl->ms, *sa, pa.d.e, dXH, dFF, dST, fl->sigma_sun)}, nw, st);
   if (fl && fl->mg) return tsat_launch_model_mag_filtered_pd({pa, model_mag_filt_args(*fl->mg, *sa, pa.d.e, dXH, dFF)}, nw, st);
   if (fl && fl->bf) return tsat_launch_mag_bias_filtered_pd({pa, mag_bias_filt_args(*fl->bf, *sa, pa.d.e, dXH, dFF)}, nw, st);
   if (fl && fl->gf) return tsat_launch_mag_filtered_pd({pa, mag_filt_args(*fl->gf, *sa, pa.d.e, dXH, dFF)}, nw, st);
@@ -388,6 +408,9 @@ int run_call(const Call& c) {
   double *dXH = nullptr, *dFF = nullptr;
   if (ok && filt && filt->X_hat) ok = s.alloc(&dXH, nS * N * 7);
   if (ok && filt && filt->filt_final) ok = s.alloc(&dFF, nS * filt->final_w());
+  // the sun call: the raw sun table is the call's, the packed rows are the handle's
+  double *dS = nullptr, *dST = nullptr;
+  if (ok && filt && filt->ms) ok = s.alloc(&dS, nB * 3) && (dST = tsat_ws_sun(c.h, nB * 4 * 8)) != nullptr;
   if (!ok) return efail(-10, std::string("device allocation failed in ") + ((c.pd && !aplqr) ? "tsat_pd_ensemble" : c.name));
   ENS_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
   for (hipEvent_t& e : s.ev) ENS_HIP(hipEventCreate(&e));
@@ -432,6 +455,11 @@ int run_call(const Call& c) {
     if (sens->sensor) ENS_HIP(hipMemcpy(dSens, sens->sensor, nS * SNW * 8, hipMemcpyHostToDevice));
     ENS_HIP(tsat_launch_sensed_pack(dSens, dSN, T, M, Mp, s.stream));
   }
+  if (dST) {                                                 // sun rows [rows][3] -> [rows][4]: the pack of the field rows
+    ENS_HIP(hipMemcpy(dS, filt->Stab, nB * 3 * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(tsat_ensemble_pack_bt_kernel, dim3((unsigned)((nB + 255) / 256)), dim3(256), 0, s.stream, (int64_t)nB, dS, dST);
+    ENS_HIP(hipGetLastError());
+  }
   if (dXH) ENS_HIP(hipMemsetAsync(dXH, 0, nS * N * 7 * 8, s.stream));   // the last row of every horizon and all beyond it stay zero
   ENS_HIP(hipEventRecord(s.ev[0], s.stream));
   // ---- 5. the gains kernel (TVLQR): one wavefront per slew runs the gain half of the tracking kernel ------------------
@@ -449,9 +477,9 @@ int run_call(const Call& c) {
     const DispArgs<double> d{a, dPL, Mp, dSat, dClip};
     SensArgs<double> sa;
     if (sens) sa = sens_args(*sens->s, *o, dSN, Mp);
-    if (c.tv) ENS_HIP(launch_tvlqr(a, disp ? &d : nullptr, dGT, sens ? &sa : nullptr, filt, dXH, dFF, cls, nw, s.stream));
-    else ENS_HIP(launch_pd({d, dGT, dGain, dX0N, c.pd->feedforward, c.pd->limit_mode}, sens ? &sa : nullptr, filt, dXH, dFF, nw, s.stream,
-                         aplqr));
+    if (c.tv) ENS_HIP(launch_tvlqr(a, disp ? &d : nullptr, dGT, sens ? &sa : nullptr, filt, dXH, dFF, dST, cls, nw, s.stream));
+    else ENS_HIP(launch_pd({d, dGT, dGain, dX0N, c.pd->feedforward, c.pd->limit_mode}, sens ? &sa : nullptr, filt, dXH, dFF, dST, nw,
+                         s.stream, aplqr));
   }
   ENS_HIP(hipEventRecord(s.ev[c.tv ? 2 : 1], s.stream));
   if (K_lqr) {
@@ -900,6 +928,76 @@ int tsat_tvlqr_ensemble_model_mag_filtered(tsat_handle* h, const tsat_tvlqr_opti
   Call c{f ? "tsat_tvlqr_ensemble_model_mag_filtered" : "tsat_tvlqr_ensemble_sensed", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0,
          dtau, dt, Jmat, x0_sim, noise_id0, n_knots, stats, summary, stats_nominal, X_sim};
   c.tv = &law; c.disp = &d; c.grav = &g; c.sens = &se; c.filt = f ? &fl : nullptr;
+  return run_call(c);
+}
+
+void tsat_model_mag_sun_filter_default_options(tsat_model_mag_sun_filter_options* f) {
+  if (!f) return;
+  tsat_model_mag_filter_options g;
+  tsat_model_mag_filter_default_options(&g);
+  f->sigma_v = g.sigma_v; f->sigma_w = g.sigma_w; f->sigma_u = g.sigma_u; f->sigma_g = g.sigma_g; f->sigma_m = g.sigma_m;
+  f->sigma_s = 0.0;                                            // the caller's sensor: no default, and 0 is rejected with a sun table
+  f->p0_att = g.p0_att; f->p0_bias = g.p0_bias;
+  f->reserved = 0;
+}
+
+int tsat_tvlqr_ensemble_model_mag_sun_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                                               const double* X, const double* U, const double* xf, const double* Btab,
+                                               const int32_t* btab_idx, const double* tau0, const double* dtau, const double* dt,
+                                               const double* Jmat, const double* Qd, const double* Qfd, const double* Rd,
+                                               const double* x0_sim, const int64_t* noise_id0, const int32_t* n_knots, const double* plant,
+                                               const double* sat_lo, const double* sat_hi, tsat_tvlqr_stats* stats, double* summary,
+                                               tsat_tvlqr_stats* stats_nominal, double* K_lqr, double* X_sim, int32_t* n_clipped,
+                                               const double* Rtab, double gm, const tsat_sensor_options* sn, const double* sensor,
+                                               const tsat_model_mag_sun_filter_options* f, double* X_hat, double* filt_final,
+                                               const double* Stab, double sigma_sun) {
+  if (no_sun_arguments(f != nullptr, Stab, sigma_sun)) return -1;
+  if (!Stab) {   // no sun table: the parent on the seven shared options (f == NULL: its sensed call), byte for byte
+    tsat_model_mag_filter_options g;
+    if (f) g = model_mag_options_of(*f);
+    return tsat_tvlqr_ensemble_model_mag_filtered(h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, Qd, Qfd, Rd, x0_sim,
+                                                  noise_id0, n_knots, plant, sat_lo, sat_hi, stats, summary, stats_nominal, K_lqr, X_sim,
+                                                  n_clipped, Rtab, gm, sn, sensor, f ? &g : nullptr, X_hat, filt_final);
+  }
+  const TvlqrPart law{Qd, Qfd, Rd, K_lqr};
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  const Sensing se{sn, sensor};
+  Filtering fl{nullptr, X_hat, filt_final};
+  fl.ms = f; fl.Stab = Stab; fl.sigma_sun = sigma_sun; fl.sun_rows = o ? n_btab * (int64_t)o->n_tab : 0;
+  Call c{"tsat_tvlqr_ensemble_model_mag_sun_filtered", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, x0_sim, noise_id0,
+         n_knots, stats, summary, stats_nominal, X_sim};
+  c.tv = &law; c.disp = &d; c.grav = &g; c.sens = &se; c.filt = &fl;
+  return run_call(c);
+}
+
+int tsat_pd_ensemble_model_mag_sun_filtered(tsat_handle* h, const tsat_tvlqr_options* o, int64_t T, int64_t n_btab, int32_t M,
+                                            const double* X, const double* U, const double* xf, const double* Btab, const int32_t* btab_idx,
+                                            const double* tau0, const double* dtau, const double* dt, const double* Jmat, const double* kd,
+                                            const double* kp, int32_t feedforward, int32_t limit_mode, const double* x0_sim,
+                                            const double* x0_nom, const int64_t* noise_id0, const int32_t* n_knots, const double* plant,
+                                            const double* sat_lo, const double* sat_hi, tsat_tvlqr_stats* stats, double* summary,
+                                            tsat_tvlqr_stats* stats_nominal, double* X_sim, int32_t* n_clipped, const double* Rtab, double gm,
+                                            const tsat_sensor_options* sn, const double* sensor,
+                                            const tsat_model_mag_sun_filter_options* f, double* X_hat, double* filt_final,
+                                            const double* Stab, double sigma_sun) {
+  if (no_sun_arguments(f != nullptr, Stab, sigma_sun)) return -1;
+  if (!Stab) {   // no sun table: the parent on the seven shared options (f == NULL: its sensed call), byte for byte
+    tsat_model_mag_filter_options g;
+    if (f) g = model_mag_options_of(*f);
+    return tsat_pd_ensemble_model_mag_filtered(h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, kd, kp, feedforward,
+                                               limit_mode, x0_sim, x0_nom, noise_id0, n_knots, plant, sat_lo, sat_hi, stats, summary,
+                                               stats_nominal, X_sim, n_clipped, Rtab, gm, sn, sensor, f ? &g : nullptr, X_hat, filt_final);
+  }
+  const PdPart law{kd, kp, feedforward, limit_mode, x0_nom};
+  const Dispersion d{plant, sat_lo, sat_hi, n_clipped};
+  const Gravity g{Rtab, gm};
+  const Sensing se{sn, sensor};
+  Filtering fl{nullptr, X_hat, filt_final};
+  fl.ms = f; fl.Stab = Stab; fl.sigma_sun = sigma_sun; fl.sun_rows = o ? n_btab * (int64_t)o->n_tab : 0;
+  Call c{"tsat_pd_ensemble_model_mag_sun_filtered", h, o, T, n_btab, M, X, U, xf, Btab, btab_idx, tau0, dtau, dt, Jmat, x0_sim, noise_id0,
+         n_knots, stats, summary, stats_nominal, X_sim};
+  c.pd = &law; c.disp = &d; c.grav = &g; c.sens = &se; c.filt = &fl;
   return run_call(c);
 }
 

@@ -46,6 +46,45 @@ def orbit_rows(pos, n_tab):
     return np.ascontiguousarray(pos[:, :int(n_tab)])
 
 
+def sun_direction(mjd, au=False):
+    """The sun vector in ECI (mean equator of date) at modified Julian date ``mjd`` (a scalar or an array; the result is (3,) or
+    (..., 3)) from the low-precision almanac series, with T the Julian centuries from J2000: mean longitude 280.460 + 36000.771 T,
+    mean anomaly M = 357.5291092 + 35999.05034 T, ecliptic longitude = mean longitude + 1.914666471 sin M + 0.019994643 sin 2M,
+    obliquity 23.439291 - 0.0130042 T (degrees); good to about 0.01 deg over 1950-2050. A unit vector; ``au=True`` scales it by the
+    series' distance 1.000140612 - 0.016708617 cos M - 0.000139589 cos 2M (astronomical units)."""
+    T = (np.asarray(mjd, dtype=np.float64) + 2400000.5 - 2451545.0) / 36525.0
+    lm = 280.460 + 36000.771 * T
+    M = np.radians(357.5291092 + 35999.05034 * T)
+    lam = np.radians(lm + 1.914666471 * np.sin(M) + 0.019994643 * np.sin(2.0 * M))
+    eps = np.radians(23.439291 - 0.0130042 * T)
+    s = np.stack([np.cos(lam), np.cos(eps) * np.sin(lam), np.sin(eps) * np.sin(lam)], axis=-1)
+    if au:
+        s = s * (1.000140612 - 0.016708617 * np.cos(M) - 0.000139589 * np.cos(2.0 * M))[..., None]
+    return s
+
+
+def sun_rows(Rtab, mjd, R_E=6371.0):
+    """The sun table ``Stab`` (n_btab, n_tab, 3) of the model-mag-sun-filtered ensembles (``tracking.attitude_ensemble_model_mag_sun_filtered``)
+    from the orbit rows ``Rtab`` (n_btab, n_tab, 3) km of ``orbit_rows``: row i is ``sun_direction`` where the satellite at orbit row
+    i is lit and exactly zero where it is in the cylindrical shadow of the Earth — r . s < 0 and |r - (r . s) s| < R_E. ``mjd`` is a
+    scalar or (n_btab,): the direction is CONSTANT PER TABLE (the sun moves 0.04 deg per hour, far below a coarse sun sensor's noise
+    over a slew). Penumbra and albedo are left out."""
+    R = np.asarray(Rtab, dtype=np.float64)
+    if R.ndim != 3 or R.shape[2] != 3:
+        raise ValueError("Rtab must be (n_btab, n_tab, 3)")
+    mjd = np.asarray(mjd, dtype=np.float64)
+    if mjd.ndim > 1 or (mjd.ndim == 1 and mjd.shape != (R.shape[0],)) or not np.all(np.isfinite(mjd)):
+        raise ValueError("mjd must be a finite scalar or (n_btab,)")
+    if not np.all(np.isfinite(R)) or not float(R_E) > 0.0:
+        raise ValueError("Rtab must be finite and R_E positive")
+    s = np.broadcast_to(sun_direction(mjd), (R.shape[0], 3))[:, None, :]
+    along = np.sum(R * s, axis=2, keepdims=True)
+    dark = (along[..., 0] < 0.0) & (np.linalg.norm(R - along * s, axis=2) < float(R_E))
+    S = np.ascontiguousarray(np.broadcast_to(s, R.shape))
+    S[dark] = 0.0
+    return S
+
+
 def attach_igrf_tables(solver, batch, kep=None, chunk=4096):
     """Replace the field tables of a workload batch by IGRF-12 tables generated on the GPU for its orbits — what the
     reference does before every solve (``magnetic_simulation(A[i,:], t0, t_final, N, ...)``, src/monte_carlo.jl:149): one

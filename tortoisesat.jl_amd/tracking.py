@@ -372,11 +372,12 @@ def attitude_ensemble_pd(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X
 
 
 def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0, want_trajectories,
-             sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=None, filtering=None, aplqr=False):
+             sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=None, filtering=None, aplqr=False, sun=None):
     """``tsat_pd_ensemble`` — with ``aplqr`` ``tsat_aplqr_ensemble``, ``kd`` being Kg (T, 6, 3) and ``kp`` rd —, or with ``sensing`` = (SensorOptions, sensor array or None) ``tsat_pd_ensemble_sensed``, or with
     ``filtering`` = (FilterOptions, X_hat or None, filt_final or None) besides ``tsat_pd_ensemble_filtered`` — with ModelFilterOptions
     in its place ``tsat_pd_ensemble_model_filtered``, with MagFilterOptions ``tsat_pd_ensemble_mag_filtered``, with
-    MagBiasFilterOptions ``tsat_pd_ensemble_mag_bias_filtered``, with ModelMagFilterOptions ``tsat_pd_ensemble_model_mag_filtered``"""
+    MagBiasFilterOptions ``tsat_pd_ensemble_mag_bias_filtered``, with ModelMagFilterOptions ``tsat_pd_ensemble_model_mag_filtered``,
+    with ModelMagSunFilterOptions and ``sun`` = (Stab or None, sigma_sun) ``tsat_pd_ensemble_model_mag_sun_filtered``"""
     lib = _abi.load()
     T, N = batch.T, batch.N
     c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
@@ -435,8 +436,10 @@ def _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, s
     elif filtering is not None:
         name = {_abi.ModelFilterOptions: "tsat_pd_ensemble_model_filtered", _abi.MagFilterOptions: "tsat_pd_ensemble_mag_filtered",
                 _abi.MagBiasFilterOptions: "tsat_pd_ensemble_mag_bias_filtered",
-                _abi.ModelMagFilterOptions: "tsat_pd_ensemble_model_mag_filtered"}.get(type(filtering[0]), "tsat_pd_ensemble_filtered")
-        rc = getattr(lib, name)(*args, C.byref(sensing[0]), d(sensing[1]), C.byref(filtering[0]), d(filtering[1]), d(filtering[2]))
+                _abi.ModelMagFilterOptions: "tsat_pd_ensemble_model_mag_filtered",
+                _abi.ModelMagSunFilterOptions: "tsat_pd_ensemble_model_mag_sun_filtered"}.get(type(filtering[0]), "tsat_pd_ensemble_filtered")
+        rc = getattr(lib, name)(*args, C.byref(sensing[0]), d(sensing[1]), C.byref(filtering[0]), d(filtering[1]), d(filtering[2]),
+                                *([] if sun is None else [d(sun[0]), float(sun[1])]))
     else:
         name, rc = "tsat_pd_ensemble_sensed", lib.tsat_pd_ensemble_sensed(*args, C.byref(sensing[0]), d(sensing[1]))
     if rc != 0:
@@ -618,9 +621,9 @@ def attitude_ensemble_filtered(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, 
 
 def _tv_filtered_call(name, filtering, solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant, Rtab, gm, sat, sensor, sigma_gyro,
                       sigma_att, sigma_mag, latency, noise_id0, sigma_scale, want_K, want_trajectories, linearize_dt_sq, u_scale,
-                      min_steps, w_tol, angle_tol, filter, want_estimates):
+                      min_steps, w_tol, angle_tol, filter, want_estimates, sun=None):
     """``tsat_tvlqr_ensemble_filtered`` or ``tsat_tvlqr_ensemble_model_filtered`` (``name``), ``filtering`` the function that makes
-    the call's (options, X_hat, filt_final)"""
+    the call's (options, X_hat, filt_final); ``sun`` = (Stab or None, sigma_sun): the two arguments a sun-sensor call ends with"""
     lib, head, tail, out = _ensemble_call(solver, batch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, noise_id0, sigma_scale, want_K,
                                           want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol)
     T, M = out["stats"].shape
@@ -638,7 +641,7 @@ def _tv_filtered_call(name, filtering, solver, batch, X, U, x0_sim, Qd, Qfd, Rd,
     ncl = np.zeros((T, M), dtype=np.int32)
     d = _abi.as_dp
     rc = getattr(lib, name)(*head, d(plant), d(lo), d(hi), *tail, _abi.as_ip(ncl), d(Rtab), float(gm), C.byref(so), d(sensor),
-                            C.byref(fo), d(Xh), d(ff))
+                            C.byref(fo), d(Xh), d(ff), *([] if sun is None else [d(sun[0]), float(sun[1])]))
     if rc != 0:
         raise RuntimeError(f"{name} failed rc={rc}: {lib.tsat_ensemble_last_error().decode()}")
     return dict(out, n_clipped=ncl, X_hat=Xh, filt_final=ff)
@@ -891,4 +894,70 @@ def attitude_ensemble_pd_model_mag_filtered(solver, batch: SlewBatch, x0_sim, kd
     fo, Xh, ff = _model_mag_filtering(T, M, batch.N, filter, want_estimates)
     out = _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
                    want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing, filtering=(fo, Xh, ff))
+    return dict(out, X_hat=Xh, filt_final=ff)
+
+
+def model_mag_sun_filter_options(sigma_w, sigma_g, sigma_m, sigma_s, sigma_v=0.0, sigma_u=0.0, p0_att=None, p0_bias=0.0):
+    """The ``tsat_model_mag_sun_filter_options`` of the model-mag-sun-filtered ensembles: ``model_mag_filter_options`` and the
+    sun-sensor noise the filter assumes, ``sigma_s`` (dimensionless, radians for small angles, > 0; it has no default)."""
+    g = model_mag_filter_options(sigma_w, sigma_g, sigma_m, sigma_v, sigma_u, p0_att, p0_bias)
+    if not (np.isfinite(sigma_s) and float(sigma_s) > 0.0):
+        raise ValueError("sigma_s must be finite and positive")
+    return _abi.ModelMagSunFilterOptions(sigma_v=g.sigma_v, sigma_w=g.sigma_w, sigma_u=g.sigma_u, sigma_g=g.sigma_g, sigma_m=g.sigma_m,
+                                         sigma_s=float(sigma_s), p0_att=g.p0_att, p0_bias=g.p0_bias, reserved=0)
+
+
+def _model_mag_sun_filtering(T, M, N, filter, want_estimates):
+    """(ModelMagSunFilterOptions, X_hat (T, M, N, 7) or None, filt_final (T, M, 12)) of a model-mag-sun-filtered call"""
+    if not isinstance(filter, _abi.ModelMagSunFilterOptions):
+        raise ValueError("filter must come from model_mag_sun_filter_options(): sigma_w, sigma_m and sigma_s have no default")
+    return filter, (np.empty((T, M, N, 7)) if want_estimates else None), np.empty((T, M, MODEL_MAG_FILTER_W))
+
+
+def _sun(batch, Stab, sigma_sun):
+    """(Stab (n_btab, n_tab, 3) contiguous or None, sigma_sun) of a model-mag-sun-filtered call"""
+    if Stab is None:
+        if float(sigma_sun) != 0.0:
+            raise ValueError("sigma_sun needs the sun table Stab")
+        return None, 0.0
+    Stab = np.ascontiguousarray(Stab, dtype=np.float64)
+    if Stab.shape != (batch.Btab.shape[0], batch.n_tab, 3):
+        raise ValueError("Stab must be (n_btab, n_tab, 3), indexed like the first n_tab rows of the field tables")
+    if not (np.isfinite(sigma_sun) and float(sigma_sun) >= 0.0):
+        raise ValueError("sigma_sun must be finite and not negative")
+    return Stab, float(sigma_sun)
+
+
+def attitude_ensemble_model_mag_sun_filtered(solver, batch: SlewBatch, X, U, x0_sim, Qd, Qfd, Rd, noise_seed, plant=None, Rtab=None,
+                                             gm=0.0, sat=None, sensor=None, sigma_gyro=0.0, sigma_att=0.0, sigma_mag=0.0, latency=0,
+                                             noise_id0=None, sigma_scale=1.0, want_K=False, want_trajectories=False, linearize_dt_sq=True,
+                                             u_scale=1e-2, min_steps=10, w_tol=0.05, angle_tol=0.08727, filter=None, want_estimates=False,
+                                             Stab=None, sigma_sun=0.0):
+    """``attitude_ensemble_model_mag_filtered`` with a SUN SENSOR (``tsat_tvlqr_ensemble_model_mag_sun_filtered``): per knot one sun
+    sample at noise ``sigma_sun`` (dimensionless) against the sun table ``Stab`` (n_btab, n_tab, 3; ``magnetic.sun_rows``), whose
+    zero rows are eclipse — no sample and no update there; the recursion is in include/tortoise_hip.h. ``filter`` from
+    ``model_mag_sun_filter_options`` (required). ``Stab`` None is the model-mag-filtered call. Returns its dict."""
+    return _tv_filtered_call("tsat_tvlqr_ensemble_model_mag_sun_filtered", _model_mag_sun_filtering, solver, batch, X, U, x0_sim, Qd, Qfd,
+                             Rd, noise_seed, plant, Rtab, gm, sat, sensor, sigma_gyro, sigma_att, sigma_mag, latency, noise_id0,
+                             sigma_scale, want_K, want_trajectories, linearize_dt_sq, u_scale, min_steps, w_tol, angle_tol, filter,
+                             want_estimates, sun=_sun(batch, Stab, sigma_sun))
+
+
+def attitude_ensemble_pd_model_mag_sun_filtered(solver, batch: SlewBatch, x0_sim, kd, kp, noise_seed, X=None, U=None, plant=None,
+                                                Rtab=None, gm=0.0, sat=None, limit_mode=0, x0_nom=None, sensor=None, sigma_gyro=0.0,
+                                                sigma_att=0.0, sigma_mag=0.0, latency=0, noise_id0=None, want_trajectories=False,
+                                                sigma_scale=1.0, u_scale=1e-2, min_steps=10, w_tol=0.05, angle_tol=0.08727, filter=None,
+                                                want_estimates=False, Stab=None, sigma_sun=0.0):
+    """``attitude_ensemble_pd_model_mag_filtered`` with the sun sensor of ``attitude_ensemble_model_mag_sun_filtered``
+    (``tsat_pd_ensemble_model_mag_sun_filtered``). Returns the dict of ``attitude_ensemble_pd_sensed`` plus ``X_hat`` and
+    ``filt_final`` as there."""
+    x0 = np.asarray(x0_sim)
+    if x0.ndim != 3:
+        raise ValueError("x0_sim must be (T, M, 7)")
+    T, M = batch.T, x0.shape[1]
+    sensing = _sensing(T, M, sensor, sigma_gyro, sigma_att, sigma_mag, latency)
+    fo, Xh, ff = _model_mag_sun_filtering(T, M, batch.N, filter, want_estimates)
+    out = _pd_call(solver, batch, x0_sim, kd, kp, noise_seed, X, U, plant, Rtab, gm, sat, limit_mode, x0_nom, noise_id0,
+                   want_trajectories, sigma_scale, u_scale, min_steps, w_tol, angle_tol, sensing=sensing, filtering=(fo, Xh, ff),
+                   sun=_sun(batch, Stab, sigma_sun))
     return dict(out, X_hat=Xh, filt_final=ff)
